@@ -29,7 +29,12 @@ every block).  cfg4/cfg5: the fixed batch is split by
 zfec_amd.shard.shard_range (strong scaling).  The only collectives are the timing barrier and the
 max/sum reductions.
 
-Also reported: the dominant kernel's roofline (encode: (k+r)*sz*stripes
+A plain run sets up, warms up, times the steps and prints the result line
+(--dump-outputs DIR: it also writes the last timed step's parity and recovered
+blocks as DIR/<name>.npy; the inputs come from a fixed seed, so two builds can
+be compared output for output).  Everything below runs only with --full.
+
+Also reported (--full): the dominant kernel's roofline (encode: (k+r)*sz*stripes
 algorithmic HBM bytes per launch / average launch duration over back-to-back
 launches between two HIP events on the launch stream; PMC traffic from
 profiles/pmc_summary.json), the decode kernel's, a batched 1 MiB-stripe
@@ -119,6 +124,9 @@ WORKLOADS = {
     "cfg5": (3, 10, 4 << 10, 1000000, "strong"),
 }
 
+# --dump-outputs: values written per array over all ranks (float32: 16 MiB for each of the two arrays)
+DUMP_MAX_VALUES = 4 << 20
+
 
 def parse():
     p = argparse.ArgumentParser()
@@ -127,11 +135,20 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS) + ["first_seen"],
                    help="first_seen: only the first_seen_decode leg (cfg4's shape), for the counter runs")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg: per-kernel rooflines (warm / cold "
+                        "back-to-back launches, event pairs), fresh-pattern decodes, the batched 1 MiB-stripe and "
+                        "first-seen legs (cfg2) and the CPU baselines.  Without it the run sets up, warms up, times "
+                        "the steps and prints the headline line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what their last step computed (the parity blocks of the encode, "
+                        "the blocks recovered by the decode) as DIR/<name>.npy in float32; outputs above "
+                        "%d values are written as a fixed, seeded sample of their bytes" % DUMP_MAX_VALUES)
     p.add_argument("--no-first-seen", action="store_true",
-                   help="cfg2: skip the first_seen_decode leg (first-seen erasure patterns at cfg4's shape)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+                   help="--full, cfg2: skip the first_seen_decode leg (first-seen erasure patterns at cfg4's shape)")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
-    p.add_argument("--no-extra", action="store_true", help="skip the 1 MiB-stripe batched leg")
+    p.add_argument("--no-extra", action="store_true", help="--full: skip the 1 MiB-stripe batched leg")
     p.add_argument("--layout", default="256", choices=["odd128", "256"],
                    help="block row stride in HBM: 256-byte multiple (default) or an odd number of 128-byte lines")
     p.add_argument("--no-row-padding", action="store_true",
@@ -598,8 +615,42 @@ def back_to_back(fns, n, stream, leg):
     return a.elapsed_time(b) / n, host_us
 
 
+def dump_positions(n, limit=DUMP_MAX_VALUES):
+    """The byte positions --dump-outputs writes of an output of n bytes: None
+    (all of them) up to `limit`, else that many positions drawn from a fixed
+    seed, sorted."""
+    if n <= limit:
+        return None
+    return np.sort(np.random.default_rng(64).integers(0, n, size=limit, dtype=np.int64))
+
+
+def dump_outputs(dirname, arrays, sz, rank=0, world=1):
+    """--dump-outputs: a step's outputs as DIR/<name>.npy (float32, one value
+    per byte; <name>_rank<r>.npy with several ranks).  arrays: name -> uint8
+    tensor [stripe][block][row stride], of which the first sz bytes of a row
+    are the caller's.  An output of more than DUMP_MAX_VALUES bytes (divided
+    among the ranks) is written as a sample of them (dump_positions: positions
+    in the [stripe][block][sz] bytes without the row padding), so runs with the
+    same arguments write the same positions."""
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        ns, nb, ld = t.shape
+        n = ns * nb * sz
+        pos = dump_positions(n, DUMP_MAX_VALUES // world)
+        if pos is None:
+            vals = t[:, :, :sz].reshape(-1)
+        else:
+            flat = (pos // sz) * ld + pos % sz  # position in the padded rows
+            vals = t.reshape(-1)[torch.from_numpy(flat).to(t.device)]
+        fname = name + ("" if world == 1 else "_rank%d" % rank) + ".npy"
+        np.save(os.path.join(dirname, fname), vals.to(torch.float32).cpu().numpy())
+        written[fname] = {"values": int(vals.numel()), "of": n}
+    return written
+
+
 def run_workload(k, m, sz, ns, steps, warmup, dist, use_graph=False, layout="256", row_padding=True, fresh=0,
-                 streams=1, paired=False):
+                 streams=1, paired=False, full=False, dump_dir=None):
     """Encode + decode `ns` stripes per step; returns timings.
 
     HBM layout: [stripe][block][row_stride] with the row stride = sz rounded up
@@ -616,9 +667,10 @@ def run_workload(k, m, sz, ns, steps, warmup, dist, use_graph=False, layout="256
     # decode from the last k blocks (all secondaries when m >= 2k); primaries at their slot
     slots = place(list(range(m - k, m)), k)
     nrec = sum(1 for s in slots if s >= k)
-    # rotation sets for the cold legs: set 0 is the timed loop's
+    # rotation sets for the cold legs (--full): set 0 is the timed loop's.  A plain run keeps
+    # two, so that set-up still launches every matrix twice (see capi.jit_wait() below)
     enc_fp, dec_fp = (k + r) * ld * ns, (k + nrec) * ld * ns
-    nsets = max(2, -(-COLD_SPAN // min(enc_fp, dec_fp)))
+    nsets = max(2, -(-COLD_SPAN // min(enc_fp, dec_fp))) if full else 2
     data = [torch.randint(0, 256, (ns, k, ld), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(nsets)]
     par = [torch.empty((ns, r, ld), dtype=torch.uint8, device="cuda") for _ in range(nsets)]
     recv = [torch.empty((ns, k, ld), dtype=torch.uint8, device="cuda") for _ in range(nsets)]  # slot order
@@ -768,6 +820,14 @@ def run_workload(k, m, sz, ns, steps, warmup, dist, use_graph=False, layout="256
     elif paired:
         for _ in range(steps):
             LEGS.add("timed loop", kernels["step"])
+    out = {"elapsed_s": el, "gpu_step_ms": e0.elapsed_time(e1) / steps, "launch": launch, "nsets": nsets,
+           "nrec": nrec, "slots": slots, "kernels": kernels}
+    if dump_dir:
+        # the last timed step's results: the parity its encode wrote, the blocks its decode recovered
+        out["dumped"] = dump_outputs(dump_dir, {"parity": par[0], "recovered": rec[0]}, sz,
+                                     dist.get_rank() if dist else 0, dist.get_world_size() if dist else 1)
+    if not full:
+        return out
 
     # Per-kernel launch duration for the rooflines: back-to-back launches of
     # one kernel between two HIP events on the launch stream, (a) "warm": the
@@ -799,11 +859,9 @@ def run_workload(k, m, sz, ns, steps, warmup, dist, use_graph=False, layout="256
 
     npl = max(50, steps)
     enc_pl, dec_pl = per_launch(npl)
-    out = {"elapsed_s": el, "gpu_step_ms": e0.elapsed_time(e1) / steps, "launch": launch,
-           "enc_ms": enc_c, "dec_ms": dec_c, "enc_ms_warm": enc_w, "dec_ms_warm": dec_w,
-           "enc_ms_pairs": enc_pl, "dec_ms_pairs": dec_pl, "b2b_launches": nb, "nsets": nsets,
-           "enqueue_us": (enc_host_us, dec_host_us),
-           "pair_launches": npl, "nrec": nrec, "slots": slots, "kernels": kernels}
+    out.update({"enc_ms": enc_c, "dec_ms": dec_c, "enc_ms_warm": enc_w, "dec_ms_warm": dec_w,
+                "enc_ms_pairs": enc_pl, "dec_ms_pairs": dec_pl, "b2b_launches": nb,
+                "enqueue_us": (enc_host_us, dec_host_us), "pair_launches": npl})
     if fresh:
         out["decode_fresh"] = decode_fresh(code, k, m, sz, ns, ld, data[0], par[0], recv[0], fresh, stream)
     return out
@@ -1141,15 +1199,11 @@ def main():
     if args.streams is None:
         args.streams = 1 if args.workload == "cfg3" or args.paired else 2
     t = run_workload(k, m, sz, ns, args.steps, args.warmup, dist, use_graph=args.graph, layout=args.layout,
-                     streams=args.streams, paired=args.paired,
-                     row_padding=not args.no_row_padding, fresh=fresh if rank == 0 else 0)
+                     streams=args.streams, paired=args.paired, full=args.full, dump_dir=args.dump_outputs,
+                     row_padding=not args.no_row_padding, fresh=fresh if rank == 0 and args.full else 0)
     el = reduce(dist, t["elapsed_s"], dist.ReduceOp.MAX if dist else None)
     total_bytes = reduce(dist, float(args.steps * 2 * k * sz * ns), dist.ReduceOp.SUM if dist else None)
     value = total_bytes / el / 1e9
-    nrec = t["nrec"]
-    enc_bytes = (k + r) * sz * ns    # read k blocks, write m-k blocks, per stripe
-    dec_bytes = (k + nrec) * sz * ns  # read k blocks, write the recovered ones
-    gbps = lambda nbytes, ms: nbytes / (ms * 1e-3) / 1e9
     desc = {"cfg2": "K=3 M=10, one 64 MiB stripe per GPU",
             "cfg3": "K=10 M=16, one 256 MiB stripe per GPU",
             "cfg4": "K=20 M=60, 1 GiB = 1024 x 1 MiB stripes split across GPUs",
@@ -1157,13 +1211,6 @@ def main():
     if args.slabs:
         desc = desc.replace("stripe per GPU", "stripe split into byte-range slabs across GPUs")
     row_padding = not args.no_row_padding
-    timing = ("%d launches back to back between two HIP events on the launch stream, enqueued while a spin kernel "
-              "holds the stream (average launch duration, no host gaps) after untimed launches worth %.0f ms of GPU "
-              "time (the clock the chip settles at under sustained load), over a rotation "
-              "of %d disjoint buffer sets spanning >= 768 MiB (3x the 256 MiB Infinity Cache), so every launch "
-              "reads and writes HBM; *_warm: the same on one buffer set (as the timed loop runs); "
-              "launch_ms_event_pairs: mean of %d encode/decode steps as in the timed loop with a HIP event pair "
-              "around each launch" % (t["b2b_launches"], WARM_MS, t["nsets"], t["pair_launches"]))
     out = {
         "metric": METRIC,
         "value": round(value, 2),
@@ -1192,42 +1239,25 @@ def main():
                                    % (world, sz) if args.slabs else
                                    "stripes sharded across %d GPU(s), no collective" % world)},
         "stripe_roundtrip_GBps": round(value / 2, 2),
-        "roofline": {"bound": "hbm", "achieved": round(gbps(enc_bytes, t["enc_ms"]), 1), "peak": HBM_PEAK_GBPS,
-                     "unit": "GB/s", "frac": round(gbps(enc_bytes, t["enc_ms"]) / HBM_PEAK_GBPS, 4),
-                     "traffic": None if args.slabs else pmc_traffic(args.workload),
-                     "traffic_warm": None if args.slabs else pmc_traffic(args.workload, "encode warm"),
-                     "kernel": "%s (encode)" % t["kernels"]["encode"], "algorithmic_bytes_per_launch": enc_bytes,
-                     "launch_ms": round(t["enc_ms"], 4),
-                     "achieved_warm": round(gbps(enc_bytes, t["enc_ms_warm"]), 1),
-                     "frac_warm": round(gbps(enc_bytes, t["enc_ms_warm"]) / HBM_PEAK_GBPS, 4),
-                     "launch_ms_warm": round(t["enc_ms_warm"], 4),
-                     "launch_ms_event_pairs": round(t["enc_ms_pairs"], 4),
-                     "rw_ceiling": rw_ceiling(k * sz * ns, r * sz * ns, gbps(enc_bytes, t["enc_ms"])),
-                     "host_enqueue_us": round(t["enqueue_us"][0], 1),
-                     "timing": timing},
-        "decode_roofline": {"achieved": round(gbps(dec_bytes, t["dec_ms"]), 1),
-                            "frac": round(gbps(dec_bytes, t["dec_ms"]) / HBM_PEAK_GBPS, 4),
-                            "kernel": "%s (decode)" % t["kernels"]["decode"],
-                            "algorithmic_bytes_per_launch": dec_bytes, "launch_ms": round(t["dec_ms"], 4),
-                            "frac_warm": round(gbps(dec_bytes, t["dec_ms_warm"]) / HBM_PEAK_GBPS, 4),
-                            "launch_ms_warm": round(t["dec_ms_warm"], 4),
-                            "launch_ms_event_pairs": round(t["dec_ms_pairs"], 4),
-                            "rw_ceiling": rw_ceiling(k * sz * ns, nrec * sz * ns, gbps(dec_bytes, t["dec_ms"]))},
-        "valu_roofline": None if args.slabs else valu_roofline(args.workload, t["kernels"]["encode"], t["enc_ms"]),
         "launch": t["launch"],
         "streams": args.streams, "paired": args.paired,
         "gpu_ms_per_step": round(t["gpu_step_ms"], 4),
-        "encode_input_GBps": round(gbps(k * sz * ns, t["enc_ms"]), 1),
-        "decode_input_GBps": round(gbps(k * sz * ns, t["dec_ms"]), 1),
+        "kernels": t["kernels"],
+        "full": args.full,
     }
+    if "dumped" in t:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "dtype": "float32 (one value per byte)",
+                                 "files": t["dumped"]}
+    if args.full:
+        out.update(rooflines(args, t, k, r, sz, ns))
     if "decode_fresh" in t:
         out["decode_fresh_pattern"] = t["decode_fresh"]
-    if rank == 0 and not args.no_extra and args.workload == "cfg2":
+    if args.full and rank == 0 and not args.no_extra and args.workload == "cfg2":
         out["batched_1MiB"] = run_batched_1mib(20)
-    if rank == 0 and not args.no_first_seen and args.workload == "cfg2":
+    if args.full and rank == 0 and not args.no_first_seen and args.workload == "cfg2":
         out["first_seen_decode"] = run_first_seen()
         out["first_launch_encode"] = out["first_seen_decode"].pop("first_launch_encode")
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             csz = min(sz, -(-(64 << 20) // k))  # sample stripes of at most 64 MiB (same K/M)
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, k, m, csz)
@@ -1255,6 +1285,48 @@ def main():
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def rooflines(args, t, k, r, sz, ns):
+    """--full: the result line's per-kernel figures (run_workload's back-to-back
+    and event-pair launch durations against the HBM and VALU ceilings)."""
+    nrec = t["nrec"]
+    enc_bytes = (k + r) * sz * ns    # read k blocks, write m-k blocks, per stripe
+    dec_bytes = (k + nrec) * sz * ns  # read k blocks, write the recovered ones
+    gbps = lambda nbytes, ms: nbytes / (ms * 1e-3) / 1e9
+    timing = ("%d launches back to back between two HIP events on the launch stream, enqueued while a spin kernel "
+              "holds the stream (average launch duration, no host gaps) after untimed launches worth %.0f ms of GPU "
+              "time (the clock the chip settles at under sustained load), over a rotation "
+              "of %d disjoint buffer sets spanning >= 768 MiB (3x the 256 MiB Infinity Cache), so every launch "
+              "reads and writes HBM; *_warm: the same on one buffer set (as the timed loop runs); "
+              "launch_ms_event_pairs: mean of %d encode/decode steps as in the timed loop with a HIP event pair "
+              "around each launch" % (t["b2b_launches"], WARM_MS, t["nsets"], t["pair_launches"]))
+    return {
+        "roofline": {"bound": "hbm", "achieved": round(gbps(enc_bytes, t["enc_ms"]), 1), "peak": HBM_PEAK_GBPS,
+                     "unit": "GB/s", "frac": round(gbps(enc_bytes, t["enc_ms"]) / HBM_PEAK_GBPS, 4),
+                     "traffic": None if args.slabs else pmc_traffic(args.workload),
+                     "traffic_warm": None if args.slabs else pmc_traffic(args.workload, "encode warm"),
+                     "kernel": "%s (encode)" % t["kernels"]["encode"], "algorithmic_bytes_per_launch": enc_bytes,
+                     "launch_ms": round(t["enc_ms"], 4),
+                     "achieved_warm": round(gbps(enc_bytes, t["enc_ms_warm"]), 1),
+                     "frac_warm": round(gbps(enc_bytes, t["enc_ms_warm"]) / HBM_PEAK_GBPS, 4),
+                     "launch_ms_warm": round(t["enc_ms_warm"], 4),
+                     "launch_ms_event_pairs": round(t["enc_ms_pairs"], 4),
+                     "rw_ceiling": rw_ceiling(k * sz * ns, r * sz * ns, gbps(enc_bytes, t["enc_ms"])),
+                     "host_enqueue_us": round(t["enqueue_us"][0], 1),
+                     "timing": timing},
+        "decode_roofline": {"achieved": round(gbps(dec_bytes, t["dec_ms"]), 1),
+                            "frac": round(gbps(dec_bytes, t["dec_ms"]) / HBM_PEAK_GBPS, 4),
+                            "kernel": "%s (decode)" % t["kernels"]["decode"],
+                            "algorithmic_bytes_per_launch": dec_bytes, "launch_ms": round(t["dec_ms"], 4),
+                            "frac_warm": round(gbps(dec_bytes, t["dec_ms_warm"]) / HBM_PEAK_GBPS, 4),
+                            "launch_ms_warm": round(t["dec_ms_warm"], 4),
+                            "launch_ms_event_pairs": round(t["dec_ms_pairs"], 4),
+                            "rw_ceiling": rw_ceiling(k * sz * ns, nrec * sz * ns, gbps(dec_bytes, t["dec_ms"]))},
+        "valu_roofline": None if args.slabs else valu_roofline(args.workload, t["kernels"]["encode"], t["enc_ms"]),
+        "encode_input_GBps": round(gbps(k * sz * ns, t["enc_ms"]), 1),
+        "decode_input_GBps": round(gbps(k * sz * ns, t["dec_ms"]), 1),
+    }
 
 
 if __name__ == "__main__":

@@ -55,8 +55,8 @@ def _torchrun(args, launcher=True):
 
 @pytest.mark.timeout(300)
 def test_bench_two_ranks_cfg4_sharded():
-    out = _torchrun(["--workload", "cfg4", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extra", "--fresh",
-                     "0"])
+    out = _torchrun(["--full", "--workload", "cfg4", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extra",
+                     "--fresh", "0"])
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2
     assert out["config"]["stripes_per_gpu"] == 512  # 1024 stripes split over 2 ranks
     assert out["scaling"] == "strong"
@@ -66,7 +66,8 @@ def test_bench_two_ranks_cfg4_sharded():
 
 @pytest.mark.timeout(300)
 def test_bench_two_ranks_cfg2_slabs():
-    out = _torchrun(["--workload", "cfg2", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extra", "--slabs"])
+    out = _torchrun(["--full", "--workload", "cfg2", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extra",
+                     "--slabs"])
     assert out["n_gpus"] == 2
     assert out["scaling"] == "strong"
     sz = -(-(64 << 20) // 3)

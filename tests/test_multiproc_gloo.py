@@ -207,6 +207,20 @@ def test_rw_ceiling_bounds():
     assert abs(c["frac_of_peak"] - c["GBps"] / bench.HBM_PEAK_GBPS) < 1e-3
 
 
+def test_dump_positions_fixed_and_bounded():
+    """bench.py --dump-outputs: a small output is written whole; a larger one as
+    the same sorted in-range sample every time, and a rank's two float32 arrays
+    stay under 64 MB."""
+    import bench
+
+    assert bench.dump_positions(bench.DUMP_MAX_VALUES) is None
+    n = 10 ** 8
+    a, b = bench.dump_positions(n), bench.dump_positions(n)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_MAX_VALUES
+    assert a[0] >= 0 and a[-1] < n and (np.diff(a) >= 0).all()
+    assert 2 * 4 * bench.DUMP_MAX_VALUES <= 64 * 10 ** 6
+
+
 def _bench(args, env_extra=None):
     import subprocess
     import sys

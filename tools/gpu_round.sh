@@ -18,9 +18,9 @@ cd $ROOT
 for what in "$@"; do
   case $what in
     bench)
-      timeout -k 10 420 python -u bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+      timeout -k 10 420 python -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
       for W in cfg3 cfg4 cfg5; do
-        timeout -k 10 300 python -u bench.py --workload $W --no-cpu > $OUT/bench_$W.json 2> $OUT/bench_$W.err
+        timeout -k 10 300 python -u bench.py --full --workload $W --no-cpu > $OUT/bench_$W.json 2> $OUT/bench_$W.err
       done ;;
     tests)
       timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread > $OUT/pytest_gpu.log 2>&1
@@ -30,7 +30,7 @@ for what in "$@"; do
       timeout -k 10 420 python -u tools/bytes_latency.py > $OUT/bytes_latency.log 2>&1 ;;
     stats)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d $OUT/stats -o st -- python3 $ROOT/bench.py --no-cpu > $OUT/stats_bench.json 2> $OUT/stats_bench.err)
+        -d $OUT/stats -o st -- python3 $ROOT/bench.py --full --no-cpu > $OUT/stats_bench.json 2> $OUT/stats_bench.err)
       # keep the --stats summary, drop the per-dispatch trace (gpurun copies back <= 64 MiB)
       find $OUT/stats -name "*kernel_trace.csv" -delete ;;
     profile)

@@ -18,7 +18,7 @@ for W in $WLS; do
   mkdir -p $OUT
   EXTRA=""
   [ "$W" = "cfg2" ] || EXTRA="--no-extra"
-  ARGS="--workload $W --steps 20 --warmup 3 --no-cpu $EXTRA"
+  ARGS="--full --workload $W --steps 20 --warmup 3 --no-cpu $EXTRA"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -o kt -- python3 $ROOT/bench.py $ARGS --legs-out $OUT/legs_kt.json > $OUT/ktrace.log 2>&1
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o f -- python3 $ROOT/bench.py $ARGS --legs-out $OUT/legs_f.json > $OUT/fetch.log 2>&1
   timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o w -- python3 $ROOT/bench.py $ARGS --legs-out $OUT/legs_w.json > $OUT/write.log 2>&1

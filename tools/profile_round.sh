@@ -16,7 +16,7 @@ for W in $WLS; do
   OUT=$ROOT/gpurun_out/$TAG/$W
   mkdir -p $OUT
   # the same arguments in all three passes: tools/pmc_summary.py matches dispatches by order
-  ARGS="--workload $W --steps 20 --warmup 3 --no-cpu --no-extra"
+  ARGS="--full --workload $W --steps 20 --warmup 3 --no-cpu --no-extra"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -o kt -- python3 $ROOT/bench.py $ARGS > $OUT/ktrace.log 2>&1
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o f -- python3 $ROOT/bench.py $ARGS > $OUT/fetch.log 2>&1
   timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o w -- python3 $ROOT/bench.py $ARGS > $OUT/write.log 2>&1
