@@ -34,6 +34,8 @@ Config* read_env() {
     c->small_lanes = env_size("ZFEC_HIP_SMALL_LANES", 2048);
     const size_t sc = env_size("ZFEC_HIP_STAGE_CHUNK", 0);
     c->stage_chunk = sc >= (64u << 10) ? sc / 4096 * 4096 : 0;
+    // the launch path ignores a value past its own cap (CUs x 8192, known there)
+    c->grid_cap = env_size("ZFEC_HIP_GRID_CAP", 0);
     return c;
 }
 

@@ -9,8 +9,8 @@
 //
 // No knob changes the bytes a call returns.  Round 4 removed the knobs whose
 // variants lost their A/Bs (and the code they selected); what is left is the
-// host-path policy a caller may tune and three test hooks that only change how
-// work is cut into launches (INTEGRATION.md "Environment").  Read elsewhere,
+// host-path policy a caller may tune and four test hooks that only change how
+// work is cut into launches and workgroups (INTEGRATION.md "Environment").  Read elsewhere,
 // once: ZFEC_HIP_JIT / ZFEC_HIP_JIT_CACHE / ZFEC_HIP_JIT_VERBOSE /
 // ZFEC_HIP_JIT_DUMP (bitslice.cpp), ZFEC_HIP_GENERIC (kernels.hip),
 // ZFEC_HIP_HOST_THREADS (host_pool.cpp).
@@ -32,6 +32,7 @@ struct Config {
     size_t launch_units;   // ZFEC_HIP_LAUNCH_UNITS: units per launch (long rows cut into byte ranges, batches into groups)
     uint64_t small_lanes;  // ZFEC_HIP_SMALL_LANES: launches below this many lanes take matapply_small (0: never)
     size_t stage_chunk;    // ZFEC_HIP_STAGE_CHUNK: bytes of each block per staged chunk (0: automatic)
+    size_t grid_cap;       // ZFEC_HIP_GRID_CAP: most workgroups per launch of the unit kernels (reg, rows, pair, lds; 0: automatic)
 };
 
 const Config& config();

@@ -2042,6 +2042,14 @@ int g_num_cu = 256;
 // walks grid-stride.
 constexpr uint64_t kGridPerCu = 8 * 1024;
 
+// Config::grid_cap (a test hook) lowers the cap so that a launch a test can
+// afford walks grid-stride; values outside [1, the cap] are ignored.
+uint64_t unit_grid_cap() {
+    const uint64_t cap = uint64_t(g_num_cu) * kGridPerCu;
+    const uint64_t hook = config().grid_cap;
+    return hook >= 1 && hook < cap ? hook : cap;
+}
+
 void init_dispatch() {
     int dev = 0;
     if (hipGetDevice(&dev) == hipSuccess) {
@@ -2118,7 +2126,7 @@ uint32_t fill_regjob(const ApplySpec& a, RegJob<K, R>& job, bool rows) {
     // one unit per lane up to the grid cap; beyond it a grid-stride loop
     const uint64_t lanes = rows ? a.nstripes * 64u : cps * a.nstripes;  // rows: one wave per stripe
     const uint64_t need = (lanes + kBlock - 1) / kBlock;
-    const uint64_t cap = uint64_t(g_num_cu) * kGridPerCu;
+    const uint64_t cap = unit_grid_cap();
     const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
     const uint64_t gstride = uint64_t(grid) * kBlock;
     job.gs_s = static_cast<uint32_t>(gstride / cps);
@@ -2289,7 +2297,7 @@ hipError_t launch_lds(const ApplySpec& a, hipStream_t stream) {
     const size_t rows = v.pad_tile ? (a.r + v.pad_tile - 1) / v.pad_tile * v.pad_tile : a.r;
     const size_t lds = size_t(a.k) * rows * 32;
     const uint64_t need = (total + kBlock - 1) / kBlock;
-    const uint64_t cap = uint64_t(g_num_cu) * kGridPerCu;
+    const uint64_t cap = unit_grid_cap();
     const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
     const uint64_t gstride = uint64_t(grid) * kBlock;
     job.gs_s = static_cast<uint32_t>(gstride / cps);
