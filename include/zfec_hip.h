@@ -150,6 +150,50 @@ int fec_decode_batch(const fec_t* code,
                      const unsigned* index, size_t sz, size_t nstripes,
                      void* stream, unsigned flags);
 
+/* Batched decode, a pattern per stripe: every stripe of the batch may have
+ * received different blocks (a storage node repairing many small objects).
+ * patterns: npatterns x k block numbers (host memory); pattern p says slot j of
+ * a stripe holds block patterns[p*k+j].  A pattern's k numbers are distinct and
+ * less than n, in ANY slot order (fec_decode's "primary i at slot i" is not
+ * required).  pattern_of: nstripes pattern ids (unsigned, 4 bytes each), in host
+ * OR device memory.  Output: all k primaries of every stripe in order (the stripe
+ * itself, FEC_FLAG_ALL_PRIMARIES semantics: a present primary is copied), k rows
+ * per stripe: primary i of stripe s at dst + s*dst_stripe_stride +
+ * i*dst_block_stride.  Bit-identical to fec_decode whatever the slot order.
+ *
+ * src and dst are device memory on one device, or page-locked host memory;
+ * pageable host memory returns FEC_EINVAL (this call does not stage).  Strides
+ * as in fec_decode_batch, except that a block-major layout is walked stripe by
+ * stripe (its stripes do not share a matrix, so it is not collapsed).
+ * FEC_FLAG_ASYNC and FEC_FLAG_LIBRARY_STREAM as in fec_decode_batch;
+ * FEC_FLAG_ROW_PADDING is accepted and ignored.
+ *
+ * All arguments are checked before any GPU work: a NULL argument, npatterns ==
+ * 0 with stripes to decode, more than 65536 patterns, a block number >= n or a
+ * duplicate in a pattern, and an id >= npatterns in a HOST-side pattern_of
+ * return FEC_EINVAL with a message naming the pattern or stripe.  Ids in DEVICE
+ * memory cannot be checked by the host: a stripe whose id is >= npatterns is
+ * left unwritten (no table is read for it), and no error is reported.
+ *
+ * k <= 4 runs in one launch of matapply_mixed<k>; the per-pattern tables (and
+ * host-side ids) are uploaded by a stream-ordered copy from pinned staging the
+ * library owns, so pattern_of and patterns may be reused as soon as the call
+ * returns.  k > 4 is cut into runs of consecutive stripes with one id, each run
+ * one fec_decode_batch-style launch; a device-side pattern_of is first copied
+ * to the host, which SYNCHRONISES the stream.  While the stream is being
+ * captured into a graph the call returns FEC_EINVAL. */
+int fec_decode_batch_mixed(const fec_t* code,
+                           const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                           gf* dst, size_t dst_block_stride, size_t dst_stripe_stride,
+                           const unsigned* patterns, size_t npatterns,
+                           const unsigned* pattern_of,
+                           size_t sz, size_t nstripes, void* stream, unsigned flags);
+
+/* Host only, no GPU: the k x k matrix fec_decode_batch_mixed applies for one
+ * pattern (row i yields primary i from the k slots), row-major into rows[k*k].
+ * FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
+int fec_mixed_decode_rows(const fec_t* code, const unsigned* pattern, gf* rows);
+
 /* Batched calls over several GPUs of this process.  The nstripes stripes are
  * split into contiguous, balanced ranges, one per entry of devices[] (entry d
  * gets stripes [d*q + min(d, e), ...), q = nstripes / ndevices, e = the

@@ -309,6 +309,118 @@ class Decoder(_fec.Decoder):
                                                   flags=flags)
         return out
 
+    def decode_batch_mixed(self, blocks, blocknums):
+        """Decode many independent stripes that each received their own block
+        numbers, in one launch (fec_decode_batch_mixed).
+
+        blocks: uint8 device tensor [nstripes, k, sz] (strides as in
+        decode_batch).  blocknums: an [nstripes, k] integer array -- a list of
+        lists, a numpy array, or a torch tensor on the host or on the device --
+        row s holding the block numbers of stripe s's slots, distinct, in [0,
+        m-1] and in any slot order; or a tuple (patterns [P, k], pattern_of
+        [nstripes]) of the distinct rows and each stripe's index into them.
+        The array form is reduced to that pair with unique() where it lives;
+        a device array's ids stay on the device.  Device-side pattern_of ids
+        cannot be range-checked: a stripe whose id is not below P is left
+        unwritten.  Returns a new [nstripes, k, sz] tensor of every stripe's k
+        primaries in order, block-major when the input was; the work is
+        enqueued on the current stream.  Host (numpy) blocks are not staged by
+        this call."""
+        import numpy as np
+
+        k, m = self.k, self.m
+        if _is_host_array(blocks):
+            raise Error("Precondition violation: decode_batch_mixed takes a device tensor; host (numpy) blocks are "
+                        "not staged by this call")
+        is_tensor = type(blocks).__module__.startswith("torch") and hasattr(blocks, "data_ptr")
+        if not is_tensor or str(blocks.dtype) != "torch.uint8" or blocks.dim() != 3:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz]" % k)
+        if blocks.shape[1] != k:
+            raise Error("Precondition violation: blocks is required to hold %d blocks per stripe, not %d"
+                        % (k, blocks.shape[1]))
+        ns = blocks.shape[0]
+        ids_dev = None  # device tensor of ids, or
+        ids_host = None  # numpy uint32 array of ids
+        if isinstance(blocknums, tuple) and len(blocknums) == 2:
+            pats, ids = blocknums
+            pats = pats.cpu().numpy() if hasattr(pats, "data_ptr") else np.asarray(pats)
+            if hasattr(ids, "data_ptr"):
+                if ids.dim() != 1 or ids.dtype.is_floating_point:
+                    raise Error("Precondition violation: pattern_of is required to be a 1-D integer array")
+                nids = ids.shape[0]
+                if ids.is_cuda:
+                    ids_dev = ids
+                else:
+                    ids_host = ids.numpy()
+            else:
+                ids_host = np.asarray(ids)
+                if ids_host.ndim != 1 or (ids_host.size and ids_host.dtype.kind not in "iu"):
+                    raise Error("Precondition violation: pattern_of is required to be a 1-D integer array")
+                nids = ids_host.shape[0]
+            if nids != ns:
+                raise Error("Precondition violation: pattern_of is required to hold nstripes = %d ids, not %d"
+                            % (ns, nids))
+        elif hasattr(blocknums, "data_ptr"):  # torch tensor, host or device
+            import torch
+
+            if blocknums.dim() != 2 or tuple(blocknums.shape) != (ns, k) or blocknums.dtype.is_floating_point:
+                raise Error("Precondition violation: blocknums is required to be an integer array [nstripes, k] = "
+                            "[%d, %d]" % (ns, k))
+            upat, inv = torch.unique(blocknums, dim=0, return_inverse=True)
+            pats = upat.cpu().numpy()
+            if blocknums.is_cuda:
+                ids_dev = inv.reshape(-1)
+            else:
+                ids_host = inv.reshape(-1).numpy()
+        else:
+            arr = np.asarray(blocknums)
+            if arr.ndim != 2 or arr.shape != (ns, k) or arr.dtype.kind not in "iu":
+                raise Error("Precondition violation: blocknums is required to be an integer array [nstripes, k] = "
+                            "[%d, %d]" % (ns, k))
+            if ns:
+                pats, inv = np.unique(arr, axis=0, return_inverse=True)
+            else:
+                pats, inv = arr, np.zeros(0, dtype=np.int64)
+            ids_host = inv.reshape(-1)
+        if pats.ndim != 2 or pats.shape[1] != k or (pats.size and pats.dtype.kind not in "iu"):
+            raise Error("Precondition violation: patterns is required to be an integer array [P, k = %d]" % k)
+        if pats.size and (pats.min() < 0 or pats.max() >= m):
+            bad = pats[(pats < 0) | (pats >= m)][0]
+            raise Error("Precondition violation: block nums are required to be in [0, m-1] = [0, %d], but one was %d"
+                        % (m - 1, bad))
+        for row in pats:
+            if len(set(row.tolist())) != k:
+                raise Error("Precondition violation: the block nums of a stripe are required to be distinct, but one "
+                            "stripe has %r" % (row.tolist(),))
+        npat = pats.shape[0]
+        if ids_host is not None and ids_host.size and (ids_host.min() < 0 or ids_host.max() >= npat):
+            raise Error("Precondition violation: pattern_of ids are required to be in [0, %d]" % (npat - 1))
+        if not blocks.is_cuda:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
+                        "not a host tensor" % k)
+        ns, sz, sbs, sss, ptr = _batch_view(blocks, k, "blocks")
+        out = _batch_out(blocks, sss < sbs, ns, k, sz)
+        if ns and sz:
+            import torch
+
+            if ids_dev is not None:
+                if ids_dev.device != blocks.device:
+                    raise Error("Precondition violation: device blocknums are required to be on the blocks' device")
+                ids = ids_dev.to(torch.int32).contiguous()  # non-negative ids: the bits of uint32
+                ids_ptr = ids.data_ptr()
+            else:
+                ids = np.ascontiguousarray(ids_host, dtype=np.uint32)
+                ids_ptr = ids.ctypes.data
+            optr, obs, oss = _batch_strides(out)
+            stream, flags = _batch_call_args(blocks)
+            # `ids` need only outlive the call: host ids are copied into the
+            # library's staging, device ids are read by work of this stream
+            with _as_error():
+                _capi_code(self).decode_batch_mixed(ptr, sbs, sss, optr, obs, oss,
+                                                    np.ascontiguousarray(pats, dtype=np.uint32), ids_ptr, sz, ns,
+                                                    stream=stream, flags=flags)
+        return out
+
     def _check_blocknums(self, blocknums):
         """Validated list of k block numbers (the reference's checks,
         zfec/_fecmodule.c:429-472, plus distinctness)."""

@@ -57,6 +57,8 @@ SYMBOLS = [
     ("fec_reload_config", ctypes.c_int, []),
     ("fec_last_wait", ctypes.c_int, []),
     ("fec_run_batch_jobs", ctypes.c_int, [_P, _SZ, _P, _U]),
+    ("fec_decode_batch_mixed", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _UP, _SZ, _P, _SZ, _SZ, _P, _U]),
+    ("fec_mixed_decode_rows", ctypes.c_int, [_P, _UP, _P]),
 ]
 
 JIT_OFF, JIT_AUTO, JIT_FORCE = 0, 1, 2
@@ -220,6 +222,32 @@ class Code(object):
         if st:
             check(st)
 
+    def decode_batch_mixed(self, src, sbs, sss, dst, dbs, dss, patterns, pattern_of_ptr, sz, nstripes, stream=0,
+                           flags=FEC_FLAG_ASYNC):
+        """fec_decode_batch_mixed: `patterns` is a sequence of k-number
+        sequences (or a [P, k] integer numpy array); `pattern_of_ptr` is the
+        address of nstripes uint32 pattern ids in host or device memory, which
+        the caller keeps alive until the call returns."""
+        if hasattr(patterns, "ctypes"):
+            import numpy as np
+
+            pats = np.ascontiguousarray(patterns, dtype=np.uint32)
+            npat = pats.shape[0] if pats.ndim == 2 else 0
+            if pats.ndim != 2 or pats.shape[1] != self.k:
+                raise FecError("patterns is required to be [npatterns, k = %d]" % self.k)
+            arr = ctypes.cast(pats.ctypes.data, _UP) if pats.size else uint_array([])
+        else:
+            rows = [tuple(p) for p in patterns]
+            for p in rows:
+                if len(p) != self.k:
+                    raise FecError("patterns is required to be [npatterns, k = %d]" % self.k)
+            npat = len(rows)
+            arr = uint_array([x for p in rows for x in p])
+        st = lib().fec_decode_batch_mixed(self.ptr, src, sbs, sss, dst, dbs, dss, arr, npat, pattern_of_ptr or None, sz,
+                                          nstripes, stream or None, flags)
+        if st:
+            check(st)
+
     def encode_batch_multi(self, src, sbs, sss, dst, dbs, dss, block_nums, sz, nstripes, devices, flags=0):
         """fec_encode_batch_multi: the stripes split over `devices` (host memory)."""
         devs = (ctypes.c_int * max(1, len(devices)))(*devices)
@@ -239,6 +267,18 @@ class Code(object):
     def decode_ptrs(self, in_addrs, out_addrs, index, sz, stream=0, flags=FEC_FLAG_ASYNC):
         check(lib().fec_decode_ex(self.ptr, ptr_array(in_addrs), ptr_array(out_addrs), uint_array(index),
                                   sz, stream or None, flags))
+
+
+def mixed_decode_rows(code, pattern):
+    """fec_mixed_decode_rows: the k*k bytes (row-major) of the matrix
+    fec_decode_batch_mixed applies for `pattern` (k block numbers, any slot
+    order); row i yields primary i.  Host only."""
+    pattern = list(pattern)
+    if len(pattern) != code.k:
+        raise FecError("pattern is required to hold k = %d block numbers" % code.k)
+    rows = (ctypes.c_ubyte * (code.k * code.k))()
+    check(lib().fec_mixed_decode_rows(code.ptr, uint_array(pattern), ctypes.cast(rows, _P)))
+    return bytes(rows)
 
 
 class BatchJob(ctypes.Structure):

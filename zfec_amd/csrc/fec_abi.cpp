@@ -1356,6 +1356,169 @@ FEC_API int fec_decode_batch(const fec_t* code, const gf* src, size_t src_block_
     });
 }
 
+// ---- batched decode, a pattern per stripe ------------------------------------------
+namespace {
+// A pattern's k block numbers: each < n, all distinct.  `p`: its number, for the message.
+int check_pattern(const fec_t* code, const unsigned* pat, size_t p) {
+    unsigned char seen[256] = {};
+    for (unsigned j = 0; j < code->k; ++j) {
+        if (pat[j] >= code->n)
+            return set_status(FEC_EINVAL, "pattern %zu: block number %u out of range (n = %u)", p, pat[j],
+                              unsigned(code->n));
+        if (seen[pat[j]]) return set_status(FEC_EINVAL, "pattern %zu: duplicate block number %u", p, pat[j]);
+        seen[pat[j]] = 1;
+    }
+    return FEC_OK;
+}
+
+// The k x k matrix that yields the k primaries from slots holding the blocks
+// pattern[0..k): the inverse of the matrix whose row j is enc_matrix's row
+// pattern[j] (a primary's row there is its unit vector).  Any slot order.
+int mixed_rows(const fec_t* code, const unsigned* pat, uint8_t* rows) {
+    const unsigned k = code->k;
+    for (unsigned j = 0; j < k; ++j) std::memcpy(rows + size_t(j) * k, code->enc_matrix + size_t(pat[j]) * k, k);
+    if (!invert_matrix(rows, k)) return set_status(FEC_ESINGULAR, "decode matrix is singular");
+    return FEC_OK;
+}
+
+int run_mixed(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst, size_t dbs, size_t dss,
+              const unsigned* patterns, size_t npatterns, const unsigned* pattern_of, int idev, size_t sz,
+              size_t nstripes, void* stream, unsigned flags) {
+    const unsigned k = code->k;
+    // device memory on one device, or page-locked host memory (read and written in place)
+    const size_t src_extent = (nstripes - 1) * sss + (k - 1) * sbs + sz;
+    const size_t dst_extent = (nstripes - 1) * dss + (k - 1) * dbs + sz;
+    const int sdev = pointer_device(src), ddev = pointer_device(dst);
+    const gf* zsrc = src;
+    gf* zdst = dst;
+    if (sdev < 0 && !(zsrc = mapped_block(src, src_extent)))
+        return set_status(FEC_EINVAL, "fec_decode_batch_mixed takes device or page-locked host memory: src is "
+                                      "pageable host memory, which this call does not stage");
+    if (ddev < 0 && !(zdst = const_cast<gf*>(mapped_block(dst, dst_extent))))
+        return set_status(FEC_EINVAL, "fec_decode_batch_mixed takes device or page-locked host memory: dst is "
+                                      "pageable host memory, which this call does not stage");
+    if (sdev >= 0 && ddev >= 0 && sdev != ddev)
+        return set_status(FEC_EINVAL, "batched entry points take memory on one device");
+    int dev = sdev >= 0 ? sdev : ddev;
+    if (dev < 0) dev = idev;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
+    if (idev >= 0 && idev != dev)
+        return set_status(FEC_EINVAL, "pattern_of lives on device %d, the blocks on device %d", idev, dev);
+    DeviceGuard guard(dev);
+    DevCtx* d = nullptr;
+    if (dev_ctx(dev, &d)) return t_status;
+    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
+    if (stream_capturing(st))
+        return set_status(FEC_EINVAL, "fec_decode_batch_mixed: the stream is being captured into a graph (the "
+                                      "pattern tables are uploaded when the call is made)");
+    hipError_t e;
+    if (k <= kMixedMaxK) {
+        thread_local std::vector<uint8_t> rows;
+        rows.resize(npatterns * k * k);
+        for (size_t p = 0; p < npatterns; ++p)
+            if (mixed_rows(code, patterns + p * k, &rows[p * k * k])) return t_status;
+        const uint8_t* in[kMixedMaxK];
+        uint8_t* out[kMixedMaxK];
+        for (unsigned j = 0; j < k; ++j) {
+            in[j] = zsrc + j * sbs;
+            out[j] = zdst + j * dbs;
+        }
+        MixedSpec m;
+        m.k = k;
+        m.rows = rows.data();
+        m.npatterns = static_cast<uint32_t>(npatterns);
+        m.ids_host = idev < 0 ? pattern_of : nullptr;
+        m.ids_dev = idev < 0 ? nullptr : pattern_of;
+        m.in = in;
+        m.out = out;
+        m.sz = sz;
+        m.nstripes = nstripes;
+        m.in_sstride = sss;
+        m.out_sstride = dss;
+        ++t_launches;
+        if ((e = launch_mixed(m, st)) != hipSuccess) return hip_fail(e, "launch_mixed");
+    } else {
+        // codes past the register shapes: maximal runs of consecutive stripes
+        // with one id, each through the shared-pattern batched path
+        thread_local std::vector<unsigned> hids;
+        const unsigned* ids = pattern_of;
+        if (idev >= 0) {
+            hids.resize(nstripes);
+            if ((e = hipMemcpyAsync(hids.data(), pattern_of, nstripes * sizeof(unsigned), hipMemcpyDeviceToHost,
+                                    st)) != hipSuccess)
+                return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
+            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+            ids = hids.data();
+        }
+        std::unordered_map<unsigned, std::vector<uint8_t>> rows_of;
+        const unsigned jf = (flags & FEC_FLAG_LIBRARY_STREAM) | FEC_FLAG_ASYNC;
+        for (size_t s0 = 0; s0 < nstripes;) {
+            size_t s1 = s0 + 1;
+            while (s1 < nstripes && ids[s1] == ids[s0]) ++s1;
+            const unsigned id = ids[s0];
+            if (id < npatterns) {  // (device ids are not checked: such stripes stay unwritten, as on the kernel)
+                std::vector<uint8_t>& rows = rows_of[id];
+                if (rows.empty()) {
+                    rows.resize(size_t(k) * k);
+                    if (mixed_rows(code, patterns + size_t(id) * k, rows.data())) return t_status;
+                }
+                if (run_batch(code, rows.data(), k, src + s0 * sss, sbs, sss, dst + s0 * dss, dbs, dss, sz, s1 - s0,
+                              stream, jf))
+                    return t_status;
+            }
+            s0 = s1;
+        }
+    }
+    if (!(flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_mixed_decode_rows(const fec_t* code, const unsigned* pattern, gf* rows) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!pattern) return set_status(FEC_EINVAL, "pattern is NULL");
+    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
+    if (check_pattern(code, pattern, 0)) return t_status;
+    return guarded([&] {
+        if (mixed_rows(code, pattern, rows)) return t_status;
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API int fec_decode_batch_mixed(const fec_t* code, const gf* src, size_t src_block_stride,
+                                   size_t src_stripe_stride, gf* dst, size_t dst_block_stride,
+                                   size_t dst_stripe_stride, const unsigned* patterns, size_t npatterns,
+                                   const unsigned* pattern_of, size_t sz, size_t nstripes, void* stream,
+                                   unsigned flags) {
+    // every check that needs no GPU comes first
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!src || !dst) return set_status(FEC_EINVAL, "NULL buffer");
+    if (!patterns) return set_status(FEC_EINVAL, "patterns is NULL");
+    if (!pattern_of) return set_status(FEC_EINVAL, "pattern_of is NULL");
+    if (npatterns == 0 && nstripes > 0)
+        return set_status(FEC_EINVAL, "npatterns is 0: stripe 0 of %zu has no pattern", nstripes);
+    if (npatterns > kMixedMaxPatterns)
+        return set_status(FEC_EINVAL, "%zu patterns: a call takes at most %u", npatterns, unsigned(kMixedMaxPatterns));
+    for (size_t p = 0; p < npatterns; ++p)
+        if (check_pattern(code, patterns + p * code->k, p)) return t_status;
+    // ids in host memory are checked here; ids in device memory cannot be (the
+    // kernel leaves a stripe with an id >= npatterns unwritten)
+    const int ngpu = gpu_available();
+    const int idev = ngpu ? pointer_device(pattern_of) : -1;
+    if (idev < 0)
+        for (size_t s = 0; s < nstripes; ++s)
+            if (pattern_of[s] >= npatterns)
+                return set_status(FEC_EINVAL, "stripe %zu: pattern id %u out of range (npatterns = %zu)", s,
+                                  pattern_of[s], npatterns);
+    if (!ngpu) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (sz == 0 || nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_mixed(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,
+                         patterns, npatterns, pattern_of, idev, sz, nstripes, stream, flags);
+    });
+}
+
 namespace zfec_hip {
 namespace {
 // A fec_run_batch_jobs job resolved for a paired launch (register-kernel

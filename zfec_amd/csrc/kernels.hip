@@ -20,6 +20,8 @@
 //                       kernel argument block sized to them (RegJob) and stay
 //                       in registers; the per-chunk body is straight-line code.
 //   matapply_rows<K, R> the same arithmetic, one wave per stripe of short blocks.
+//   matapply_mixed<K>   the same arithmetic, K outputs, each stripe's tables picked
+//                       by its pattern id from a device-side table (scalar loads).
 //   matapply_lds        any k <= 32, r <= 48 (longer codes are split by the
 //                       caller): each workgroup expands its coefficients into
 //                       LDS tables from a compile-time bank of all 256 values;
@@ -640,6 +642,110 @@ __global__ __launch_bounds__(kBlock) void matapply_rows(const RegJob<K, R> job) 
 #pragma unroll
         for (int h = 0; h < 4; ++h)
             if (live[h]) reg_compute_store<K, R, 0, AL>(job, T, x[h], s * job.out_sstride + o[h], true, 16u);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// matapply_mixed<K>: a batched decode whose stripes each have their own
+// erasure pattern (fec_decode_batch_mixed), k <= 4, all k primaries out.  The
+// K x K tables of every pattern of the call sit in device memory
+// (mixed_tab_dwords<K>() dwords per pattern, the Tab layout row-major, padded
+// to 16 bytes); ids[s] says which one stripe s uses.
+//
+// A wave's 64 units lie in ONE stripe: stripe s gets wps = ceil(cps / 64)
+// waves, the last one partly masked.  So the stripe, its pattern id and the
+// table address are the same in every lane; they are formed through
+// readfirstlane and read through constant-address-space pointers, which makes
+// the id and the table dwords scalar loads and lets v_perm take the tables as
+// SGPR pairs, as in matapply_reg.  (The ids and the tables are written before
+// the launch, by a copy or an earlier kernel of the stream, and never by this
+// kernel: the scalar cache starts every kernel empty.)  An id >= npatterns
+// reads no table and leaves its stripe unwritten.  Blocks under 1 KiB have
+// fewer than 64 chunks, so part of each wave idles there.
+// ---------------------------------------------------------------------------
+template <int K>
+constexpr uint32_t mixed_tab_dwords() {
+    return (K * K * 5 + 3) / 4 * 4;
+}
+
+template <int K>
+struct alignas(16) MixedJob {
+    uint64_t sz, in_sstride, out_sstride;
+    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
+    uint32_t wps;            // waves per stripe
+    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    uint32_t npatterns;
+    const uint32_t* tables;  // npatterns x mixed_tab_dwords<K>()
+    const uint32_t* ids;     // nstripes pattern ids
+    const uint8_t* in[K];
+    uint8_t* out[K];
+};
+
+typedef const __attribute__((address_space(4))) uint32_t* CU32;
+
+template <int K>
+__global__ __launch_bounds__(kBlock) void matapply_mixed(const MixedJob<K> job) {
+    constexpr uint32_t TD = mixed_tab_dwords<K>();
+    constexpr bool AL = reg_argload(K, K);  // K = 4: each row's tables are read where they are used
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    const CU32 ids = (CU32)job.ids;
+    while (s < job.nstripes) {
+        const uint32_t c = w * 64u + lane;
+        const bool live = c < job.cps;
+        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+        u32x4 x[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+        if (live) {
+            const uint64_t ib = s * job.in_sstride + sp.off;
+            if (sp.full) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load16(job.in[j] + ib);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load_tail(job.in[j] + ib, sp.nb);
+            }
+        }
+        const uint32_t id = __builtin_amdgcn_readfirstlane(ids[s]);
+        if (id < job.npatterns) {
+            CU32 tp = (CU32)job.tables + size_t(id) * TD;
+            Sel sel[4][K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                sel[0][j] = selectors(x[j].x);
+                sel[1][j] = selectors(x[j].y);
+                sel[2][j] = selectors(x[j].z);
+                sel[3][j] = selectors(x[j].w);
+            }
+            const uint64_t ob = s * job.out_sstride + sp.off;
+#pragma unroll
+            for (int r = 0; r < K; ++r) {
+                if constexpr (AL) asm volatile("" : "+s"(tp));
+                Tab t[K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const uint32_t i = (r * K + j) * 5;
+                    t[j] = Tab{tp[i], tp[i + 1], tp[i + 2], tp[i + 3], tp[i + 4]};
+                }
+                const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]), gf_dot<K>(t, sel[3])};
+                if (live) {
+                    if (sp.full)
+                        store16_pol<0>(job.out[r] + ob, y);
+                    else
+                        store_tail(job.out[r] + ob, y, sp.nb);
+                }
+            }
+        }
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
     }
 }
 
@@ -3072,7 +3178,158 @@ hipError_t launch_bsr(const ApplySpec& a, hipStream_t stream) {
                       job);
 }
 
+// ---- matapply_mixed dispatch ------------------------------------------------------
+// Staging of a mixed call's pattern tables and host-side ids, per thread and
+// device.  The TableRing pattern -- a pinned host slot, its device twin filled
+// by one stream-ordered copy, an event recorded after the slot's last launch
+// and waited for before the slot is rewritten, so consecutive calls (on any
+// streams) never share a slot in flight -- with slots that grow to what a call
+// needs: 4096 K=4 patterns are 1.3 MB of tables, 10^6 host-side ids 4 MB.
+struct MixedRing {
+    static constexpr int kSlots = 4;
+    struct Slot {
+        uint8_t* dev = nullptr;
+        uint8_t* host = nullptr;
+        size_t cap = 0;
+        hipEvent_t ev = nullptr;
+        bool busy = false;
+    };
+    Slot slot[kSlots];
+    unsigned next = 0;
+};
+
+struct MixedRings {
+    std::unordered_map<int, MixedRing> dev;
+    ~MixedRings() {
+        for (auto& kv : dev) {
+            int cur = 0;
+            if (hipGetDevice(&cur) != hipSuccess || hipSetDevice(kv.first) != hipSuccess) continue;
+            for (MixedRing::Slot& s : kv.second.slot) {
+                if (s.ev) (void)hipEventSynchronize(s.ev), (void)hipEventDestroy(s.ev);
+                if (s.dev) (void)hipFree(s.dev);
+                if (s.host) (void)hipHostFree(s.host);
+            }
+            (void)hipSetDevice(cur);
+        }
+    }
+};
+thread_local MixedRings t_mixed_rings;
+
+hipError_t mixed_slot(size_t bytes, MixedRing::Slot** out) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    MixedRing& t = t_mixed_rings.dev[dev];
+    MixedRing::Slot& s = t.slot[t.next++ % MixedRing::kSlots];
+    if (!s.ev && (e = hipEventCreateWithFlags(&s.ev, kSlotEventFlags)) != hipSuccess) return e;
+    if (s.busy && (e = hipEventSynchronize(s.ev)) != hipSuccess) return e;  // its last launch has read it
+    s.busy = false;
+    if (s.cap < bytes) {
+        if (s.dev) (void)hipFree(s.dev);
+        if (s.host) (void)hipHostFree(s.host);
+        s.dev = s.host = nullptr;
+        s.cap = 0;
+        const size_t cap = (std::max<size_t>(bytes, size_t(64) << 10) + 4095) / 4096 * 4096;
+        if ((e = hipMalloc(&s.dev, cap)) != hipSuccess) return e;
+        if ((e = hipHostMalloc(&s.host, cap, hipHostMallocDefault)) != hipSuccess) {
+            (void)hipFree(s.dev);
+            s.dev = nullptr;
+            return e;
+        }
+        s.cap = cap;
+    }
+    *out = &s;
+    return hipSuccess;
+}
+
+template <int K>
+hipError_t launch_mixed_k(const MixedSpec& m, hipStream_t stream) {
+    static const char* const kNames[kMixedMaxK + 1] = {"", "matapply_mixed<1>", "matapply_mixed<2>",
+                                                       "matapply_mixed<3>", "matapply_mixed<4>"};
+    constexpr uint32_t TD = mixed_tab_dwords<K>();
+    const size_t tab_bytes = (size_t(m.npatterns) * TD * 4 + 255) / 256 * 256;
+    const size_t ids_bytes = m.ids_host ? size_t(m.nstripes) * 4 : 0;
+    MixedRing::Slot* slot = nullptr;
+    hipError_t e = mixed_slot(tab_bytes + ids_bytes, &slot);
+    if (e != hipSuccess) return e;
+    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
+    for (size_t p = 0; p < m.npatterns; ++p) {
+        uint32_t* t = ht + p * TD;
+        for (int i = 0; i < K * K; ++i)
+            std::memcpy(t + i * 5, &kHostBank.w[uint32_t(m.rows[p * K * K + i]) * 8], 5 * sizeof(uint32_t));
+        for (uint32_t i = K * K * 5; i < TD; ++i) t[i] = 0;
+    }
+    if (ids_bytes) std::memcpy(slot->host + tab_bytes, m.ids_host, ids_bytes);
+    if ((e = hipMemcpyAsync(slot->dev, slot->host, tab_bytes + ids_bytes, hipMemcpyHostToDevice, stream)) !=
+        hipSuccess)
+        return e;
+    const uint32_t* ids = m.ids_host ? reinterpret_cast<const uint32_t*>(slot->dev + tab_bytes) : m.ids_dev;
+    // Launches of at most Config::launch_units lanes: blocks longer than that
+    // many 16-byte chunks are cut into byte ranges (whole waves of 1 KiB),
+    // batches into stripe groups, the id pointer advanced per group.
+    const uint64_t max_units = config().launch_units;
+    const uint64_t piece = (max_units & ~uint64_t(63)) * kChunk;
+    const uint64_t cap = unit_grid_cap();
+    auto launches = [&]() -> hipError_t {
+        for (uint64_t b0 = 0; b0 < m.sz; b0 += piece) {
+            const uint64_t len = std::min(piece, m.sz - b0);
+            const uint64_t cps = (len + kChunk - 1) / kChunk, wps = (cps + 63) / 64;
+            const uint64_t group = std::max<uint64_t>(1, max_units / (wps * 64));
+            for (uint64_t s0 = 0; s0 < m.nstripes; s0 += group) {
+                const uint64_t ns = std::min(group, m.nstripes - s0);
+                MixedJob<K> job;
+                job.sz = len;
+                job.in_sstride = m.in_sstride;
+                job.out_sstride = m.out_sstride;
+                job.nstripes = static_cast<uint32_t>(ns);
+                job.cps = static_cast<uint32_t>(cps);
+                job.wps = static_cast<uint32_t>(wps);
+                job.npatterns = m.npatterns;
+                job.tables = reinterpret_cast<const uint32_t*>(slot->dev);
+                job.ids = ids + s0;
+                for (int j = 0; j < K; ++j) {
+                    job.in[j] = m.in[j] + b0 + s0 * m.in_sstride;
+                    job.out[j] = m.out[j] + b0 + s0 * m.out_sstride;
+                }
+                const uint64_t waves = ns * wps, need = (waves + kBlock / 64 - 1) / (kBlock / 64);
+                const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
+                const uint64_t gstride = uint64_t(grid) * (kBlock / 64);
+                job.gs_s = static_cast<uint32_t>(gstride / wps);
+                job.gs_w = static_cast<uint32_t>(gstride % wps);
+                const hipError_t le =
+                    launch_job(reinterpret_cast<const void*>(matapply_mixed<K>), grid, kBlock, 0, stream, job);
+                if (le != hipSuccess) return le;
+            }
+        }
+        return hipSuccess;
+    };
+    e = launches();
+    // the copy (and any launch made) reads the slot: it stays busy whatever happened
+    if (hipEventRecord(slot->ev, stream) == hipSuccess)
+        slot->busy = true;
+    else
+        (void)hipStreamSynchronize(stream);
+    if (e == hipSuccess) t_last_kernel = kNames[K];
+    return e;
+}
+
 }  // namespace
+
+hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (m.k < 1 || m.k > kMixedMaxK || m.npatterns < 1 || m.npatterns > kMixedMaxPatterns || !m.rows ||
+        (!m.ids_host && !m.ids_dev) || m.sz == 0 || m.nstripes == 0)
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
+    t_signal_used = false;
+    switch (m.k) {
+    case 1: return launch_mixed_k<1>(m, stream);
+    case 2: return launch_mixed_k<2>(m, stream);
+    case 3: return launch_mixed_k<3>(m, stream);
+    default: return launch_mixed_k<4>(m, stream);
+    }
+}
 
 int generic_mode() {
     int g = g_generic.load();

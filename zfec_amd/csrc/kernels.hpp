@@ -67,6 +67,29 @@ hipError_t launch_apply(const ApplySpec& a, hipStream_t stream);
 // caller launches them one at a time).  Neither may read what the other writes.
 hipError_t launch_apply_pair(const ApplySpec& x, const ApplySpec& y, hipStream_t stream);
 
+// A batched decode with a pattern per stripe (matapply_mixed<K>, k <= 4): k
+// inputs and k outputs per stripe, stripe s applying the k x k matrix
+// rows + ids[s] * k * k.  The ids are nstripes uint32 in host memory (ids_host:
+// copied, then uploaded with the tables) or, with ids_host null, in device
+// memory (ids_dev: read in place; an id >= npatterns leaves its stripe
+// unwritten).  The tables (and host ids) go through pinned staging slots by a
+// stream-ordered copy, so the call declines under graph capture
+// (hipErrorNotSupported).  hipErrorInvalidValue for other shapes.
+constexpr uint32_t kMixedMaxK = 4;
+constexpr uint32_t kMixedMaxPatterns = 65536;  // patterns per call
+struct MixedSpec {
+    uint32_t k;
+    const uint8_t* rows;  // npatterns x k x k coefficients (host memory)
+    uint32_t npatterns;
+    const uint32_t* ids_host;
+    const uint32_t* ids_dev;
+    const uint8_t* const* in;  // k input block bases (stripe 0), kernel-visible addresses
+    uint8_t* const* out;       // k output block bases (stripe 0)
+    uint64_t sz, nstripes;
+    uint64_t in_sstride, out_sstride;
+};
+hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
