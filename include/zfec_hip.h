@@ -194,6 +194,61 @@ int fec_decode_batch_mixed(const fec_t* code,
  * FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
 int fec_mixed_decode_rows(const fec_t* code, const unsigned* pattern, gf* rows);
 
+/* Batched parity verification (scrubbing): are the blocks a store holds still
+ * consistent with each other?  Nothing is written but a few bits per stripe.
+ *
+ * Every stripe holds nb = num_block_nums blocks: slot j of stripe s at
+ * src + s*src_stripe_stride + j*src_block_stride holds block block_nums[j].
+ * The numbers are distinct, all < n, in any order, and k + 1 <= nb <= n.  The
+ * first k slots are the basis, the other c = nb - k slots the checks.  Check i
+ * (slot k + i) is consistent when, over all sz bytes, it equals row i of
+ * P = E[checks] . inverse(E[basis]) applied to the basis blocks (E: the code's
+ * enc_matrix).  With the basis 0..k-1 in order P is the encode rows of the
+ * check blocks: the common "primaries against parity" scrub.
+ *
+ * Result: W = ceil(c / 32) words per stripe.  Bit i % 32 of
+ * mismatch[s*W + i/32] is set iff check i of stripe s differs in at least one
+ * byte; every other bit is 0.  The library clears the nstripes x W words
+ * itself, in stream order, before its kernels run; they never write to src.
+ *
+ * Reading the mask: the code is MDS, so P has no zero entry.  A corrupt check
+ * block sets exactly its own bit; ONE corrupt basis block sets all c bits of
+ * its stripe.  (Telling which block is bad when all bits are set takes another
+ * call with another basis.)
+ *
+ * src: device memory on one device, or page-locked host memory read in place;
+ * pageable host memory returns FEC_EINVAL (this call does not stage).  A
+ * block-major layout is walked stripe by stripe.  mismatch in device memory is
+ * used in place (on the blocks' device, else FEC_EINVAL) and FEC_FLAG_ASYNC is
+ * honoured.  mismatch in host memory, pageable or page-locked: the kernels use
+ * device-scope atomics, which must not be aimed at host memory over PCIe, so
+ * the library gathers the words in device memory it owns and copies them back;
+ * the call is then synchronous whatever the flags.  FEC_FLAG_LIBRARY_STREAM as
+ * elsewhere; FEC_FLAG_ROW_PADDING is accepted and ignored.  While the stream is
+ * being captured into a graph the call returns FEC_EINVAL.
+ *
+ * Checked before any GPU work, in this order, each FEC_EINVAL with a message:
+ * invalid fec_t; NULL src, block_nums or mismatch; nb <= k ("nothing to
+ * check"); nb > n; a block number >= n; a duplicate.  Then FEC_ENODEV when no
+ * GPU is visible.  nstripes == 0 returns FEC_OK; sz == 0 returns FEC_OK with the
+ * words cleared.
+ *
+ * k <= 4 runs on matverify_reg<k, r> (at most 8 checks per launch): the check
+ * rows are recomputed in registers and compared, so the call reads every block
+ * once and, on clean data, writes nothing.  Other codes compute the expected
+ * rows into library scratch (at most 64 MiB per device, batches cut to fit)
+ * with the encode kernels and compare them with rows_differ. */
+int fec_verify_batch(const fec_t* code,
+                     const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                     const unsigned* block_nums, size_t num_block_nums,
+                     size_t sz, size_t nstripes,
+                     unsigned* mismatch, void* stream, unsigned flags);
+
+/* Host only, no GPU: the c x k matrix P fec_verify_batch applies for
+ * block_nums (row i yields the block of slot k + i from the k basis slots),
+ * row-major into rows[c*k].  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
+int fec_verify_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
+
 /* Batched calls over several GPUs of this process.  The nstripes stripes are
  * split into contiguous, balanced ranges, one per entry of devices[] (entry d
  * gets stripes [d*q + min(d, e), ...), q = nstripes / ndevices, e = the

@@ -421,6 +421,63 @@ class Decoder(_fec.Decoder):
                                                     stream=stream, flags=flags)
         return out
 
+    def verify_batch(self, blocks, blocknums):
+        """Check many independent stripes for consistency without writing any
+        block (scrubbing; fec_verify_batch).
+
+        blocks: uint8 device tensor [nstripes, nb, sz] (strides as in
+        decode_batch), slot j of every stripe holding block blocknums[j].
+        blocknums: nb distinct ints in [0, m-1], in any order, with
+        k + 1 <= nb <= m; the first k slots are the basis, the other nb - k the
+        checks.  Returns a torch.bool tensor [nstripes, nb - k] on the blocks'
+        device: True where a check block differs, in at least one byte, from
+        what the basis blocks imply.  A corrupt check block sets only its own
+        column; one corrupt basis block sets every column of its stripe.  The
+        work is enqueued on the current stream, without a host sync.  Host
+        (numpy) blocks are not staged by this call."""
+        import torch
+
+        k, m = self.k, self.m
+        if _is_host_array(blocks):
+            raise Error("Precondition violation: verify_batch takes a device tensor; host (numpy) blocks are not "
+                        "staged by this call")
+        try:
+            nums = list(blocknums)
+        except TypeError:
+            raise TypeError("Second argument was not a sequence.")
+        nb = len(nums)
+        if nb <= k or nb > m:
+            raise Error("Precondition violation: blocknums is required to hold between k + 1 = %d and m = %d block "
+                        "nums, not %d" % (k + 1, m, nb))
+        for x in nums:
+            if not isinstance(x, int) or x < 0 or x >= m:
+                raise Error("Precondition violation: block nums are required to be in [0, m-1] = [0, %d], but one "
+                            "was %r" % (m - 1, x))
+        if len(set(nums)) != nb:
+            raise Error("Precondition violation: block nums are required to be distinct, but got %r" % (nums,))
+        is_tensor = type(blocks).__module__.startswith("torch") and hasattr(blocks, "data_ptr")
+        if not is_tensor or blocks.dtype != torch.uint8 or blocks.dim() != 3:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz]"
+                        % nb)
+        if blocks.shape[1] != nb:
+            raise Error("Precondition violation: blocks is required to hold %d blocks per stripe, not %d"
+                        % (nb, blocks.shape[1]))
+        if not blocks.is_cuda:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
+                        "not a host tensor" % nb)
+        ns, sz, sbs, sss, ptr = _batch_view(blocks, nb, "blocks")
+        c = nb - k
+        words = (c + 31) // 32
+        if not (ns and sz):
+            return torch.zeros((ns, c), dtype=torch.bool, device=blocks.device)
+        mask = torch.empty((ns, words), dtype=torch.int32, device=blocks.device)  # the library clears it
+        stream, flags = _batch_call_args(blocks)
+        with _as_error():
+            _capi_code(self).verify_batch(ptr, sbs, sss, nums, sz, ns, mask.data_ptr(), stream=stream, flags=flags)
+        shifts = torch.arange(32, dtype=torch.int32, device=blocks.device)
+        bits = (mask.unsqueeze(-1) >> shifts) & 1
+        return bits.reshape(ns, words * 32)[:, :c].ne(0)
+
     def _check_blocknums(self, blocknums):
         """Validated list of k block numbers (the reference's checks,
         zfec/_fecmodule.c:429-472, plus distinctness)."""

@@ -59,6 +59,8 @@ SYMBOLS = [
     ("fec_run_batch_jobs", ctypes.c_int, [_P, _SZ, _P, _U]),
     ("fec_decode_batch_mixed", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _UP, _SZ, _P, _SZ, _SZ, _P, _U]),
     ("fec_mixed_decode_rows", ctypes.c_int, [_P, _UP, _P]),
+    ("fec_verify_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
+    ("fec_verify_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
 ]
 
 JIT_OFF, JIT_AUTO, JIT_FORCE = 0, 1, 2
@@ -248,6 +250,16 @@ class Code(object):
         if st:
             check(st)
 
+    def verify_batch(self, src, sbs, sss, block_nums, sz, nstripes, mismatch_ptr, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_verify_batch: slot j of every stripe holds block block_nums[j],
+        the first k slots the basis, the rest the checks; `mismatch_ptr` is the
+        address of nstripes * ceil((len(block_nums) - k) / 32) uint32 words in
+        device or host memory, which the library clears and sets bits in."""
+        st = lib().fec_verify_batch(self.ptr, src, sbs, sss, _nums(block_nums), len(block_nums), sz, nstripes,
+                                    mismatch_ptr or None, stream or None, flags)
+        if st:
+            check(st)
+
     def encode_batch_multi(self, src, sbs, sss, dst, dbs, dss, block_nums, sz, nstripes, devices, flags=0):
         """fec_encode_batch_multi: the stripes split over `devices` (host memory)."""
         devs = (ctypes.c_int * max(1, len(devices)))(*devices)
@@ -278,6 +290,16 @@ def mixed_decode_rows(code, pattern):
         raise FecError("pattern is required to hold k = %d block numbers" % code.k)
     rows = (ctypes.c_ubyte * (code.k * code.k))()
     check(lib().fec_mixed_decode_rows(code.ptr, uint_array(pattern), ctypes.cast(rows, _P)))
+    return bytes(rows)
+
+
+def verify_rows(code, block_nums):
+    """fec_verify_rows: the c*k bytes (row-major, c = len(block_nums) - k) of
+    the matrix fec_verify_batch applies for `block_nums`; row i yields the
+    block of slot k + i from the k basis slots.  Host only."""
+    nums = list(block_nums)
+    rows = (ctypes.c_ubyte * max(1, (len(nums) - code.k) * code.k))()
+    check(lib().fec_verify_rows(code.ptr, uint_array(nums), len(nums), ctypes.cast(rows, _P)))
     return bytes(rows)
 
 

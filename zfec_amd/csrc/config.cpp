@@ -36,6 +36,9 @@ Config* read_env() {
     c->stage_chunk = sc >= (64u << 10) ? sc / 4096 * 4096 : 0;
     // the launch path ignores a value past its own cap (CUs x 8192, known there)
     c->grid_cap = env_size("ZFEC_HIP_GRID_CAP", 0);
+    const size_t vs = env_size("ZFEC_HIP_VERIFY_SCRATCH", 0), vmax = size_t(64) << 20;
+    // (255 check rows of at least 128 bytes each must fit)
+    c->verify_scratch = vs >= (64u << 10) && vs < vmax ? vs : vmax;
     return c;
 }
 

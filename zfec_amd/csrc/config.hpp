@@ -9,7 +9,7 @@
 //
 // No knob changes the bytes a call returns.  Round 4 removed the knobs whose
 // variants lost their A/Bs (and the code they selected); what is left is the
-// host-path policy a caller may tune and four test hooks that only change how
+// host-path policy a caller may tune and five test hooks that only change how
 // work is cut into launches and workgroups (INTEGRATION.md "Environment").  Read elsewhere,
 // once: ZFEC_HIP_JIT / ZFEC_HIP_JIT_CACHE / ZFEC_HIP_JIT_VERBOSE /
 // ZFEC_HIP_JIT_DUMP (bitslice.cpp), ZFEC_HIP_GENERIC (kernels.hip),
@@ -33,6 +33,7 @@ struct Config {
     uint64_t small_lanes;  // ZFEC_HIP_SMALL_LANES: launches below this many lanes take matapply_small (0: never)
     size_t stage_chunk;    // ZFEC_HIP_STAGE_CHUNK: bytes of each block per staged chunk (0: automatic)
     size_t grid_cap;       // ZFEC_HIP_GRID_CAP: most workgroups per launch of the unit kernels (reg, rows, pair, lds; 0: automatic)
+    size_t verify_scratch; // ZFEC_HIP_VERIFY_SCRATCH: cap of fec_verify_batch's expected-row scratch, bytes (64 MiB; only lowered)
 };
 
 const Config& config();

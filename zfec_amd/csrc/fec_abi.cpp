@@ -103,6 +103,16 @@ struct DevCtx {
     uint32_t* flag = nullptr;      // pinned completion word of small synchronous calls
     uint32_t* flag_dev = nullptr;  // its address in the device's view
     uint32_t seq = 0;
+    // fec_verify_batch: the expected check rows of the two-step path, and the
+    // mismatch words of a call whose `mismatch` is host memory.  Calls of this
+    // thread on different streams share them: each use waits (on the GPU) for
+    // the event recorded after the previous one.
+    void* vbuf = nullptr;
+    size_t vcap = 0;
+    void* vmask = nullptr;
+    size_t vmask_cap = 0;
+    hipEvent_t ev_verify = nullptr;
+    bool verify_busy = false;
 };
 
 struct ThreadCtx {
@@ -120,6 +130,9 @@ struct ThreadCtx {
             if (d.hbuf) (void)hipHostFree(d.hbuf);
             if (d.sbuf) (void)hipHostFree(d.sbuf);
             if (d.flag) (void)hipHostFree(d.flag);
+            if (d.ev_verify) (void)hipEventSynchronize(d.ev_verify), (void)hipEventDestroy(d.ev_verify);
+            if (d.vbuf) (void)hipFree(d.vbuf);
+            if (d.vmask) (void)hipFree(d.vmask);
             (void)hipSetDevice(cur);
         }
     }
@@ -1516,6 +1529,231 @@ FEC_API int fec_decode_batch_mixed(const fec_t* code, const gf* src, size_t src_
     return guarded([&] {
         return run_mixed(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,
                          patterns, npatterns, pattern_of, idev, sz, nstripes, stream, flags);
+    });
+}
+
+// ---- batched parity verification (scrub) ---------------------------------------------
+namespace {
+// nb block numbers of a verify call: k + 1 <= nb <= n, each < n, all distinct.
+int check_verify_nums(const fec_t* code, const unsigned* nums, size_t nb) {
+    if (nb <= code->k)
+        return set_status(FEC_EINVAL, "nothing to check: %zu blocks per stripe, a check needs more than k = %u", nb,
+                          unsigned(code->k));
+    if (nb > code->n)
+        return set_status(FEC_EINVAL, "%zu blocks per stripe, but the code has only n = %u", nb, unsigned(code->n));
+    for (size_t j = 0; j < nb; ++j)
+        if (nums[j] >= code->n)
+            return set_status(FEC_EINVAL, "block number %u out of range (n = %u)", nums[j], unsigned(code->n));
+    unsigned char seen[256] = {};
+    for (size_t j = 0; j < nb; ++j) {
+        if (seen[nums[j]]) return set_status(FEC_EINVAL, "duplicate block number %u", nums[j]);
+        seen[nums[j]] = 1;
+    }
+    return FEC_OK;
+}
+
+// P = E[checks] . inverse(E[basis]), c x k row-major: row i yields the block in
+// slot k + i from the k basis slots.
+int verify_rows(const fec_t* code, const unsigned* nums, size_t nb, uint8_t* P) {
+    const unsigned k = code->k;
+    thread_local std::vector<uint8_t> inv;
+    inv.resize(size_t(k) * k);
+    if (mixed_rows(code, nums, inv.data())) return t_status;
+    for (size_t i = 0; i + k < nb; ++i) {
+        const uint8_t* e = code->enc_matrix + size_t(nums[k + i]) * k;
+        for (unsigned j = 0; j < k; ++j) {
+            uint8_t acc = 0;
+            for (unsigned l = 0; l < k; ++l) acc ^= gf_mul(e[l], inv[size_t(l) * k + j]);
+            P[i * k + j] = acc;
+        }
+    }
+    return FEC_OK;
+}
+
+// Device memory of at least `bytes` the thread keeps per device.  Growing it
+// first waits for the last verify call that used the old one.
+int ensure_verify_buf(DevCtx& d, void*& buf, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return FEC_OK;
+    if (d.verify_busy) (void)hipEventSynchronize(d.ev_verify);
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    cap = 0;
+    const size_t want = align_up(std::max<size_t>(bytes, size_t(1) << 20), 4096);
+    const hipError_t e = hipMalloc(&buf, want);
+    if (e != hipSuccess) return set_status(FEC_ENOMEM, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
+    cap = want;
+    return FEC_OK;
+}
+
+// k <= 4: matverify_reg, at most 8 check rows per launch, the bit index advancing.
+int verify_reg_path(const uint8_t* P, unsigned k, unsigned c, const gf* src, size_t sbs, size_t sss, size_t sz,
+                    size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st) {
+    const uint8_t* in[4];
+    const uint8_t* chk[8];
+    for (unsigned j = 0; j < k; ++j) in[j] = src + j * sbs;
+    for (unsigned g0 = 0; g0 < c; g0 += 8) {
+        const unsigned rg = std::min(8u, c - g0);
+        for (unsigned i = 0; i < rg; ++i) chk[i] = src + size_t(k + g0 + i) * sbs;
+        VerifySpec v;
+        v.coef = P + size_t(g0) * k;
+        v.coef_stride = k;
+        v.k = k;
+        v.r = rg;
+        v.in = in;
+        v.chk = chk;
+        v.sz = sz;
+        v.nstripes = nstripes;
+        v.sstride = sss;
+        v.mismatch = mask;
+        v.words = words;
+        v.bit0 = g0;
+        ++t_launches;
+        const hipError_t e = launch_verify(v, st);
+        if (e != hipSuccess) return hip_fail(e, "launch_verify");
+    }
+    return FEC_OK;
+}
+
+// Every other shape: the expected check rows into scratch through
+// apply_matrix (whatever kernel it picks), then rows_differ against the stored
+// rows.  The scratch holds c rows of `pitch` bytes per stripe and at most
+// Config::verify_scratch bytes: a batch goes in runs of stripes that fit, a
+// stripe larger than that in byte ranges.  The bits OR together, so the
+// cutting is invisible.
+int verify_scratch_path(DevCtx& d, const uint8_t* P, unsigned k, unsigned c, const gf* src, size_t sbs, size_t sss,
+                        size_t sz, size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st) {
+    const size_t cap = config().verify_scratch;
+    size_t len = sz, run = 1;
+    if (size_t(c) * align_up(sz, 128) <= cap)
+        run = std::min(nstripes, cap / (size_t(c) * align_up(sz, 128)));
+    else
+        len = cap / c / 128 * 128;
+    const size_t pitch = align_up(len, 128), sstride = size_t(c) * pitch;
+    if (ensure_verify_buf(d, d.vbuf, d.vcap, run * sstride)) return t_status;
+    uint8_t* const scratch = static_cast<uint8_t*>(d.vbuf);
+    const uint8_t* in[kMaxWideIn];
+    uint8_t* out[kMaxWideIn];
+    const uint8_t* stored[kMaxOut];
+    for (unsigned i = 0; i < c; ++i) out[i] = scratch + i * pitch;
+    for (size_t s0 = 0; s0 < nstripes; s0 += run) {
+        const size_t ns = std::min(run, nstripes - s0);
+        for (size_t b0 = 0; b0 < sz; b0 += len) {
+            const size_t l = std::min(len, sz - b0);
+            const gf* base = src + s0 * sss + b0;
+            for (unsigned j = 0; j < k; ++j) in[j] = base + j * sbs;
+            if (apply_matrix(P, k, c, in, out, l, ns, sss, sstride, st)) return t_status;
+            for (unsigned g0 = 0; g0 < c; g0 += kMaxOut) {
+                const unsigned rg = std::min<unsigned>(kMaxOut, c - g0);
+                for (unsigned i = 0; i < rg; ++i) stored[i] = base + size_t(k + g0 + i) * sbs;
+                DifferSpec f;
+                f.r = rg;
+                f.a = out + g0;
+                f.b = stored;
+                f.sz = l;
+                f.nstripes = ns;
+                f.a_sstride = sstride;
+                f.b_sstride = sss;
+                f.mismatch = mask + s0 * words;
+                f.words = words;
+                f.bit0 = g0;
+                ++t_launches;
+                const hipError_t e = launch_rows_differ(f, st);
+                if (e != hipSuccess) return hip_fail(e, "launch_rows_differ");
+            }
+        }
+    }
+    return FEC_OK;
+}
+
+int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const unsigned* nums, size_t nb, size_t sz,
+               size_t nstripes, unsigned* mismatch, void* stream, unsigned flags) {
+    const unsigned k = code->k, c = static_cast<unsigned>(nb - k), words = (c + 31) / 32;
+    if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
+    const size_t mask_bytes = nstripes * words * sizeof(uint32_t);
+    const int mdev = pointer_device(mismatch);
+    int dev = -1;
+    const gf* zsrc = src;
+    if (sz) {
+        // device memory on one device, or page-locked host memory (read in place)
+        const size_t extent = (nstripes - 1) * sss + (nb - 1) * sbs + sz;
+        dev = pointer_device(src);
+        if (dev < 0 && !(zsrc = mapped_block(src, extent)))
+            return set_status(FEC_EINVAL, "fec_verify_batch takes device or page-locked host memory: src is pageable "
+                                          "host memory, which this call does not stage");
+        if (dev >= 0 && mdev >= 0 && mdev != dev)
+            return set_status(FEC_EINVAL, "mismatch lives on device %d, the blocks on device %d", mdev, dev);
+    }
+    if (dev < 0) dev = mdev;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
+    DeviceGuard guard(dev);
+    DevCtx* d = nullptr;
+    if (dev_ctx(dev, &d)) return t_status;
+    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
+    if (stream_capturing(st))
+        return set_status(FEC_EINVAL, "fec_verify_batch: the stream is being captured into a graph (the call uses "
+                                      "memory the library owns and reuses)");
+    hipError_t e;
+    if (!d->ev_verify && (e = hipEventCreateWithFlags(&d->ev_verify, hipEventDisableTiming)) != hipSuccess)
+        return hip_fail(e, "hipEventCreateWithFlags");
+    // the thread's scratch and mask buffer: wait (on the GPU) for the call that used them last
+    const bool reg = k <= 4, shared = mdev < 0 || (!reg && sz);
+    if (shared && d->verify_busy && (e = hipStreamWaitEvent(st, d->ev_verify, 0)) != hipSuccess)
+        return hip_fail(e, "hipStreamWaitEvent");
+    // mismatch in host memory: the kernels' device-scope atomics must not aim
+    // at host memory over PCIe, so the words are gathered in device memory
+    if (mdev < 0 && ensure_verify_buf(*d, d->vmask, d->vmask_cap, mask_bytes)) return t_status;
+    uint32_t* const mask = mdev < 0 ? static_cast<uint32_t*>(d->vmask) : mismatch;
+    if ((e = hipMemsetAsync(mask, 0, mask_bytes, st)) != hipSuccess) return hip_fail(e, "hipMemsetAsync (mismatch)");
+    int rc = FEC_OK;
+    if (sz) {
+        thread_local std::vector<uint8_t> P;
+        P.resize(size_t(c) * k);
+        rc = verify_rows(code, nums, nb, P.data());
+        if (!rc)
+            rc = reg ? verify_reg_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st)
+                     : verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st);
+    }
+    if (!rc && mdev < 0 && (e = hipMemcpyAsync(mismatch, mask, mask_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpyAsync D2H (mismatch)");
+    // whatever was enqueued uses the shared buffers: they stay busy whatever happened
+    if (shared) {
+        if (hipEventRecord(d->ev_verify, st) == hipSuccess)
+            d->verify_busy = true;
+        else
+            (void)hipStreamSynchronize(st);
+    }
+    if (rc) return rc;
+    if ((mdev < 0 || !(flags & FEC_FLAG_ASYNC)) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_verify_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
+    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
+    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+    return guarded([&] {
+        if (verify_rows(code, block_nums, num_block_nums, rows)) return t_status;
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API int fec_verify_batch(const fec_t* code, const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                             const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
+                             unsigned* mismatch, void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!src) return set_status(FEC_EINVAL, "NULL buffer: src");
+    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
+    if (!mismatch) return set_status(FEC_EINVAL, "mismatch is NULL");
+    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+    if (!gpu_available()) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_verify(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
+                          mismatch, stream, flags);
     });
 }
 

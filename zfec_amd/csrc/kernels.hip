@@ -22,6 +22,10 @@
 //   matapply_rows<K, R> the same arithmetic, one wave per stripe of short blocks.
 //   matapply_mixed<K>   the same arithmetic, K outputs, each stripe's tables picked
 //                       by its pattern id from a device-side table (scalar loads).
+//   matverify_reg<K, R> the same arithmetic, nothing stored: the R rows are compared
+//                       with the stored check blocks and only mismatch bits are
+//                       OR-ed out (fec_verify_batch); rows_differ compares rows
+//                       another kernel computed, for the shapes past k = 4.
 //   matapply_lds        any k <= 32, r <= 48 (longer codes are split by the
 //                       caller): each workgroup expands its coefficients into
 //                       LDS tables from a compile-time bank of all 256 values;
@@ -739,6 +743,197 @@ __global__ __launch_bounds__(kBlock) void matapply_mixed(const MixedJob<K> job) 
                         store_tail(job.out[r] + ob, y, sp.nb);
                 }
             }
+        }
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// matverify_reg<K, R>: parity verification (fec_verify_batch), k <= 4 and up
+// to 8 check rows per launch.  The R rows matapply_reg<K, R> would store are
+// computed in registers from the K basis blocks and compared with the R
+// stored check blocks: the launch reads K + R rows and writes nothing unless a
+// row differs.  matapply_mixed's walk: a wave's 64 units lie in one stripe, so
+// the stripe number is wave-uniform.  Per unit all K + R loads are issued
+// before any arithmetic; per row the four words of computed ^ stored are
+// OR-ed, one ballot turns "any lane differs" into one bit of a wave-uniform
+// mask, and if the mask is nonzero ONE lane issues one relaxed device-scope
+// fetch_or per touched word of the stripe's mismatch words.  Dead lanes (past
+// the stripe's last chunk) hold zeros on both sides; the byte tail is
+// zero-filled on both sides by load_tail; the overlapped last chunk of
+// chunk_span compares some bytes twice, which is harmless.  OR is
+// order-independent, so the result is deterministic.
+// ---------------------------------------------------------------------------
+template <int K, int R>
+struct alignas(16) VerifyJob {
+    uint64_t sz, sstride;
+    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
+    uint32_t wps;            // waves per stripe
+    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    uint32_t words;          // mismatch words per stripe
+    uint32_t bit0;           // bit index of this launch's first check row
+    uint32_t pad_;
+    uint32_t* mismatch;
+    const uint8_t* in[K];
+    const uint8_t* chk[R];
+    uint32_t tab[K * R * 5];  // the RegJob layout: row i, input j at (i*K + j)*5
+};
+
+// ORs `bits` (bit 0 = bit index `bit` of the stripe's words) into the words at
+// `base`: one atomic per touched word, issued by the calling lane.
+__device__ __forceinline__ void mismatch_or(uint32_t* base, uint32_t bit, uint32_t bits) {
+    const uint64_t m = static_cast<uint64_t>(bits) << (bit & 31u);
+    uint32_t* wp = base + (bit >> 5);
+    const uint32_t lo = static_cast<uint32_t>(m), hi = static_cast<uint32_t>(m >> 32);
+    if (lo) (void)__hip_atomic_fetch_or(wp, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (hi) (void)__hip_atomic_fetch_or(wp + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matverify_reg(const VerifyJob<K, R> job) {
+    constexpr bool AL = reg_argload(K, R);  // each row's tables are read where they are used
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    while (s < job.nstripes) {
+        const uint32_t c = w * 64u + lane;
+        const bool live = c < job.cps;
+        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+        u32x4 x[K], y[R];
+#pragma unroll
+        for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < R; ++r) y[r] = u32x4{0u, 0u, 0u, 0u};
+        if (live) {
+            const uint64_t ib = s * job.sstride + sp.off;
+            // AL: the block pointers too are read where they are used, so they
+            // do not sit in SGPRs next to the tables (<4,8> spilled otherwise)
+            const uint8_t* in[K];
+            const uint8_t* chk[R];
+            if constexpr (AL) {
+                const KPtr<VerifyJob<K, R>> kj = kernarg_job<VerifyJob<K, R>>();
+#pragma unroll
+                for (int j = 0; j < K; ++j) in[j] = kj->in[j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) chk[r] = kj->chk[r];
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) in[j] = job.in[j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) chk[r] = job.chk[r];
+            }
+            if (sp.full) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load16(in[j] + ib);
+#pragma unroll
+                for (int r = 0; r < R; ++r) y[r] = load16(chk[r] + ib);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load_tail(in[j] + ib, sp.nb);
+#pragma unroll
+                for (int r = 0; r < R; ++r) y[r] = load_tail(chk[r] + ib, sp.nb);
+            }
+        }
+        Sel sel[4][K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            sel[0][j] = selectors(x[j].x);
+            sel[1][j] = selectors(x[j].y);
+            sel[2][j] = selectors(x[j].z);
+            sel[3][j] = selectors(x[j].w);
+        }
+        uint32_t mask = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            Tab t[K];
+            if constexpr (AL) {
+                const KPtr<VerifyJob<K, R>> kj = kernarg_job<VerifyJob<K, R>>();
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const uint32_t i = (r * K + j) * 5;
+                    t[j] = Tab{kj->tab[i], kj->tab[i + 1], kj->tab[i + 2], kj->tab[i + 3], kj->tab[i + 4]};
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const uint32_t* p = &job.tab[(r * K + j) * 5];
+                    t[j] = Tab{p[0], p[1], p[2], p[3], p[4]};
+                }
+            }
+            const uint32_t d = (gf_dot<K>(t, sel[0]) ^ y[r].x) | (gf_dot<K>(t, sel[1]) ^ y[r].y) |
+                               (gf_dot<K>(t, sel[2]) ^ y[r].z) | (gf_dot<K>(t, sel[3]) ^ y[r].w);
+            if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << r;
+        }
+        if (mask != 0u && lane == 0u) mismatch_or(job.mismatch + size_t(s) * job.words, job.bit0, mask);
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// rows_differ: the second step of parity verification for the shapes
+// matverify_reg does not take.  The expected check rows were computed into
+// scratch (a) by whatever kernel apply_matrix picks; this kernel compares them
+// with the stored rows (b): run-time r <= kMaxOut, the same walk and the same
+// ballot-then-OR reduction.  Rows go in groups of 4 so that 8 loads are in
+// flight before the first comparison.
+// ---------------------------------------------------------------------------
+struct alignas(16) DifferJob {
+    uint64_t sz, a_sstride, b_sstride;
+    uint32_t nstripes, cps, wps, gs_w, gs_s;
+    uint32_t words, bit0, r;
+    uint32_t* mismatch;
+    const uint8_t* a[kMaxOut];
+    const uint8_t* b[kMaxOut];
+};
+
+__global__ __launch_bounds__(kBlock) void rows_differ(const DifferJob job) {
+    constexpr uint32_t G = 4;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    while (s < job.nstripes) {
+        const uint32_t c = w * 64u + lane;
+        const bool live = c < job.cps;
+        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+        const uint64_t ao = s * job.a_sstride + sp.off, bo = s * job.b_sstride + sp.off;
+        uint32_t* const base = job.mismatch + size_t(s) * job.words;
+        for (uint32_t r0 = 0; r0 < job.r; r0 += G) {
+            const uint32_t n = job.r - r0 < G ? job.r - r0 : G;
+            u32x4 p[G], q[G];
+#pragma unroll
+            for (uint32_t i = 0; i < G; ++i) {
+                p[i] = q[i] = u32x4{0u, 0u, 0u, 0u};
+                if (i < n && live) {
+                    if (sp.full) {
+                        p[i] = load16(job.a[r0 + i] + ao);
+                        q[i] = load16(job.b[r0 + i] + bo);
+                    } else {
+                        p[i] = load_tail(job.a[r0 + i] + ao, sp.nb);
+                        q[i] = load_tail(job.b[r0 + i] + bo, sp.nb);
+                    }
+                }
+            }
+            uint32_t mask = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < G; ++i) {
+                const u32x4 d = p[i] ^ q[i];
+                if (__builtin_amdgcn_ballot_w64((d.x | d.y | d.z | d.w) != 0u) != 0ull) mask |= 1u << i;
+            }
+            if (mask != 0u && lane == 0u) mismatch_or(base, job.bit0 + r0, mask);
         }
         w += job.gs_w;
         s += job.gs_s;
@@ -3313,7 +3508,137 @@ hipError_t launch_mixed_k(const MixedSpec& m, hipStream_t stream) {
     return e;
 }
 
+// ---- parity verification dispatch (matverify_reg, rows_differ) ---------------------
+// The wave-inside-one-stripe walk of a launch over ns stripes of len bytes.
+struct WaveWalk {
+    uint32_t cps, wps, grid, gs_w, gs_s;
+};
+
+WaveWalk wave_walk(uint64_t len, uint64_t ns) {
+    WaveWalk k;
+    const uint64_t cps = (len + kChunk - 1) / kChunk, wps = (cps + 63) / 64;
+    const uint64_t waves = ns * wps, need = (waves + kBlock / 64 - 1) / (kBlock / 64);
+    const uint64_t cap = unit_grid_cap();
+    k.cps = static_cast<uint32_t>(cps);
+    k.wps = static_cast<uint32_t>(wps);
+    k.grid = static_cast<uint32_t>(need < cap ? need : cap);
+    const uint64_t gstride = uint64_t(k.grid) * (kBlock / 64);
+    k.gs_s = static_cast<uint32_t>(gstride / wps);
+    k.gs_w = static_cast<uint32_t>(gstride % wps);
+    return k;
+}
+
+// Launches of at most Config::launch_units lanes, as launch_mixed_k cuts them:
+// blocks longer than that many 16-byte chunks into byte ranges (whole waves of
+// 1 KiB), batches into stripe groups.  f(b0, len, s0, ns) makes one launch.
+template <class F>
+hipError_t verify_pieces(uint64_t sz, uint64_t nstripes, F&& f) {
+    const uint64_t max_units = config().launch_units;
+    const uint64_t piece = (max_units & ~uint64_t(63)) * kChunk;
+    for (uint64_t b0 = 0; b0 < sz; b0 += piece) {
+        const uint64_t len = std::min(piece, sz - b0);
+        const uint64_t wps = ((len + kChunk - 1) / kChunk + 63) / 64;
+        const uint64_t group = std::max<uint64_t>(1, max_units / (wps * 64));
+        for (uint64_t s0 = 0; s0 < nstripes; s0 += group) {
+            const hipError_t e = f(b0, len, s0, std::min(group, nstripes - s0));
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+char g_verify_names[kRegK + 1][kRegR + 1][24];
+
+template <int K, int R>
+hipError_t launch_verify_kr(const VerifySpec& v, hipStream_t stream) {
+    VerifyJob<K, R> job;
+    job.sstride = v.sstride;
+    job.words = v.words;
+    job.bit0 = v.bit0;
+    job.pad_ = 0;
+    for (int i = 0; i < R; ++i)
+        for (int j = 0; j < K; ++j)
+            std::memcpy(&job.tab[(i * K + j) * 5], &kHostBank.w[uint32_t(v.coef[size_t(i) * v.coef_stride + j]) * 8],
+                        5 * sizeof(uint32_t));
+    const hipError_t e = verify_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const WaveWalk ww = wave_walk(len, ns);
+        job.sz = len;
+        job.nstripes = static_cast<uint32_t>(ns);
+        job.cps = ww.cps;
+        job.wps = ww.wps;
+        job.gs_w = ww.gs_w;
+        job.gs_s = ww.gs_s;
+        job.mismatch = v.mismatch + s0 * v.words;
+        for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
+        for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
+        return launch_job(reinterpret_cast<const void*>(matverify_reg<K, R>), ww.grid, kBlock, 0, stream, job);
+    });
+    if (e == hipSuccess) t_last_kernel = g_verify_names[K][R];
+    return e;
+}
+
+typedef hipError_t (*VerifyLaunch)(const VerifySpec&, hipStream_t);
+
+template <int K, int... R>
+constexpr std::array<VerifyLaunch, kRegR + 1> verify_row(std::integer_sequence<int, R...>) {
+    return {{nullptr, launch_verify_kr<K, R + 1>...}};
+}
+
+const std::array<VerifyLaunch, kRegR + 1> g_verify_launch[kRegK + 1] = {
+    {}, verify_row<1>(std::make_integer_sequence<int, kRegR>()), verify_row<2>(std::make_integer_sequence<int, kRegR>()),
+    verify_row<3>(std::make_integer_sequence<int, kRegR>()), verify_row<4>(std::make_integer_sequence<int, kRegR>())};
+
 }  // namespace
+
+hipError_t launch_verify(const VerifySpec& v, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    static std::once_flag names_once;
+    std::call_once(names_once, [] {
+        for (int k = 1; k <= kRegK; ++k)
+            for (int r = 1; r <= kRegR; ++r)
+                snprintf(g_verify_names[k][r], sizeof g_verify_names[k][r], "matverify_reg<%d,%d>", k, r);
+    });
+    if (v.k < 1 || v.k > static_cast<uint32_t>(kRegK) || v.r < 1 || v.r > static_cast<uint32_t>(kRegR) ||
+        v.coef_stride < v.k || !v.mismatch || v.sz == 0 || v.nstripes == 0 || v.nstripes >= (1ull << 32) ||
+        uint64_t(v.bit0) + v.r > uint64_t(v.words) * 32)
+        return hipErrorInvalidValue;
+    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
+    t_signal_used = false;
+    return g_verify_launch[v.k][v.r](v, stream);
+}
+
+hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (d.r < 1 || d.r > static_cast<uint32_t>(kMaxOut) || !d.mismatch || d.sz == 0 || d.nstripes == 0 ||
+        d.nstripes >= (1ull << 32) || uint64_t(d.bit0) + d.r > uint64_t(d.words) * 32)
+        return hipErrorInvalidValue;
+    t_signal_flag = nullptr;
+    t_signal_used = false;
+    DifferJob job;
+    job.a_sstride = d.a_sstride;
+    job.b_sstride = d.b_sstride;
+    job.words = d.words;
+    job.bit0 = d.bit0;
+    job.r = d.r;
+    for (uint32_t i = d.r; i < static_cast<uint32_t>(kMaxOut); ++i) job.a[i] = job.b[i] = nullptr;
+    const hipError_t e = verify_pieces(d.sz, d.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const WaveWalk ww = wave_walk(len, ns);
+        job.sz = len;
+        job.nstripes = static_cast<uint32_t>(ns);
+        job.cps = ww.cps;
+        job.wps = ww.wps;
+        job.gs_w = ww.gs_w;
+        job.gs_s = ww.gs_s;
+        job.mismatch = d.mismatch + s0 * d.words;
+        for (uint32_t i = 0; i < d.r; ++i) {
+            job.a[i] = d.a[i] + b0 + s0 * d.a_sstride;
+            job.b[i] = d.b[i] + b0 + s0 * d.b_sstride;
+        }
+        return launch_job(reinterpret_cast<const void*>(rows_differ), ww.grid, kBlock, 0, stream, job);
+    });
+    if (e == hipSuccess) t_last_kernel = "rows_differ";
+    return e;
+}
 
 hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream) {
     std::call_once(g_dispatch_once, init_dispatch);

@@ -90,6 +90,39 @@ struct MixedSpec {
 };
 hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream);
 
+// Parity verification (fec_verify_batch): nothing is written but mismatch bits.
+// Bit (bit0 + i) % 32 of mismatch[s * words + (bit0 + i) / 32] is OR-ed in
+// (relaxed, device scope) when row i of stripe s differs in at least one byte;
+// clean data performs no store and no atomic.  The words are cleared by the
+// caller, in stream order, before the launch.  mismatch is device memory.
+//
+// launch_verify (matverify_reg<K, R>, k <= 4, r <= 8): row i is the r x k
+// matrix `coef` applied to the k basis blocks, compared with the stored check
+// block chk[i]; basis and checks share the stripe stride.
+// launch_rows_differ (rows_differ, r <= kMaxOut): row i of a against row i of b.
+// hipErrorInvalidValue for other shapes.
+struct VerifySpec {
+    const uint8_t* coef;  // r x k coefficients, row i at coef + i * coef_stride
+    uint32_t coef_stride;
+    uint32_t k, r;
+    const uint8_t* const* in;   // k basis block bases (stripe 0), kernel-visible addresses
+    const uint8_t* const* chk;  // r stored check block bases (stripe 0)
+    uint64_t sz, nstripes, sstride;
+    uint32_t* mismatch;
+    uint32_t words, bit0;
+};
+hipError_t launch_verify(const VerifySpec& v, hipStream_t stream);
+
+struct DifferSpec {
+    uint32_t r;
+    const uint8_t* const* a;  // r row bases (stripe 0)
+    const uint8_t* const* b;
+    uint64_t sz, nstripes, a_sstride, b_sstride;
+    uint32_t* mismatch;
+    uint32_t words, bit0;
+};
+hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
