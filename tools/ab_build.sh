@@ -13,7 +13,8 @@
 #   "name=git:REV FLAGS"  the same with compiler flags (a knob of that commit)
 #
 # The library loads its variant with ZFEC_HIP_LIB=abuild/<name>/libzfec_hip.so
-# (zfec_amd/capi.py); tools/ab_bsr.py runs the variants interleaved.
+# (zfec_amd/capi.py); tools/ab_bsr.py runs the variants interleaved on the
+# bit-sliced shapes, tools/ab_bench.py on the headline (plain bench.py runs).
 #
 #   tools/ab_build.sh "r05=git:a1850ed" "base=-DZFEC_TR64=0 legacy" "new="
 set -euo pipefail

@@ -15,19 +15,18 @@
 //            (4 KiB contiguous per block per wave), lanes 1 KiB apart
 //   plain    `lane` with default-policy stores instead of nt
 //   ntload   `lane` with nt loads too
-//   prod / prod_xcd: the production kernel without / with XCD-contiguous
-//            workgroup order (ZFEC_HIP_XCD)
-//   prod_gmN the production kernel with its grid capped at N x the resident
-//            workgroups (a grid-stride walk of ~units / (N x resident lanes)
-//            units per lane; the default cap is 1024, i.e. one unit per lane)
+//   prod     the production dispatcher's kernel (launch_apply)
 //   prod_bm  the production kernel on the same stripes stored block-major
 //            (one long row per block, as fec_encode_batch collapses them)
-// usage: tools/mb_cold.exe [buffer sets] [stripes] | tools/mb_cold.exe sweep
+// usage: tools/mb_cold.exe [buffer sets] [stripes] | tools/mb_cold.exe sweep | launch | blocks | tail | ldsweep | one
+//   one      cfg2's stripe: the production kernel against the copy walk of the
+//            register kernels' straight-line single-stripe form (mb_one)
 // Ceilings: read3 (only the 3 loads), write7 (only the 7 stores), copy1
 // (1 load, 1 store per unit).
 //
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/mb_cold.hip zfec_amd/csrc/bitslice.cpp \
-//          zfec_amd/csrc/gf256.cpp -ldl -o tools/mb_cold.exe
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude tools/mb_cold.hip zfec_amd/csrc/bitslice.cpp \
+//          zfec_amd/csrc/gf256.cpp zfec_amd/csrc/config.cpp zfec_amd/csrc/host_pool.cpp -ldl -lpthread \
+//          -o tools/mb_cold.exe
 #include "../zfec_amd/csrc/kernels.hip"
 
 #include <cstdio>
@@ -116,6 +115,16 @@ __global__ __launch_bounds__(256) void mb(const Lay L) {
 // does the end-of-kernel write-back of dirty L2 lines set part of the fixed
 // per-launch cost?  Workgroups >= tail_wg take the write-through stores.
 template <int SP>
+__device__ __forceinline__ void store_wt(uint8_t* p, u32x4 v) {
+    if constexpr (SP == 1)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+    else if constexpr (SP == 2)
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+    else
+        store16_pol<3>(p, v);
+}
+
+template <int SP>
 __global__ __launch_bounds__(256) void mb_tail(const Lay L, uint32_t tail_wg) {
     const uint32_t u = blockIdx.x * 256 + threadIdx.x;
     if (u >= L.units) return;
@@ -128,7 +137,7 @@ __global__ __launch_bounds__(256) void mb_tail(const Lay L, uint32_t tail_wg) {
     for (int r = 0; r < R; ++r) {
         uint8_t* q = L.out + ob + r * L.ld;
         if (wt)
-            store16_pol<true, SP>(q, acc ^ uint32_t(r));
+            store_wt<SP>(q, acc ^ uint32_t(r));
         else
             __builtin_nontemporal_store(acc ^ uint32_t(r), reinterpret_cast<u32x4*>(q));
     }
@@ -166,161 +175,50 @@ float run(const std::vector<Lay>& sets, int reps, uint32_t grid) {
     return ms / reps;
 }
 
-float run_prod(const std::vector<Lay>& sets, int reps, uint64_t sz, uint32_t ns) {
-    std::vector<MatJob> jobs(sets.size());
-    static const uint8_t coef[R * K] = {15, 8, 6, 45, 48, 28, 153, 224, 120, 11, 231, 237, 137, 59, 179, 70, 241, 182, 186, 217, 98};
-    for (size_t i = 0; i < sets.size(); ++i) {
-        MatJob& j = jobs[i];
-        std::memset(&j, 0, sizeof j);
-        j.sz = sz;
-        j.in_sstride = K * sets[i].ld;
-        j.out_sstride = R * sets[i].ld;
-        j.nstripes = ns;
-        j.k = K;
-        j.r = R;
-        for (int q = 0; q < K; ++q) j.in[q] = sets[i].in + q * sets[i].ld;
-        for (int q = 0; q < R; ++q) j.out[q] = sets[i].out + q * sets[i].ld;
-        std::memcpy(j.coef, coef, sizeof coef);
-    }
+// One production launch (launch_apply) of the K=3/M=10 encode rows over a buffer set.
+struct Prod {
+    const uint8_t* in[K];
+    uint8_t* out[R];
+    ApplySpec a;
+};
+static const uint8_t kCoef[R * K] = {15, 8, 6, 45, 48, 28, 153, 224, 120, 11, 231, 237, 137, 59, 179, 70, 241, 182, 186, 217, 98};
+
+void fill_prod(Prod& p, const Lay& L, uint64_t row, uint64_t sz, uint64_t ns, uint64_t in_ss, uint64_t out_ss) {
+    for (int q = 0; q < K; ++q) p.in[q] = L.in + q * row;
+    for (int q = 0; q < R; ++q) p.out[q] = L.out + q * row;
+    p.a = ApplySpec{kCoef, K, K, R, p.in, p.out, sz, ns, in_ss, out_ss, false};
+}
+
+float time_prod(std::vector<Prod>& jobs, int reps) {
     hipEvent_t a, b;
     CK(hipEventCreate(&a));
     CK(hipEventCreate(&b));
-    for (int i = 0; i < 3; ++i) CK(launch_matapply(jobs[i % jobs.size()], 0));
+    for (int i = 0; i < 3; ++i) CK(launch_apply(jobs[i % jobs.size()].a, 0));
     CK(hipEventRecord(a, 0));
-    for (int i = 0; i < reps; ++i) CK(launch_matapply(jobs[(i + 3) % jobs.size()], 0));
+    for (int i = 0; i < reps; ++i) CK(launch_apply(jobs[(i + 3) % jobs.size()].a, 0));
     CK(hipEventRecord(b, 0));
     CK(hipEventSynchronize(b));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, a, b));
     return ms / reps;
+}
+
+float run_prod(const std::vector<Lay>& sets, int reps, uint64_t sz, uint32_t ns) {
+    std::vector<Prod> jobs(sets.size());
+    for (size_t i = 0; i < sets.size(); ++i) fill_prod(jobs[i], sets[i], sets[i].ld, sz, ns, K * sets[i].ld, R * sets[i].ld);
+    return time_prod(jobs, reps);
 }
 
 // The same stripes stored block-major (block j of every stripe back to back:
 // one row of ns * sz bytes per block), as fec_encode_batch collapses them:
 // one launch over 10 long streams.
 float run_prod_bm(const std::vector<Lay>& sets, int reps, uint64_t sz, uint32_t ns) {
-    std::vector<MatJob> jobs(sets.size());
-    static const uint8_t coef[R * K] = {15, 8, 6, 45, 48, 28, 153, 224, 120, 11, 231, 237, 137, 59, 179, 70, 241, 182, 186, 217, 98};
-    for (size_t i = 0; i < sets.size(); ++i) {
-        MatJob& j = jobs[i];
-        std::memset(&j, 0, sizeof j);
-        j.sz = sz * ns;
-        j.nstripes = 1;
-        j.k = K;
-        j.r = R;
-        for (int q = 0; q < K; ++q) j.in[q] = sets[i].in + q * sz * ns;
-        for (int q = 0; q < R; ++q) j.out[q] = sets[i].out + q * sz * ns;
-        std::memcpy(j.coef, coef, sizeof coef);
-    }
-    hipEvent_t a, b;
-    CK(hipEventCreate(&a));
-    CK(hipEventCreate(&b));
-    for (int i = 0; i < 3; ++i) CK(launch_matapply(jobs[i % jobs.size()], 0));
-    CK(hipEventRecord(a, 0));
-    for (int i = 0; i < reps; ++i) CK(launch_matapply(jobs[(i + 3) % jobs.size()], 0));
-    CK(hipEventRecord(b, 0));
-    CK(hipEventSynchronize(b));
-    float ms = 0;
-    CK(hipEventElapsedTime(&ms, a, b));
-    return ms / reps;
+    std::vector<Prod> jobs(sets.size());
+    for (size_t i = 0; i < sets.size(); ++i) fill_prod(jobs[i], sets[i], sz * ns, sz * ns, 1, 0, 0);
+    return time_prod(jobs, reps);
 }
 
 }  // namespace
-
-// Walk variants of matapply_reg<3,7> on one stripe per block (block-major),
-// cold: U units per lane per loop trip, prefetch of the next unit, and the grid
-// (one unit per lane, or capped at `cap` x the resident workgroups with a
-// grid-stride loop), launched directly (tables in the kernel arguments as
-// launch_matapply puts them).
-template <int U, bool PF>
-float run_walk(const std::vector<Lay>& sets, int reps, uint64_t sz, uint32_t ns, int cap) {
-    typedef void (*Fn)(const MatJob);
-    Fn fn = matapply_reg<K, R, true, U, 0, PF, 0, true>;
-    static const uint8_t coef[R * K] = {15, 8, 6, 45, 48, 28, 153, 224, 120, 11, 231, 237, 137, 59, 179, 70, 241, 182, 186, 217, 98};
-    int nb = 0;
-    CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(fn), kBlock, 0));
-    int ncu = 256;
-    hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
-    std::vector<MatJob> jobs(sets.size());
-    for (size_t i = 0; i < sets.size(); ++i) {
-        MatJob& j = jobs[i];
-        std::memset(&j, 0, sizeof j);
-        j.sz = sz * ns;
-        j.nstripes = 1;
-        j.k = K;
-        j.r = R;
-        for (int q = 0; q < K; ++q) j.in[q] = sets[i].in + q * sz * ns;
-        for (int q = 0; q < R; ++q) j.out[q] = sets[i].out + q * sz * ns;
-        for (int c = 0; c < K * R; ++c)
-            for (int q = 0; q < 5; ++q) j.tab[c * 5 + q] = kHostBank.w[coef[c] * 8 + q];
-        j.tables = 1;
-        const uint64_t cps = (j.sz + kChunk - 1) / kChunk;
-        j.cps = static_cast<uint32_t>(cps);
-        const uint64_t lanes = (cps + U - 1) / U;
-        const uint64_t need = (lanes + kBlock - 1) / kBlock;
-        const uint64_t capb = cap ? uint64_t(ncu) * nb * cap : need;
-        const uint32_t grid = static_cast<uint32_t>(need < capb ? need : capb);
-        const uint64_t gstride = uint64_t(grid) * kBlock;
-        j.gs_s = static_cast<uint32_t>(gstride / cps);
-        j.gs_c = static_cast<uint32_t>(gstride % cps);
-        j.pad_ = grid;  // (unused by the kernel) the grid to launch
-    }
-    hipEvent_t a, b;
-    CK(hipEventCreate(&a));
-    CK(hipEventCreate(&b));
-    for (int i = 0; i < 3; ++i)
-        hipLaunchKernelGGL(fn, dim3(jobs[i % jobs.size()].pad_), dim3(kBlock), 0, 0, jobs[i % jobs.size()]);
-    CK(hipEventRecord(a, 0));
-    for (int i = 0; i < reps; ++i) {
-        const MatJob& j = jobs[(i + 3) % jobs.size()];
-        hipLaunchKernelGGL(fn, dim3(j.pad_), dim3(kBlock), 0, 0, j);
-    }
-    CK(hipEventRecord(b, 0));
-    CK(hipEventSynchronize(b));
-    float ms = 0;
-    CK(hipEventElapsedTime(&ms, a, b));
-    return ms / reps;
-}
-
-int walks() {
-    const uint64_t sz1 = (1u << 20) / 3 + 1;
-    for (uint32_t ns : {64u, 256u}) {
-        const uint64_t fp = uint64_t(K + R) * sz1 * ns;
-        const int nsets = std::max<int>(2, int((1536ull << 20) / fp) + 1);
-        std::vector<Lay> sets(nsets);
-        for (auto& L : sets) {
-            CK(hipMalloc(&L.in, ns * K * sz1));
-            CK(hipMalloc(&L.out, ns * R * sz1));
-            CK(hipMemset(L.in, 0x5A, ns * K * sz1));
-            L.ld = sz1;
-        }
-        CK(hipDeviceSynchronize());
-        const double bytes = double(K + R) * sz1 * ns;
-        for (int rnd = 0; rnd < 2; ++rnd) {
-            struct V {
-                const char* name;
-                float ms;
-            } vs[] = {
-                {"prod (dispatcher)", run_prod_bm(sets, 20, sz1, ns)},
-                {"U1 PF grid=units", run_walk<1, true>(sets, 20, sz1, ns, 0)},
-                {"U1 noPF grid=units", run_walk<1, false>(sets, 20, sz1, ns, 0)},
-                {"U2 grid=units/2", run_walk<2, false>(sets, 20, sz1, ns, 0)},
-                {"U4 grid=units/4", run_walk<4, false>(sets, 20, sz1, ns, 0)},
-                {"U2 cap=2", run_walk<2, false>(sets, 20, sz1, ns, 2)},
-                {"U4 cap=1", run_walk<4, false>(sets, 20, sz1, ns, 1)},
-                {"U1 PF cap=4", run_walk<1, true>(sets, 20, sz1, ns, 4)},
-            };
-            for (const V& v : vs)
-                printf("walk ns=%4u %-20s %8.1f us  %7.1f GB/s  (%.3f of 8 TB/s)\n", ns, v.name, v.ms * 1e3,
-                       bytes / (v.ms * 1e-3) / 1e9, bytes / (v.ms * 1e-3) / 8e12);
-        }
-        for (auto& L : sets) {
-            CK(hipFree(L.in));
-            CK(hipFree(L.out));
-        }
-    }
-    return 0;
-}
 
 // Size sweep of the production kernel on one long stripe per block (block-major),
 // cold: how the HBM fraction of a K=3/M=10 encode grows with the launch's size.
@@ -427,6 +325,62 @@ int tail() {
     return 0;
 }
 
+// The walk of the register kernels' single-stripe form (kernels.hip
+// reg_body_one) with the arithmetic replaced by an XOR: the lane's unit is its
+// global index, the last chunk and the spare lanes of the last workgroup are
+// shifted back to end at the row's end, no division, no branch, nt sc1 stores.
+// `one` times it against the dividing lane walk with the same stores (mb_tail,
+// f = 1) and the production kernel on cfg2's stripe, cold, interleaved.
+__global__ __launch_bounds__(256) void mb_one(const Lay L) {
+    const uint64_t sz = L.ld;
+    const uint64_t own = static_cast<uint64_t>(blockIdx.x * 256 + threadIdx.x) * 16;
+    const uint64_t off = own + 16 <= sz ? own : sz - 16;
+    u32x4 acc = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc ^= load16(L.in + off + j * L.ld);
+#pragma unroll
+    for (int r = 0; r < R; ++r) store16_pol<3>(L.out + off + r * L.ld, acc ^ uint32_t(r));
+}
+
+float run_one(const std::vector<Lay>& sets, int reps, uint32_t grid) {
+    hipEvent_t a, b;
+    CK(hipEventCreate(&a));
+    CK(hipEventCreate(&b));
+    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(mb_one, dim3(grid), dim3(256), 0, 0, sets[i % sets.size()]);
+    CK(hipEventRecord(a, 0));
+    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(mb_one, dim3(grid), dim3(256), 0, 0, sets[(i + 3) % sets.size()]);
+    CK(hipEventRecord(b, 0));
+    CK(hipEventSynchronize(b));
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, a, b));
+    return ms / reps;
+}
+
+int one() {
+    const uint64_t sz = (64ull << 20) / 3 + 1, ld = (sz + 255) / 256 * 256;
+    const int nsets = int((1536ull << 20) / (10 * ld)) + 1;
+    std::vector<Lay> sets(nsets);
+    for (auto& L : sets) {
+        CK(hipMalloc(&L.in, K * ld));
+        CK(hipMalloc(&L.out, R * ld));
+        CK(hipMemset(L.in, 0x5A, K * ld));
+        CK(hipMemset(L.out, 0, R * ld));
+        L.ld = ld;
+        L.cps = static_cast<uint32_t>(ld / 16);
+        L.units = L.cps;
+    }
+    CK(hipDeviceSynchronize());
+    const uint32_t grid = (sets[0].units + 255) / 256;
+    const double bytes = double(K + R) * ld;
+    for (int rnd = 0; rnd < 5; ++rnd) {
+        const float prod = run_prod(sets, 40, ld, 1), walk = run_tail<3>(sets, 40, grid, 0), str8 = run_one(sets, 40, grid);
+        printf("one round %d  prod %6.2f us (%.3f of 8 TB/s)  copy, dividing walk %6.2f us  copy, straight-line %6.2f us  "
+               "prod = %.3f of the straight-line copy\n",
+               rnd, prod * 1e3, bytes / (prod * 1e-3) / 8e12, walk * 1e3, str8 * 1e3, str8 / prod);
+    }
+    return 0;
+}
+
 // The `lane` copy walk with BS-thread workgroups (256 in production): fewer,
 // larger workgroups cost less to dispatch (launch_cost) -- does the walk gain?
 template <int BS>
@@ -517,8 +471,8 @@ int main(int argc, char** argv) {
     if (argc > 1 && std::string(argv[1]) == "launch") return launch_cost();
     if (argc > 1 && std::string(argv[1]) == "blocks") return blocks();
     if (argc > 1 && std::string(argv[1]) == "tail") return tail();
+    if (argc > 1 && std::string(argv[1]) == "one") return one();
     if (argc > 1 && std::string(argv[1]) == "ldsweep") return ldsweep();
-    if (argc > 1 && std::string(argv[1]) == "walks") return walks();
     const uint32_t ns = argc > 2 ? atoi(argv[2]) : 256;
     const uint64_t sz = (1u << 20) / 3 + 1;  // 349,526
     const uint64_t ld = (sz + 255) / 256 * 256;
@@ -546,19 +500,8 @@ int main(int argc, char** argv) {
     };
     for (int round = 0; round < 3; ++round) {
         printf("-- round %d\n", round);
-        setenv("ZFEC_HIP_XCD", "1", 1);
-        rep("prod_xcd", run_prod(sets, reps, sz, ns), double(K + R) * sz * ns);
-        setenv("ZFEC_HIP_XCD", "0", 1);
         rep("prod", run_prod(sets, reps, sz, ns), double(K + R) * sz * ns);
         rep("prod_bm", run_prod_bm(sets, reps, sz, ns), double(K + R) * sz * ns);
-        for (int gm : {1, 2, 4, 16}) {  // grid cap = CUs x resident workgroups x gm (grid-stride beyond)
-            char nm[32];
-            snprintf(nm, sizeof nm, "prod_gm%d", gm);
-            const int keep = g_grid_mult;
-            g_grid_mult = gm;
-            rep(nm, run_prod(sets, reps, sz, ns), double(K + R) * sz * ns);
-            g_grid_mult = keep;
-        }
         rep("lane", run<0, false, true, 0>(sets, reps, g_lane), enc_bytes);
         rep("persist", run<1, false, true, 0>(sets, reps, g_persist), enc_bytes);
         rep("xcd", run<2, false, true, 0>(sets, reps, g_lane), enc_bytes);

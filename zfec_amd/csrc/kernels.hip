@@ -455,8 +455,134 @@ __device__ __forceinline__ void reg_body(const RegJob<K, R>& job, uint32_t block
     }
 }
 
-template <int K, int R, int SP, bool PF, bool AL>
+// ---- single-stripe, one unit per lane (ONE) -----------------------------------
+// A launch of one stripe whose grid covers every 16-byte unit (launch_reg: no
+// grid-stride, sz >= 16) needs none of the walk: the lane's unit is its global
+// index, there is no stripe to divide out, no next unit to prefetch, and the
+// last chunk shifted back to end at sz leaves no byte tail.  reg_body's fixed
+// part is the whole life of such a wave (the 64 MiB K=3/M=10 stripe: 5,462
+// workgroups of one unit per lane).  Measured on that stripe's encode + decode
+// step, interleaved with the walking form: +3.3 % (profiles/r07_reg_one_ab.json).
+//
+// ZFEC_REG_ONE (A/B knob, tools/ab_build.sh; 0 = every launch walks reg_body)
+// ZFEC_REG_TPIPE (with ONE, AL shapes: 1 = the tables of row r+1 are requested
+// before row r is computed, row 0's with the header; 0 = each row's tables
+// right before use, as reg_compute_store's AL form; the same A/B: medians
+// 2557 GB/s without it, 2578 with it, a difference inside the runs' spread)
+#ifndef ZFEC_REG_ONE
+#define ZFEC_REG_ONE 1
+#endif
+#ifndef ZFEC_REG_TPIPE
+#define ZFEC_REG_TPIPE 1
+#endif
+
+// Requests one dword of every 64-byte line of the argument block (scalar
+// loads, results unused) so that a launch's first waves, which find the
+// scalar cache empty, take those misses at once instead of one per row.  The
+// block's base is only known to be 16-byte aligned: offsets 0, 64, ... and the
+// last dword reach every line it touches.  The destinations stay allocated
+// until the wait, which the header's own wait would make anyway (scalar loads
+// return out of order: any wait is for all of them).
+template <class J>
+struct KernargTouch {
+    static constexpr int kLines = (sizeof(J) + 63) / 64;
+    uint32_t t[kLines + 1];
+    __device__ __forceinline__ void request() {
+        typedef const __attribute__((address_space(4))) uint32_t* KWords;
+        const KWords base = (KWords)__builtin_amdgcn_kernarg_segment_ptr();
+#pragma unroll
+        for (int i = 0; i < kLines; ++i)
+            asm volatile("s_load_dword %0, %1, %2" : "=s"(t[i]) : "s"(base), "n"(i * 64));
+        asm volatile("s_load_dword %0, %1, %2" : "=s"(t[kLines]) : "s"(base), "n"(int(sizeof(J)) - 4));
+    }
+    __device__ __forceinline__ void wait() {
+        __builtin_amdgcn_sched_barrier(0);  // what was requested above stays above
+        asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(t[0]));
+#pragma unroll
+        for (int i = 1; i <= kLines; ++i) asm volatile("" ::"s"(t[i]));
+    }
+};
+
+template <int K, int R>
+struct RowArgs {
+    Tab t[K];
+    uint8_t* out;
+};
+
+// Row r's tables and output pointer, read from the argument segment at this
+// point of the program (kernarg_job).
+template <int K, int R>
+__device__ __forceinline__ RowArgs<K, R> reg_row_args(int r) {
+    const KPtr<RegJob<K, R>> kj = kernarg_job<RegJob<K, R>>();
+    RowArgs<K, R> a;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const uint32_t i = (r * K + j) * 5;
+        a.t[j] = Tab{kj->tab[i], kj->tab[i + 1], kj->tab[i + 2], kj->tab[i + 3], kj->tab[i + 4]};
+    }
+    a.out = kj->out[r];
+    return a;
+}
+
+template <int K, int R, int SP, bool AL, bool TP>
+__device__ __forceinline__ void reg_body_one(const RegJob<K, R>& job) {
+    RowArgs<K, R> cur;
+    if constexpr (AL && TP) {
+        KernargTouch<RegJob<K, R>> touch;
+        touch.request();
+        cur = reg_row_args<K, R>(0);
+        touch.wait();
+    }
+    Tab T[R][K];
+    if constexpr (!AL) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < K; ++j) T[r][j] = reg_table(job, r * K + j);
+    }
+    // The lane's chunk; the last one is shifted back to end at sz
+    // (chunk_span<kChunk, true>, always full here: sz >= 16), and so is every
+    // lane of the last workgroup past it: they store the same bytes again,
+    // as overlapping chunks do, and the wave needs no branch.
+    const uint64_t sz = job.sz;
+    const uint64_t own = static_cast<uint64_t>(blockIdx.x * kBlock + threadIdx.x) * kChunk;
+    const uint64_t off = own + kChunk <= sz ? own : sz - kChunk;
+    u32x4 x[K];
+    reg_load<K, R>(job, x, off, true, kChunk);
+    if constexpr (AL && TP) {
+        Sel sel[4][K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            sel[0][j] = selectors(x[j].x);
+            sel[1][j] = selectors(x[j].y);
+            sel[2][j] = selectors(x[j].z);
+            sel[3][j] = selectors(x[j].w);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            RowArgs<K, R> nxt;
+            if (r + 1 < R) {
+                nxt = reg_row_args<K, R>(r + 1);
+                __builtin_amdgcn_sched_barrier(0);  // the requests stay ahead of this row's arithmetic
+            }
+            const u32x4 y{gf_dot<K>(cur.t, sel[0]), gf_dot<K>(cur.t, sel[1]), gf_dot<K>(cur.t, sel[2]),
+                          gf_dot<K>(cur.t, sel[3])};
+            store16_pol<SP>(cur.out + off, y);
+            if (r + 1 < R) cur = nxt;
+        }
+    } else {
+        reg_compute_store<K, R, SP, AL>(job, T, x, off, true, kChunk);
+    }
+}
+
+// ONE: 0 = the grid-stride walk (reg_body); 1 = reg_body_one; 2 = reg_body_one
+// with pipelined table loads (AL shapes).
+template <int K, int R, int SP, bool PF, bool AL, int ONE = 0>
 __global__ __launch_bounds__(kBlock) void matapply_reg(const RegJob<K, R> job) {
+    if constexpr (ONE != 0) {
+        reg_body_one<K, R, SP, AL, ONE == 2>(job);  // never a one-workgroup signalling launch (launch_reg)
+        return;
+    }
     reg_body<K, R, SP, PF, AL, 0>(job, blockIdx.x);
     // one-workgroup launches of a synchronous small call: publish completion
     // in pinned host memory, so the host need not wait in
@@ -2473,6 +2599,14 @@ hipError_t launch_reg(const ApplySpec& a, hipStream_t stream, uint32_t* sig) {
             job.done_seq = t_signal_seq;
             t_signal_used = true;
         }
+#if ZFEC_REG_ONE
+        // one stripe, every unit has its own lane, no byte tail, no signal:
+        // the straight-line form (reg_body_one)
+        else if (a.nstripes == 1 && a.sz >= kChunk && uint64_t(grid) * kBlock >= job.cps) {
+            constexpr int kOne = kArgLoad && ZFEC_REG_TPIPE ? 2 : 1;
+            fn = !ma ? matapply_reg<K, R, 3, kPrefetch, kArgLoad, kOne> : matapply_reg<K, R, 0, kPrefetch, kArgLoad, kOne>;
+        }
+#endif
     }
     return launch_job(reinterpret_cast<const void*>(fn), grid, kBlock, 0, stream, job);
 }
