@@ -249,6 +249,78 @@ int fec_verify_batch(const fec_t* code,
  * row-major into rows[c*k].  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
 int fec_verify_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
 
+/* Batched repair: rebuild any lost blocks of every stripe, primaries and parity
+ * alike, from the k blocks the stripe still holds, in one call (the step after
+ * fec_verify_batch in a store's scrub-and-repair cycle).
+ *
+ * present: npatterns x k block numbers (host memory); targets: npatterns x
+ * ntargets block numbers or FEC_REPAIR_NONE (host memory).  Stripe s uses
+ * pattern p = pattern_of[s]: slot j of the stripe, at src + s*src_stripe_stride
+ * + j*src_block_stride, holds block present[p*k+j] (k distinct numbers < n, in
+ * ANY slot order, as in fec_decode_batch_mixed), and output row i of the stripe,
+ * at dst + s*dst_stripe_stride + i*dst_block_stride, receives block
+ * targets[p*ntargets+i] of that stripe: exactly the bytes fec_decode followed
+ * by fec_encode of that block number would produce (the primary itself for a
+ * number below k).  The matrix applied is row i = E[target i] . inverse(E[present])
+ * (E: the code's enc_matrix).  A target may be any number < n: one that is also
+ * present gives a unit row, so its output is a copy; duplicates within a
+ * pattern are allowed, every output row being independent.
+ *
+ * A FEC_REPAIR_NONE target marks a row its pattern does not use: the row is NOT
+ * written, none of its sz bytes and nothing past them.  So one call serves
+ * stripes that lost different numbers of blocks: ntargets is the batch's
+ * maximum, shorter lists are filled with FEC_REPAIR_NONE, and a pattern whose
+ * targets are all FEC_REPAIR_NONE leaves its stripes untouched.
+ * 1 <= ntargets <= 32, npatterns <= 65536.
+ *
+ * pattern_of: nstripes pattern ids (unsigned, 4 bytes each) in host OR device
+ * memory.  Ids in DEVICE memory cannot be checked by the host: a stripe whose id
+ * is >= npatterns is left unwritten (no table is read for it), and no error is
+ * reported.  pattern_of == NULL requires npatterns == 1: every stripe uses
+ * pattern 0, and the call is one shared-matrix application of the pattern's
+ * rows (FEC_REPAIR_NONE rows dropped from the launch) by whatever kernel
+ * fec_encode_batch would pick for that shape, graph capture included.
+ *
+ * src and dst are device memory on one device, or page-locked host memory;
+ * pageable host memory returns FEC_EINVAL (this call does not stage).  dst must
+ * not overlap src: the result is then unspecified.  Strides as in
+ * fec_decode_batch_mixed.  FEC_FLAG_ASYNC and FEC_FLAG_LIBRARY_STREAM as there;
+ * FEC_FLAG_ROW_PADDING is accepted and ignored.  With pattern_of non-NULL the
+ * call returns FEC_EINVAL while the stream is being captured into a graph (the
+ * pattern tables are uploaded, through staging the library owns, when the call
+ * is made; present, targets and pattern_of may be reused as soon as it returns).
+ *
+ * Checked before any GPU work, in this order, each FEC_EINVAL with a message
+ * naming the pattern or stripe: invalid fec_t; NULL src, dst, present or
+ * targets; ntargets == 0 or > 32; npatterns == 0 with stripes to repair, or
+ * more than 65536 patterns; pattern_of == NULL with npatterns != 1; a present
+ * number >= n; a duplicate among a pattern's present numbers; a target that is
+ * neither < n nor FEC_REPAIR_NONE; an id >= npatterns in a HOST-side
+ * pattern_of.  Then FEC_ENODEV when no GPU is visible.  nstripes == 0 or
+ * sz == 0 returns FEC_OK.
+ *
+ * k <= 4 runs on matrepair_mixed<k, r>, at most 8 rows per launch (11 targets
+ * are launches of 8 and 3 rows over one upload of the tables; a group of rows
+ * that no pattern uses is skipped).  k > 4 is cut into runs of consecutive
+ * stripes with one id, each run one shared-matrix launch of that pattern's
+ * used rows; a device-side pattern_of is first copied to the host, which
+ * SYNCHRONISES the stream. */
+#define FEC_REPAIR_NONE 0xFFFFFFFFu /* a target slot this pattern does not use */
+int fec_repair_batch(const fec_t* code,
+                     const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                     gf* dst, size_t dst_block_stride, size_t dst_stripe_stride,
+                     const unsigned* present, const unsigned* targets,
+                     size_t ntargets, size_t npatterns,
+                     const unsigned* pattern_of,
+                     size_t sz, size_t nstripes, void* stream, unsigned flags);
+
+/* Host only, no GPU: the ntargets x k matrix fec_repair_batch applies for one
+ * pattern (row i yields block targets[i] from the k slots; a FEC_REPAIR_NONE
+ * row is all zeros), row-major into rows[ntargets*k].  The same checks on the
+ * one pattern.  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
+int fec_repair_rows(const fec_t* code, const unsigned* present, const unsigned* targets, size_t ntargets,
+                    gf* rows);
+
 /* Batched calls over several GPUs of this process.  The nstripes stripes are
  * split into contiguous, balanced ranges, one per entry of devices[] (entry d
  * gets stripes [d*q + min(d, e), ...), q = nstripes / ndevices, e = the

@@ -421,6 +421,167 @@ class Decoder(_fec.Decoder):
                                                     stream=stream, flags=flags)
         return out
 
+    def repair_batch(self, blocks, blocknums, targets, out=None):
+        """Rebuild any lost blocks, primaries and parity alike, of many
+        independent stripes that each hold their own k blocks, in one launch
+        (fec_repair_batch).
+
+        blocks: uint8 device tensor [nstripes, k, sz] (strides as in
+        decode_batch_mixed).  blocknums: an [nstripes, k] integer array -- a
+        list of lists, a numpy array, or a torch tensor on the host or on the
+        device -- row s holding the block numbers of stripe s's slots,
+        distinct, in [0, m-1] and in any slot order.  targets: an [nstripes, t]
+        integer array of the same kinds, 1 <= t <= 32: row s lists the block
+        numbers to rebuild for stripe s, in [0, m-1], or -1 for "none" (a stripe
+        that lost fewer than t blocks).  A target that is also present is
+        copied; duplicates are allowed.  Alternatively blocknums is a tuple
+        (patterns [P, k], pattern_of [nstripes]) and targets is [P, t], one row
+        per pattern.  The array form is reduced to that with unique() over the
+        concatenated [nstripes, k + t] rows where the arrays live; a device
+        array's ids stay on the device.  Device-side pattern_of ids cannot be
+        range-checked: a stripe whose id is not below P is left unwritten.
+
+        Returns [nstripes, t, sz]: row i of stripe s is block targets[s][i] of
+        that stripe, bit-identical to decode followed by encode.  With out=None
+        a new tensor is allocated (block-major when the input was) and the rows
+        of -1 targets are unspecified; with out (a uint8 tensor of that shape
+        on the blocks' device, contiguous along sz, not overlapping blocks) the
+        rows of -1 targets keep their contents, and out is returned.  The work
+        is enqueued on the current stream.  Host (numpy) blocks are not staged
+        by this call."""
+        import numpy as np
+
+        k, m = self.k, self.m
+        if _is_host_array(blocks):
+            raise Error("Precondition violation: repair_batch takes a device tensor; host (numpy) blocks are not "
+                        "staged by this call")
+        is_tensor = type(blocks).__module__.startswith("torch") and hasattr(blocks, "data_ptr")
+        if not is_tensor or str(blocks.dtype) != "torch.uint8" or blocks.dim() != 3:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz]" % k)
+        if blocks.shape[1] != k:
+            raise Error("Precondition violation: blocks is required to hold %d blocks per stripe, not %d"
+                        % (k, blocks.shape[1]))
+        ns = blocks.shape[0]
+
+        def host_table(x, what):
+            a = x.cpu().numpy() if hasattr(x, "data_ptr") else np.asarray(x)
+            if a.ndim != 2 or (a.size and a.dtype.kind not in "iu"):
+                raise Error("Precondition violation: %s is required to be a 2-D integer array" % what)
+            return a
+
+        ids_dev = None  # device tensor of ids, or
+        ids_host = None  # numpy array of ids
+        if isinstance(blocknums, tuple) and len(blocknums) == 2:
+            pats, ids = blocknums
+            pats = host_table(pats, "patterns")
+            tgts = host_table(targets, "targets")
+            if tgts.shape[0] != pats.shape[0]:
+                raise Error("Precondition violation: targets is required to hold one row per pattern: %d rows, %d "
+                            "patterns" % (tgts.shape[0], pats.shape[0]))
+            if hasattr(ids, "data_ptr"):
+                if ids.dim() != 1 or ids.dtype.is_floating_point:
+                    raise Error("Precondition violation: pattern_of is required to be a 1-D integer array")
+                nids = ids.shape[0]
+                if ids.is_cuda:
+                    ids_dev = ids
+                else:
+                    ids_host = ids.numpy()
+            else:
+                ids_host = np.asarray(ids)
+                if ids_host.ndim != 1 or (ids_host.size and ids_host.dtype.kind not in "iu"):
+                    raise Error("Precondition violation: pattern_of is required to be a 1-D integer array")
+                nids = ids_host.shape[0]
+            if nids != ns:
+                raise Error("Precondition violation: pattern_of is required to hold nstripes = %d ids, not %d"
+                            % (ns, nids))
+        else:
+            def stripe_table(x, what, width):
+                if hasattr(x, "data_ptr"):  # torch tensor, host or device
+                    a, ok = x, x.dim() == 2 and not x.dtype.is_floating_point
+                else:
+                    a = np.asarray(x)
+                    ok = a.ndim == 2 and (a.dtype.kind in "iu" or not a.size)
+                if not ok or a.shape[0] != ns or (width is not None and a.shape[1] != width):
+                    raise Error("Precondition violation: %s is required to be an integer array [nstripes, %s] = "
+                                "[%d, %s]" % (what, "t" if width is None else "k", ns, "t" if width is None else width))
+                return a
+
+            tabs = [stripe_table(blocknums, "blocknums", k), stripe_table(targets, "targets", None)]
+            on_dev = [x for x in tabs if hasattr(x, "data_ptr") and x.is_cuda]
+            if on_dev:
+                import torch
+
+                both = torch.cat([torch.as_tensor(x).to(on_dev[0].device).long() for x in tabs], dim=1)
+                urows, inv = torch.unique(both, dim=0, return_inverse=True)
+                urows = urows.cpu().numpy()
+                ids_dev = inv.reshape(-1)
+            else:
+                both = np.concatenate([x.numpy() if hasattr(x, "data_ptr") else x for x in tabs],
+                                      axis=1).astype(np.int64)
+                if ns:
+                    urows, inv = np.unique(both, axis=0, return_inverse=True)
+                else:
+                    urows, inv = both, np.zeros(0, dtype=np.int64)
+                ids_host = inv.reshape(-1)
+            pats, tgts = urows[:, :k], urows[:, k:]
+        if pats.shape[1] != k:
+            raise Error("Precondition violation: patterns is required to be an integer array [P, k = %d]" % k)
+        t = tgts.shape[1]
+        if t < 1 or t > 32:
+            raise Error("Precondition violation: targets is required to hold between 1 and 32 block nums per stripe, "
+                        "not %d" % t)
+        if pats.size and (pats.min() < 0 or pats.max() >= m):
+            bad = pats[(pats < 0) | (pats >= m)][0]
+            raise Error("Precondition violation: block nums are required to be in [0, m-1] = [0, %d], but one was %d"
+                        % (m - 1, bad))
+        for row in pats:
+            if len(set(row.tolist())) != k:
+                raise Error("Precondition violation: the block nums of a stripe are required to be distinct, but one "
+                            "stripe has %r" % (row.tolist(),))
+        if tgts.size and (tgts.min() < -1 or tgts.max() >= m):
+            bad = tgts[(tgts < -1) | (tgts >= m)][0]
+            raise Error("Precondition violation: targets are required to be in [0, m-1] = [0, %d] or -1 (none), but "
+                        "one was %d" % (m - 1, bad))
+        npat = pats.shape[0]
+        if ids_host is not None and ids_host.size and (ids_host.min() < 0 or ids_host.max() >= npat):
+            raise Error("Precondition violation: pattern_of ids are required to be in [0, %d]" % (npat - 1))
+        sz = blocks.shape[2]
+        if out is not None:
+            out_ok = type(out).__module__.startswith("torch") and hasattr(out, "data_ptr")
+            if not out_ok or str(out.dtype) != "torch.uint8" or tuple(out.shape) != (ns, t, sz):
+                raise Error("Precondition violation: out is required to be a uint8 tensor [nstripes, t, sz] = "
+                            "[%d, %d, %d]" % (ns, t, sz))
+            if out.device != blocks.device:
+                raise Error("Precondition violation: out is required to be on the blocks' device")
+            if (sz > 1 and out.stride(2) != 1) or min(out.stride(0), out.stride(1)) < 0:
+                raise Error("Precondition violation: out rows are required to be contiguous along sz")
+        if not blocks.is_cuda:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
+                        "not a host tensor" % k)
+        ns, sz, sbs, sss, ptr = _batch_view(blocks, k, "blocks")
+        if out is None:
+            out = _batch_out(blocks, sss < sbs, ns, t, sz)
+        if ns and sz and npat:
+            import torch
+
+            if ids_dev is not None:
+                if ids_dev.device != blocks.device:
+                    raise Error("Precondition violation: device blocknums are required to be on the blocks' device")
+                ids = ids_dev.to(torch.int32).contiguous()  # non-negative ids: the bits of uint32
+                ids_ptr = ids.data_ptr()
+            else:
+                ids = np.ascontiguousarray(ids_host, dtype=np.uint32)
+                ids_ptr = ids.ctypes.data
+            optr, obs, oss = _batch_strides(out)
+            stream, flags = _batch_call_args(blocks)
+            # `ids` need only outlive the call: host ids are copied into the
+            # library's staging, device ids are read by work of this stream
+            with _as_error():
+                _capi_code(self).repair_batch(ptr, sbs, sss, optr, obs, oss, np.ascontiguousarray(pats, dtype=np.int64),
+                                              np.ascontiguousarray(tgts, dtype=np.int64), ids_ptr, sz, ns,
+                                              stream=stream, flags=flags)
+        return out
+
     def verify_batch(self, blocks, blocknums):
         """Check many independent stripes for consistency without writing any
         block (scrubbing; fec_verify_batch).

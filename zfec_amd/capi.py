@@ -61,7 +61,10 @@ SYMBOLS = [
     ("fec_mixed_decode_rows", ctypes.c_int, [_P, _UP, _P]),
     ("fec_verify_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
     ("fec_verify_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
+    ("fec_repair_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _UP, _UP, _SZ, _SZ, _P, _SZ, _SZ, _P, _U]),
+    ("fec_repair_rows", ctypes.c_int, [_P, _UP, _UP, _SZ, _P]),
 ]
+FEC_REPAIR_NONE = 0xFFFFFFFF  # a target slot its pattern does not use
 
 JIT_OFF, JIT_AUTO, JIT_FORCE = 0, 1, 2
 FEC_JOB_ENCODE, FEC_JOB_DECODE = 0, 1
@@ -178,6 +181,26 @@ def _nums(vals):
     return a
 
 
+def _uint_table(rows, width, what):
+    """((unsigned* argument, keep-alive), nrows, width) of a table of unsigned
+    numbers: a sequence of equally long sequences or a 2-D integer numpy array;
+    -1 stands for 0xFFFFFFFF.  `width`: the required row length, or None."""
+    if hasattr(rows, "ctypes"):
+        import numpy as np
+
+        if rows.ndim != 2 or (rows.size and rows.dtype.kind not in "iu") or (width is not None and
+                                                                           rows.shape[1] != width):
+            raise FecError(what)
+        arr = np.ascontiguousarray(rows.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        return (ctypes.cast(arr.ctypes.data, _UP) if arr.size else uint_array([]), arr), arr.shape[0], arr.shape[1]
+    rows = [tuple(r) for r in rows]
+    w = width if width is not None else (len(rows[0]) if rows else 0)
+    for r in rows:
+        if len(r) != w:
+            raise FecError(what)
+    return (uint_array([int(x) & 0xFFFFFFFF for r in rows for x in r]), None), len(rows), w
+
+
 class Code(object):
     """RAII wrapper around fec_t* (fec_new / fec_free)."""
 
@@ -250,6 +273,23 @@ class Code(object):
         if st:
             check(st)
 
+    def repair_batch(self, src, sbs, sss, dst, dbs, dss, present, targets, pattern_of_ptr, sz, nstripes, stream=0,
+                     flags=FEC_FLAG_ASYNC):
+        """fec_repair_batch: `present` is a sequence of k-number sequences (or
+        a [P, k] integer numpy array), `targets` one of t-number sequences (or
+        [P, t]) whose entries are block numbers or FEC_REPAIR_NONE (-1 is taken
+        for it); `pattern_of_ptr` is the address of nstripes uint32 pattern ids
+        in host or device memory, which the caller keeps alive until the call
+        returns, or 0 (P = 1: every stripe uses pattern 0)."""
+        pres, npat, _ = _uint_table(present, self.k, "present is required to be [npatterns, k = %d]" % self.k)
+        tgts, ntp, nt = _uint_table(targets, None, "targets is required to be [npatterns, ntargets]")
+        if ntp != npat:
+            raise FecError("targets is required to hold one row per pattern: %d rows, %d patterns" % (ntp, npat))
+        st = lib().fec_repair_batch(self.ptr, src, sbs, sss, dst, dbs, dss, pres[0], tgts[0], nt, npat,
+                                    pattern_of_ptr or None, sz, nstripes, stream or None, flags)
+        if st:
+            check(st)
+
     def verify_batch(self, src, sbs, sss, block_nums, sz, nstripes, mismatch_ptr, stream=0, flags=FEC_FLAG_ASYNC):
         """fec_verify_batch: slot j of every stripe holds block block_nums[j],
         the first k slots the basis, the rest the checks; `mismatch_ptr` is the
@@ -301,6 +341,20 @@ def verify_rows(code, block_nums):
     rows = (ctypes.c_ubyte * max(1, (len(nums) - code.k) * code.k))()
     check(lib().fec_verify_rows(code.ptr, uint_array(nums), len(nums), ctypes.cast(rows, _P)))
     return bytes(rows)
+
+
+def repair_rows(code, present, targets):
+    """fec_repair_rows: the t*k bytes (row-major, t = len(targets)) of the
+    matrix fec_repair_batch applies for one pattern; row i yields block
+    targets[i] from the k slots holding `present`, a FEC_REPAIR_NONE (or -1)
+    row is all zeros.  Host only."""
+    present = list(present)
+    if len(present) != code.k:
+        raise FecError("present is required to hold k = %d block numbers" % code.k)
+    tg = [int(x) & 0xFFFFFFFF for x in targets]
+    rows = (ctypes.c_ubyte * max(1, len(tg) * code.k))()
+    check(lib().fec_repair_rows(code.ptr, uint_array(present), uint_array(tg), len(tg), ctypes.cast(rows, _P)))
+    return bytes(rows)[:len(tg) * code.k]
 
 
 class BatchJob(ctypes.Structure):

@@ -1552,6 +1552,18 @@ int check_verify_nums(const fec_t* code, const unsigned* nums, size_t nb) {
     return FEC_OK;
 }
 
+// out[0..k) = row `num` of enc_matrix times the k x k matrix inv: the row that
+// yields block `num` from the slots inv decodes (fec_verify_rows, fec_repair_rows).
+void enc_row_times(const fec_t* code, unsigned num, const uint8_t* inv, uint8_t* out) {
+    const unsigned k = code->k;
+    const uint8_t* e = code->enc_matrix + size_t(num) * k;
+    for (unsigned j = 0; j < k; ++j) {
+        uint8_t acc = 0;
+        for (unsigned l = 0; l < k; ++l) acc ^= gf_mul(e[l], inv[size_t(l) * k + j]);
+        out[j] = acc;
+    }
+}
+
 // P = E[checks] . inverse(E[basis]), c x k row-major: row i yields the block in
 // slot k + i from the k basis slots.
 int verify_rows(const fec_t* code, const unsigned* nums, size_t nb, uint8_t* P) {
@@ -1559,14 +1571,7 @@ int verify_rows(const fec_t* code, const unsigned* nums, size_t nb, uint8_t* P) 
     thread_local std::vector<uint8_t> inv;
     inv.resize(size_t(k) * k);
     if (mixed_rows(code, nums, inv.data())) return t_status;
-    for (size_t i = 0; i + k < nb; ++i) {
-        const uint8_t* e = code->enc_matrix + size_t(nums[k + i]) * k;
-        for (unsigned j = 0; j < k; ++j) {
-            uint8_t acc = 0;
-            for (unsigned l = 0; l < k; ++l) acc ^= gf_mul(e[l], inv[size_t(l) * k + j]);
-            P[i * k + j] = acc;
-        }
-    }
+    for (size_t i = 0; i + k < nb; ++i) enc_row_times(code, nums[k + i], inv.data(), P + i * k);
     return FEC_OK;
 }
 
@@ -1754,6 +1759,233 @@ FEC_API int fec_verify_batch(const fec_t* code, const gf* src, size_t src_block_
     return guarded([&] {
         return run_verify(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
                           mismatch, stream, flags);
+    });
+}
+
+// ---- batched repair: any lost blocks of every stripe -----------------------------------
+namespace {
+// The checks of np repair patterns, in the documented order: every present
+// number's range, then duplicates among a pattern's present numbers, then the
+// targets (a block number or FEC_REPAIR_NONE).
+int check_repair_patterns(const fec_t* code, const unsigned* present, const unsigned* targets, size_t nt, size_t np) {
+    const unsigned k = code->k;
+    for (size_t p = 0; p < np; ++p)
+        for (unsigned j = 0; j < k; ++j)
+            if (present[p * k + j] >= code->n)
+                return set_status(FEC_EINVAL, "pattern %zu: block number %u out of range (n = %u)", p,
+                                  present[p * k + j], unsigned(code->n));
+    for (size_t p = 0; p < np; ++p)
+        if (check_pattern(code, present + p * k, p)) return t_status;
+    for (size_t p = 0; p < np; ++p)
+        for (size_t i = 0; i < nt; ++i) {
+            const unsigned t = targets[p * nt + i];
+            if (t != FEC_REPAIR_NONE && t >= code->n)
+                return set_status(FEC_EINVAL, "pattern %zu: target %u is neither a block number (n = %u) nor "
+                                              "FEC_REPAIR_NONE", p, t, unsigned(code->n));
+        }
+    return FEC_OK;
+}
+
+// One pattern's nt x k matrix: row i = E[targets[i]] . inverse(E[present]), a
+// FEC_REPAIR_NONE row all zeros; *mask (may be null) gets bit i for every other row.
+int repair_rows(const fec_t* code, const unsigned* present, const unsigned* targets, size_t nt, uint8_t* rows,
+                uint32_t* mask) {
+    const unsigned k = code->k;
+    thread_local std::vector<uint8_t> inv;
+    inv.resize(size_t(k) * k);
+    if (mixed_rows(code, present, inv.data())) return t_status;
+    uint32_t live = 0;
+    for (size_t i = 0; i < nt; ++i) {
+        if (targets[i] == FEC_REPAIR_NONE) {
+            std::memset(rows + i * k, 0, k);
+        } else {
+            enc_row_times(code, targets[i], inv.data(), rows + i * k);
+            live |= 1u << i;
+        }
+    }
+    if (mask) *mask = live;
+    return FEC_OK;
+}
+
+// The live rows of one pattern as ONE shared-matrix application over nstripes
+// stripes (whatever kernel apply_matrix picks; a block-major batch collapses
+// into one long stripe as in fec_encode_batch).  Rows whose mask bit is clear
+// are dropped from the launch, so their outputs are not touched.
+int repair_shared(const uint8_t* rows, uint32_t mask, unsigned k, size_t nt, const gf* src, size_t sbs, size_t sss,
+                  gf* dst, size_t dbs, size_t dss, size_t sz, size_t nstripes, hipStream_t st) {
+    thread_local std::vector<uint8_t> coef;
+    coef.resize(nt * k);
+    const uint8_t* in[kMaxWideIn];
+    uint8_t* out[kRepairMaxRows];
+    unsigned r = 0;
+    for (size_t i = 0; i < nt; ++i)
+        if ((mask >> i) & 1u) {
+            std::memcpy(&coef[size_t(r) * k], rows + i * k, k);
+            out[r++] = dst + i * dbs;
+        }
+    if (!r) return FEC_OK;
+    for (unsigned j = 0; j < k; ++j) in[j] = src + j * sbs;
+    batch_geometry(k, r, sbs, sss, dbs, dss, 0, sz, nstripes);
+    return apply_matrix(coef.data(), k, r, in, out, sz, nstripes, sss, dss, st);
+}
+
+int run_repair(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst, size_t dbs, size_t dss,
+               const unsigned* present, const unsigned* targets, size_t nt, size_t npatterns,
+               const unsigned* pattern_of, int idev, size_t sz, size_t nstripes, void* stream, unsigned flags) {
+    const unsigned k = code->k;
+    if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
+    // device memory on one device, or page-locked host memory (read and written in place)
+    const size_t src_extent = (nstripes - 1) * sss + (k - 1) * sbs + sz;
+    const size_t dst_extent = (nstripes - 1) * dss + (nt - 1) * dbs + sz;
+    const int sdev = pointer_device(src), ddev = pointer_device(dst);
+    const gf* zsrc = src;
+    gf* zdst = dst;
+    if (sdev < 0 && !(zsrc = mapped_block(src, src_extent)))
+        return set_status(FEC_EINVAL, "fec_repair_batch takes device or page-locked host memory: src is pageable "
+                                      "host memory, which this call does not stage");
+    if (ddev < 0 && !(zdst = const_cast<gf*>(mapped_block(dst, dst_extent))))
+        return set_status(FEC_EINVAL, "fec_repair_batch takes device or page-locked host memory: dst is pageable "
+                                      "host memory, which this call does not stage");
+    if (sdev >= 0 && ddev >= 0 && sdev != ddev)
+        return set_status(FEC_EINVAL, "batched entry points take memory on one device");
+    int dev = sdev >= 0 ? sdev : ddev;
+    if (dev < 0) dev = idev;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
+    if (idev >= 0 && idev != dev)
+        return set_status(FEC_EINVAL, "pattern_of lives on device %d, the blocks on device %d", idev, dev);
+    DeviceGuard guard(dev);
+    DevCtx* d = nullptr;
+    if (dev_ctx(dev, &d)) return t_status;
+    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
+    hipError_t e;
+    thread_local std::vector<uint8_t> rows;
+    thread_local std::vector<uint32_t> masks;
+    if (!pattern_of) {
+        // one pattern for every stripe: a shared-matrix application, no new kernel
+        rows.resize(nt * k);
+        uint32_t mask = 0;
+        if (repair_rows(code, present, targets, nt, rows.data(), &mask)) return t_status;
+        if (repair_shared(rows.data(), mask, k, nt, zsrc, sbs, sss, zdst, dbs, dss, sz, nstripes, st)) return t_status;
+    } else {
+        if (stream_capturing(st))
+            return set_status(FEC_EINVAL, "fec_repair_batch: the stream is being captured into a graph (the "
+                                          "pattern tables are uploaded when the call is made)");
+        if (k <= kMixedMaxK) {
+            rows.resize(npatterns * nt * k);
+            masks.resize(npatterns);
+            for (size_t p = 0; p < npatterns; ++p)
+                if (repair_rows(code, present + p * k, targets + p * nt, nt, &rows[p * nt * k], &masks[p]))
+                    return t_status;
+            const uint8_t* in[kMixedMaxK];
+            uint8_t* out[kRepairMaxRows];
+            for (unsigned j = 0; j < k; ++j) in[j] = zsrc + j * sbs;
+            for (size_t i = 0; i < nt; ++i) out[i] = zdst + i * dbs;
+            RepairSpec r;
+            r.k = k;
+            r.t = static_cast<uint32_t>(nt);
+            r.rows = rows.data();
+            r.masks = masks.data();
+            r.npatterns = static_cast<uint32_t>(npatterns);
+            r.ids_host = idev < 0 ? pattern_of : nullptr;
+            r.ids_dev = idev < 0 ? nullptr : pattern_of;
+            r.in = in;
+            r.out = out;
+            r.sz = sz;
+            r.nstripes = nstripes;
+            r.in_sstride = sss;
+            r.out_sstride = dss;
+            ++t_launches;
+            if ((e = launch_repair(r, st)) != hipSuccess) return hip_fail(e, "launch_repair");
+        } else {
+            // codes past the register shapes: maximal runs of consecutive stripes
+            // with one id, each one shared-matrix application of that pattern's live rows
+            thread_local std::vector<unsigned> hids;
+            const unsigned* ids = pattern_of;
+            if (idev >= 0) {
+                hids.resize(nstripes);
+                if ((e = hipMemcpyAsync(hids.data(), pattern_of, nstripes * sizeof(unsigned), hipMemcpyDeviceToHost,
+                                        st)) != hipSuccess)
+                    return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
+                if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+                ids = hids.data();
+            }
+            std::unordered_map<unsigned, std::pair<std::vector<uint8_t>, uint32_t>> rows_of;
+            for (size_t s0 = 0; s0 < nstripes;) {
+                size_t s1 = s0 + 1;
+                while (s1 < nstripes && ids[s1] == ids[s0]) ++s1;
+                const unsigned id = ids[s0];
+                if (id < npatterns) {  // (device ids are not checked: such stripes stay unwritten, as on the kernel)
+                    std::pair<std::vector<uint8_t>, uint32_t>& pr = rows_of[id];
+                    if (pr.first.empty()) {
+                        pr.first.resize(nt * k);
+                        if (repair_rows(code, present + size_t(id) * k, targets + size_t(id) * nt, nt,
+                                        pr.first.data(), &pr.second))
+                            return t_status;
+                    }
+                    if (repair_shared(pr.first.data(), pr.second, k, nt, zsrc + s0 * sss, sbs, sss, zdst + s0 * dss,
+                                      dbs, dss, sz, s1 - s0, st))
+                        return t_status;
+                }
+                s0 = s1;
+            }
+        }
+    }
+    if (!(flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_repair_rows(const fec_t* code, const unsigned* present, const unsigned* targets, size_t ntargets,
+                            gf* rows) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!present) return set_status(FEC_EINVAL, "present is NULL");
+    if (!targets) return set_status(FEC_EINVAL, "targets is NULL");
+    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
+    if (ntargets == 0 || ntargets > kRepairMaxRows)
+        return set_status(FEC_EINVAL, "ntargets is %zu: a pattern has between 1 and %u targets", ntargets,
+                          unsigned(kRepairMaxRows));
+    if (check_repair_patterns(code, present, targets, ntargets, 1)) return t_status;
+    return guarded([&] {
+        if (repair_rows(code, present, targets, ntargets, rows, nullptr)) return t_status;
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API int fec_repair_batch(const fec_t* code, const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                             gf* dst, size_t dst_block_stride, size_t dst_stripe_stride, const unsigned* present,
+                             const unsigned* targets, size_t ntargets, size_t npatterns, const unsigned* pattern_of,
+                             size_t sz, size_t nstripes, void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!src || !dst) return set_status(FEC_EINVAL, "NULL buffer");
+    if (!present) return set_status(FEC_EINVAL, "present is NULL");
+    if (!targets) return set_status(FEC_EINVAL, "targets is NULL");
+    if (ntargets == 0 || ntargets > kRepairMaxRows)
+        return set_status(FEC_EINVAL, "ntargets is %zu: a call takes between 1 and %u targets per stripe", ntargets,
+                          unsigned(kRepairMaxRows));
+    if (npatterns == 0 && nstripes > 0)
+        return set_status(FEC_EINVAL, "npatterns is 0: stripe 0 of %zu has no pattern", nstripes);
+    if (npatterns > kMixedMaxPatterns)
+        return set_status(FEC_EINVAL, "%zu patterns: a call takes at most %u", npatterns, unsigned(kMixedMaxPatterns));
+    if (!pattern_of && npatterns != 1)
+        return set_status(FEC_EINVAL, "pattern_of is NULL with %zu patterns: without ids every stripe uses pattern 0, "
+                                      "so npatterns must be 1", npatterns);
+    if (check_repair_patterns(code, present, targets, ntargets, npatterns)) return t_status;
+    // ids in host memory are checked here; ids in device memory cannot be (the
+    // kernel leaves a stripe with an id >= npatterns unwritten)
+    const int ngpu = gpu_available();
+    const int idev = ngpu && pattern_of ? pointer_device(pattern_of) : -1;
+    if (pattern_of && idev < 0)
+        for (size_t s = 0; s < nstripes; ++s)
+            if (pattern_of[s] >= npatterns)
+                return set_status(FEC_EINVAL, "stripe %zu: pattern id %u out of range (npatterns = %zu)", s,
+                                  pattern_of[s], npatterns);
+    if (!ngpu) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (sz == 0 || nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_repair(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,
+                          present, targets, ntargets, npatterns, pattern_of, idev, sz, nstripes, stream, flags);
     });
 }
 

@@ -26,6 +26,9 @@
 //                       with the stored check blocks and only mismatch bits are
 //                       OR-ed out (fec_verify_batch); rows_differ compares rows
 //                       another kernel computed, for the shapes past k = 4.
+//   matrepair_mixed<K, R> matapply_mixed with R rows per pattern instead of K, each
+//                       row stored only where its pattern's live-row mask says
+//                       so (fec_repair_batch).
 //   matapply_lds        any k <= 32, r <= 48 (longer codes are split by the
 //                       caller): each workgroup expands its coefficients into
 //                       LDS tables from a compile-time bank of all 256 values;
@@ -998,6 +1001,118 @@ __global__ __launch_bounds__(kBlock) void matverify_reg(const VerifyJob<K, R> jo
             if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << r;
         }
         if (mask != 0u && lane == 0u) mismatch_or(job.mismatch + size_t(s) * job.words, job.bit0, mask);
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// matrepair_mixed<K, R>: a batched repair whose stripes each have their own
+// pattern (fec_repair_batch), k <= 4 and up to 8 output rows per launch.  It is
+// matapply_mixed<K> with R rows instead of K: the same walk (a wave's 64 units
+// lie in ONE stripe), the stripe's id and its record address wave-uniform,
+// formed through readfirstlane and read through constant-address-space
+// pointers, so ids, mask and tables are scalar loads and v_perm takes the
+// tables as SGPR pairs.
+//
+// A pattern's record in device memory holds the tables of ALL its target rows
+// (a call with more than 8 targets is several launches over one upload), the
+// Tab layout row-major, then one dword live-row mask: bit i is set when target
+// i is a block to rebuild.  Records are padded to 16 bytes.  A launch takes
+// rows [bit0, bit0 + R): tab_off is its first row's dword offset in a record.
+// A row whose mask bit is clear is skipped by a scalar branch: no table load,
+// no arithmetic and no store, so none of its bytes is touched.  An id >=
+// npatterns reads no record and leaves its stripe unwritten.  Each row's
+// tables (and, for the larger shapes, its output pointer) are read where they
+// are used, as in matapply_mixed<4> and matverify_reg.
+// ---------------------------------------------------------------------------
+template <int K, int R>
+struct alignas(16) RepairJob {
+    uint64_t sz, in_sstride, out_sstride;
+    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
+    uint32_t wps;            // waves per stripe
+    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    uint32_t npatterns;
+    uint32_t rec_dwords;     // dwords per pattern record
+    uint32_t tab_off;        // dword offset in a record of this launch's first row
+    uint32_t mask_off;       // dword offset in a record of the live-row mask
+    uint32_t bit0;           // mask bit of this launch's first row
+    const uint32_t* records;  // npatterns x rec_dwords
+    const uint32_t* ids;      // nstripes pattern ids
+    const uint8_t* in[K];
+    uint8_t* out[R];
+};
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matrepair_mixed(const RepairJob<K, R> job) {
+    constexpr bool AL = reg_argload(K, R);  // each row's tables are read where they are used
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    const CU32 ids = (CU32)job.ids;
+    while (s < job.nstripes) {
+        const uint32_t c = w * 64u + lane;
+        const bool live = c < job.cps;
+        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+        u32x4 x[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+        if (live) {
+            const uint64_t ib = s * job.in_sstride + sp.off;
+            if (sp.full) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load16(job.in[j] + ib);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load_tail(job.in[j] + ib, sp.nb);
+            }
+        }
+        const uint32_t id = __builtin_amdgcn_readfirstlane(ids[s]);
+        if (id < job.npatterns) {
+            const CU32 rp = (CU32)job.records + size_t(id) * job.rec_dwords;
+            const uint32_t mask = __builtin_amdgcn_readfirstlane(rp[job.mask_off]) >> job.bit0;
+            CU32 tp = rp + job.tab_off;
+            Sel sel[4][K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                sel[0][j] = selectors(x[j].x);
+                sel[1][j] = selectors(x[j].y);
+                sel[2][j] = selectors(x[j].z);
+                sel[3][j] = selectors(x[j].w);
+            }
+            const uint64_t ob = s * job.out_sstride + sp.off;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if ((mask >> r) & 1u) {  // wave-uniform: a scalar branch
+                    if constexpr (AL) asm volatile("" : "+s"(tp));
+                    Tab t[K];
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        const uint32_t i = (r * K + j) * 5;
+                        t[j] = Tab{tp[i], tp[i + 1], tp[i + 2], tp[i + 3], tp[i + 4]};
+                    }
+                    const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]),
+                                  gf_dot<K>(t, sel[3])};
+                    uint8_t* out;
+                    if constexpr (AL)
+                        out = kernarg_job<RepairJob<K, R>>()->out[r];
+                    else
+                        out = job.out[r];
+                    if (live) {
+                        if (sp.full)
+                            store16_pol<0>(out + ob, y);
+                        else
+                            store_tail(out + ob, y, sp.nb);
+                    }
+                }
+            }
+        }
         w += job.gs_w;
         s += job.gs_s;
         if (w >= job.wps) {
@@ -3722,7 +3837,119 @@ const std::array<VerifyLaunch, kRegR + 1> g_verify_launch[kRegK + 1] = {
     {}, verify_row<1>(std::make_integer_sequence<int, kRegR>()), verify_row<2>(std::make_integer_sequence<int, kRegR>()),
     verify_row<3>(std::make_integer_sequence<int, kRegR>()), verify_row<4>(std::make_integer_sequence<int, kRegR>())};
 
+// ---- matrepair_mixed dispatch ------------------------------------------------------
+// One upload through a MixedRing slot (the records, then any host-side ids)
+// serves every row group of a call.
+struct RepairUpload {
+    const uint32_t* records;  // device
+    const uint32_t* ids;      // device
+    uint32_t rec_dwords, mask_off;
+};
+
+constexpr uint32_t repair_rec_dwords(uint32_t k, uint32_t t) { return (t * k * 5 + 1 + 3) / 4 * 4; }
+
+char g_repair_names[kRegK + 1][kRegR + 1][28];
+
+// Rows [g0, g0 + R) of every stripe, cut into launches as verify_pieces cuts them.
+template <int K, int R>
+hipError_t launch_repair_kr(const RepairSpec& p, const RepairUpload& u, uint32_t g0, hipStream_t stream) {
+    RepairJob<K, R> job;
+    job.in_sstride = p.in_sstride;
+    job.out_sstride = p.out_sstride;
+    job.npatterns = p.npatterns;
+    job.rec_dwords = u.rec_dwords;
+    job.tab_off = g0 * K * 5;
+    job.mask_off = u.mask_off;
+    job.bit0 = g0;
+    job.records = u.records;
+    const hipError_t e = verify_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const WaveWalk ww = wave_walk(len, ns);
+        job.sz = len;
+        job.nstripes = static_cast<uint32_t>(ns);
+        job.cps = ww.cps;
+        job.wps = ww.wps;
+        job.gs_w = ww.gs_w;
+        job.gs_s = ww.gs_s;
+        job.ids = u.ids + s0;
+        for (int j = 0; j < K; ++j) job.in[j] = p.in[j] + b0 + s0 * p.in_sstride;
+        for (int i = 0; i < R; ++i) job.out[i] = p.out[g0 + i] + b0 + s0 * p.out_sstride;
+        return launch_job(reinterpret_cast<const void*>(matrepair_mixed<K, R>), ww.grid, kBlock, 0, stream, job);
+    });
+    if (e == hipSuccess) t_last_kernel = g_repair_names[K][R];
+    return e;
+}
+
+typedef hipError_t (*RepairLaunch)(const RepairSpec&, const RepairUpload&, uint32_t, hipStream_t);
+
+template <int K, int... R>
+constexpr std::array<RepairLaunch, kRegR + 1> repair_row(std::integer_sequence<int, R...>) {
+    return {{nullptr, launch_repair_kr<K, R + 1>...}};
+}
+
+const std::array<RepairLaunch, kRegR + 1> g_repair_launch[kRegK + 1] = {
+    {}, repair_row<1>(std::make_integer_sequence<int, kRegR>()), repair_row<2>(std::make_integer_sequence<int, kRegR>()),
+    repair_row<3>(std::make_integer_sequence<int, kRegR>()), repair_row<4>(std::make_integer_sequence<int, kRegR>())};
+
+hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
+    const uint32_t k = p.k, t = p.t;
+    uint32_t any = 0;
+    for (size_t q = 0; q < p.npatterns; ++q) any |= p.masks[q];
+    if (t < 32) any &= (1u << t) - 1u;
+    if (!any) return hipSuccess;  // nothing to store: no upload, no launch
+    RepairUpload u;
+    u.rec_dwords = repair_rec_dwords(k, t);
+    u.mask_off = t * k * 5;
+    const size_t tab_bytes = (size_t(p.npatterns) * u.rec_dwords * 4 + 255) / 256 * 256;
+    const size_t ids_bytes = p.ids_host ? size_t(p.nstripes) * 4 : 0;
+    MixedRing::Slot* slot = nullptr;
+    hipError_t e = mixed_slot(tab_bytes + ids_bytes, &slot);
+    if (e != hipSuccess) return e;
+    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
+    for (size_t q = 0; q < p.npatterns; ++q) {
+        uint32_t* rec = ht + q * u.rec_dwords;
+        for (uint32_t i = 0; i < t * k; ++i)
+            std::memcpy(rec + i * 5, &kHostBank.w[uint32_t(p.rows[q * t * k + i]) * 8], 5 * sizeof(uint32_t));
+        rec[u.mask_off] = p.masks[q];
+        for (uint32_t i = u.mask_off + 1; i < u.rec_dwords; ++i) rec[i] = 0;
+    }
+    if (ids_bytes) std::memcpy(slot->host + tab_bytes, p.ids_host, ids_bytes);
+    if ((e = hipMemcpyAsync(slot->dev, slot->host, tab_bytes + ids_bytes, hipMemcpyHostToDevice, stream)) !=
+        hipSuccess)
+        return e;
+    u.records = reinterpret_cast<const uint32_t*>(slot->dev);
+    u.ids = p.ids_host ? reinterpret_cast<const uint32_t*>(slot->dev + tab_bytes) : p.ids_dev;
+    for (uint32_t g0 = 0; g0 < t && e == hipSuccess; g0 += kRegR) {
+        const uint32_t rg = std::min<uint32_t>(kRegR, t - g0);
+        if (!((any >> g0) & ((1u << rg) - 1u))) continue;  // rows no pattern stores
+        e = g_repair_launch[k][rg](p, u, g0, stream);
+    }
+    // the copy (and any launch made) reads the slot: it stays busy whatever happened
+    if (hipEventRecord(slot->ev, stream) == hipSuccess)
+        slot->busy = true;
+    else
+        (void)hipStreamSynchronize(stream);
+    return e;
+}
+
 }  // namespace
+
+hipError_t launch_repair(const RepairSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    static std::once_flag names_once;
+    std::call_once(names_once, [] {
+        for (int k = 1; k <= kRegK; ++k)
+            for (int r = 1; r <= kRegR; ++r)
+                snprintf(g_repair_names[k][r], sizeof g_repair_names[k][r], "matrepair_mixed<%d,%d>", k, r);
+    });
+    if (p.k < 1 || p.k > kMixedMaxK || p.t < 1 || p.t > kRepairMaxRows || p.npatterns < 1 ||
+        p.npatterns > kMixedMaxPatterns || !p.rows || !p.masks || (!p.ids_host && !p.ids_dev) || p.sz == 0 ||
+        p.nstripes == 0 || p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
+    t_signal_used = false;
+    return launch_repair_all(p, stream);
+}
 
 hipError_t launch_verify(const VerifySpec& v, hipStream_t stream) {
     std::call_once(g_dispatch_once, init_dispatch);

@@ -90,6 +90,28 @@ struct MixedSpec {
 };
 hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream);
 
+// A batched repair with a pattern per stripe (matrepair_mixed<K, R>, k <= 4):
+// k inputs and t output rows per stripe, stripe s applying the t x k matrix
+// rows + ids[s] * t * k and storing row i only where bit i of masks[ids[s]] is
+// set; a row whose bit is clear is not touched.  More than 8 rows run as
+// launches of at most 8 over one upload; a group of rows no pattern stores is
+// skipped, and a call that stores nothing launches nothing.  Ids, staging and
+// graph capture as launch_mixed.
+constexpr uint32_t kRepairMaxRows = 32;
+struct RepairSpec {
+    uint32_t k, t;
+    const uint8_t* rows;    // npatterns x t x k coefficients (host memory)
+    const uint32_t* masks;  // npatterns live-row masks (host memory)
+    uint32_t npatterns;
+    const uint32_t* ids_host;
+    const uint32_t* ids_dev;
+    const uint8_t* const* in;  // k input block bases (stripe 0), kernel-visible addresses
+    uint8_t* const* out;       // t output row bases (stripe 0)
+    uint64_t sz, nstripes;
+    uint64_t in_sstride, out_sstride;
+};
+hipError_t launch_repair(const RepairSpec& p, hipStream_t stream);
+
 // Parity verification (fec_verify_batch): nothing is written but mismatch bits.
 // Bit (bit0 + i) % 32 of mismatch[s * words + (bit0 + i) / 32] is OR-ed in
 // (relaxed, device scope) when row i of stripe s differs in at least one byte;
