@@ -213,8 +213,7 @@ int fec_mixed_decode_rows(const fec_t* code, const unsigned* pattern, gf* rows);
  *
  * Reading the mask: the code is MDS, so P has no zero entry.  A corrupt check
  * block sets exactly its own bit; ONE corrupt basis block sets all c bits of
- * its stripe.  (Telling which block is bad when all bits are set takes another
- * call with another basis.)
+ * its stripe; fec_locate_batch below names that block.
  *
  * src: device memory on one device, or page-locked host memory read in place;
  * pageable host memory returns FEC_EINVAL (this call does not stage).  A
@@ -248,6 +247,78 @@ int fec_verify_batch(const fec_t* code,
  * block_nums (row i yields the block of slot k + i from the k basis slots),
  * row-major into rows[c*k].  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
 int fec_verify_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
+
+/* Batched single-block error location: which block of an inconsistent stripe
+ * is the corrupt one?  The step between fec_verify_batch and fec_repair_batch:
+ * scrub, locate and repair are three calls with no host round trip.
+ *
+ * Arguments as in fec_verify_batch: nb = k + c blocks per stripe, slot j holds
+ * block block_nums[j], the first k slots the basis, the other c the checks, and
+ * P = E[checks] . inverse(E[basis]) (fec_verify_rows; no zero entry).  At every
+ * byte position the syndromes are
+ *     s_i = stored check i ^ sum_j P[i][j] . basis_j,   i = 0..c-1,
+ * the words fec_verify_batch reduces to one bit each.  For c >= 2 let
+ * Q[i][j] = P[i][j] / P[0][j], i = 1..c-1 (fec_locate_rows).  Per stripe, over
+ * all sz bytes:
+ *   mismatch bit i is set iff s_i != 0 somewhere (exactly the verify bits);
+ *   excluded bit j (j < k) is set iff s_i != Q[i][j] . s_0 somewhere, for some
+ *     i >= 1: the hypothesis "only basis slot j is corrupt" is refuted.
+ * culprit[s], one unsigned per stripe, is
+ *   1. FEC_LOCATE_CLEAN when no mismatch bit is set;
+ *   2. otherwise FEC_LOCATE_UNKNOWN when c == 1 (any of the k + 1 blocks could
+ *      be the bad one);
+ *   3. otherwise k + i0 when exactly one mismatch bit i0 is set: a check block;
+ *   4. otherwise j when exactly one basis slot j is not excluded;
+ *   5. otherwise FEC_LOCATE_MANY.
+ * A value below nb is a SLOT index into block_nums, not a block number.
+ *
+ * What this guarantees (the held blocks form an MDS code, so any c columns of
+ * [P | I] are independent).  With c >= 2 a stripe with exactly one corrupt
+ * block gets that block's slot, whatever the bytes.  Two corrupt blocks at
+ * different byte positions always give MANY; two to c - 1 corrupt blocks at the
+ * same byte position give MANY (this needs c >= 3).  From c blocks corrupt at
+ * one position on the verdict can be wrong, as with any decoder past its
+ * distance: with c = 2 that is already two blocks.  At most one basis slot can
+ * survive in rule 4.
+ *
+ * src as in fec_verify_batch: device memory on one device, or page-locked host
+ * memory read in place; pageable host memory returns FEC_EINVAL.  A block-major
+ * layout is walked stripe by stripe.  culprit in device memory is used in place
+ * (on the blocks' device, else FEC_EINVAL) and FEC_FLAG_ASYNC is honoured;
+ * culprit in host memory is gathered in device memory the library owns and
+ * copied back, and the call is then synchronous whatever the flags.
+ * FEC_FLAG_LIBRARY_STREAM as elsewhere; FEC_FLAG_ROW_PADDING is accepted and
+ * ignored.  While the stream is being captured into a graph the call returns
+ * FEC_EINVAL.  src is never written, and nothing outside the nstripes verdict
+ * words is written in caller memory: the per-stripe bits are kept in device
+ * memory the library owns (the kernels' device-scope atomics aim only there).
+ *
+ * Checked before any GPU work, in this order, each FEC_EINVAL with a message:
+ * invalid fec_t; NULL src, block_nums or culprit; nb <= k ("nothing to
+ * check"); nb > n; a block number >= n; a duplicate.  Then FEC_ENODEV when no
+ * GPU is visible.  nstripes == 0 returns FEC_OK; sz == 0 returns FEC_OK with
+ * every verdict FEC_LOCATE_CLEAN.
+ *
+ * k <= 4 with 2 <= c <= 8 runs on matlocate_reg<k, c>, one launch:
+ * matverify_reg's walk with the syndromes kept in registers, the k hypotheses
+ * tested only in waves that saw a nonzero syndrome, so clean data costs what
+ * fec_verify_batch costs.  c == 1 runs the verify kernels.  Other codes compute
+ * the expected rows into library scratch as fec_verify_batch does and compare
+ * with rows_locate.  locate_finish then writes the verdicts;
+ * fec_last_kernel_name() names the kernel that read the blocks. */
+#define FEC_LOCATE_CLEAN   0xFFFFFFFFu
+#define FEC_LOCATE_MANY    0xFFFFFFFEu
+#define FEC_LOCATE_UNKNOWN 0xFFFFFFFDu
+int fec_locate_batch(const fec_t* code,
+                     const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                     const unsigned* block_nums, size_t num_block_nums,
+                     size_t sz, size_t nstripes,
+                     unsigned* culprit, void* stream, unsigned flags);
+
+/* Host only, no GPU: the (c-1) x k matrix Q fec_locate_batch tests with,
+ * row-major into rows[(c-1)*k]; c == 1 writes nothing.
+ * FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
+int fec_locate_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
 
 /* Batched repair: rebuild any lost blocks of every stripe, primaries and parity
  * alike, from the k blocks the stripe still holds, in one call (the step after

@@ -23,7 +23,11 @@ from ._fec import Error, device_count, test_from_agl, version
 __version__ = "0.1.0"
 
 __all__ = ["Encoder", "Decoder", "Error", "easyfec", "filefec", "cmdline_zfec", "cmdline_zunfec", "test_from_agl",
-           "device_count", "version", "reuse_host_memory"]
+           "device_count", "version", "reuse_host_memory", "LOCATE_CLEAN", "LOCATE_MANY", "LOCATE_UNKNOWN"]
+
+# Decoder.locate_batch verdicts that are not a slot: FEC_LOCATE_CLEAN / _MANY /
+# _UNKNOWN (include/zfec_hip.h) read as int32
+LOCATE_CLEAN, LOCATE_MANY, LOCATE_UNKNOWN = -1, -2, -3
 
 
 def _is_device_tensor(x):
@@ -598,10 +602,52 @@ class Decoder(_fec.Decoder):
         (numpy) blocks are not staged by this call."""
         import torch
 
+        nums, nb, ns, sz, sbs, sss, ptr = self._scrub_args(blocks, blocknums, "verify_batch")
+        c = nb - self.k
+        words = (c + 31) // 32
+        if not (ns and sz):
+            return torch.zeros((ns, c), dtype=torch.bool, device=blocks.device)
+        mask = torch.empty((ns, words), dtype=torch.int32, device=blocks.device)  # the library clears it
+        stream, flags = _batch_call_args(blocks)
+        with _as_error():
+            _capi_code(self).verify_batch(ptr, sbs, sss, nums, sz, ns, mask.data_ptr(), stream=stream, flags=flags)
+        shifts = torch.arange(32, dtype=torch.int32, device=blocks.device)
+        bits = (mask.unsqueeze(-1) >> shifts) & 1
+        return bits.reshape(ns, words * 32)[:, :c].ne(0)
+
+    def locate_batch(self, blocks, blocknums):
+        """Name the corrupt block of every stripe (fec_locate_batch): the step
+        between verify_batch and repair_batch.
+
+        blocks and blocknums as in verify_batch, with the same preconditions.
+        Returns a torch.int32 tensor [nstripes] on the blocks' device: a value
+        >= 0 is the SLOT (an index into blocknums, not a block number) of the
+        stripe's one corrupt block; LOCATE_CLEAN (-1) says the stripe is
+        consistent, LOCATE_MANY (-2) that more than one block is corrupt,
+        LOCATE_UNKNOWN (-3) that a single check (nb == k + 1) cannot tell
+        which block it is.  With two or more checks a stripe with exactly one
+        corrupt block always gets that block's slot.  The work is enqueued on
+        the current stream, without a host sync."""
+        import torch
+
+        nums, nb, ns, sz, sbs, sss, ptr = self._scrub_args(blocks, blocknums, "locate_batch")
+        if not (ns and sz):
+            return torch.full((ns,), LOCATE_CLEAN, dtype=torch.int32, device=blocks.device)
+        out = torch.empty((ns,), dtype=torch.int32, device=blocks.device)
+        stream, flags = _batch_call_args(blocks)
+        with _as_error():
+            _capi_code(self).locate_batch(ptr, sbs, sss, nums, sz, ns, out.data_ptr(), stream=stream, flags=flags)
+        return out
+
+    def _scrub_args(self, blocks, blocknums, what):
+        """The preconditions verify_batch and locate_batch share; returns
+        (nums, nb, nstripes, sz, block stride, stripe stride, address)."""
+        import torch
+
         k, m = self.k, self.m
         if _is_host_array(blocks):
-            raise Error("Precondition violation: verify_batch takes a device tensor; host (numpy) blocks are not "
-                        "staged by this call")
+            raise Error("Precondition violation: %s takes a device tensor; host (numpy) blocks are not "
+                        "staged by this call" % what)
         try:
             nums = list(blocknums)
         except TypeError:
@@ -627,17 +673,7 @@ class Decoder(_fec.Decoder):
             raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
                         "not a host tensor" % nb)
         ns, sz, sbs, sss, ptr = _batch_view(blocks, nb, "blocks")
-        c = nb - k
-        words = (c + 31) // 32
-        if not (ns and sz):
-            return torch.zeros((ns, c), dtype=torch.bool, device=blocks.device)
-        mask = torch.empty((ns, words), dtype=torch.int32, device=blocks.device)  # the library clears it
-        stream, flags = _batch_call_args(blocks)
-        with _as_error():
-            _capi_code(self).verify_batch(ptr, sbs, sss, nums, sz, ns, mask.data_ptr(), stream=stream, flags=flags)
-        shifts = torch.arange(32, dtype=torch.int32, device=blocks.device)
-        bits = (mask.unsqueeze(-1) >> shifts) & 1
-        return bits.reshape(ns, words * 32)[:, :c].ne(0)
+        return nums, nb, ns, sz, sbs, sss, ptr
 
     def _check_blocknums(self, blocknums):
         """Validated list of k block numbers (the reference's checks,

@@ -63,7 +63,10 @@ SYMBOLS = [
     ("fec_verify_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
     ("fec_repair_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _UP, _UP, _SZ, _SZ, _P, _SZ, _SZ, _P, _U]),
     ("fec_repair_rows", ctypes.c_int, [_P, _UP, _UP, _SZ, _P]),
+    ("fec_locate_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
+    ("fec_locate_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
 ]
+FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_REPAIR_NONE = 0xFFFFFFFF  # a target slot its pattern does not use
 
 JIT_OFF, JIT_AUTO, JIT_FORCE = 0, 1, 2
@@ -300,6 +303,16 @@ class Code(object):
         if st:
             check(st)
 
+    def locate_batch(self, src, sbs, sss, block_nums, sz, nstripes, culprit_ptr, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_locate_batch: the arguments of verify_batch; `culprit_ptr` is the
+        address of nstripes uint32 words in device or host memory, each set to
+        the corrupt block's slot index or to FEC_LOCATE_CLEAN / _MANY /
+        _UNKNOWN."""
+        st = lib().fec_locate_batch(self.ptr, src, sbs, sss, _nums(block_nums), len(block_nums), sz, nstripes,
+                                    culprit_ptr or None, stream or None, flags)
+        if st:
+            check(st)
+
     def encode_batch_multi(self, src, sbs, sss, dst, dbs, dss, block_nums, sz, nstripes, devices, flags=0):
         """fec_encode_batch_multi: the stripes split over `devices` (host memory)."""
         devs = (ctypes.c_int * max(1, len(devices)))(*devices)
@@ -341,6 +354,17 @@ def verify_rows(code, block_nums):
     rows = (ctypes.c_ubyte * max(1, (len(nums) - code.k) * code.k))()
     check(lib().fec_verify_rows(code.ptr, uint_array(nums), len(nums), ctypes.cast(rows, _P)))
     return bytes(rows)
+
+
+def locate_rows(code, block_nums):
+    """fec_locate_rows: the (c-1)*k bytes (row-major, c = len(block_nums) - k)
+    of the matrix Q fec_locate_batch tests with, Q[i][j] = P[i][j] / P[0][j]
+    for i = 1..c-1; empty for c == 1.  Host only."""
+    nums = list(block_nums)
+    n = max(0, (len(nums) - code.k - 1) * code.k)
+    rows = (ctypes.c_ubyte * max(1, n))()
+    check(lib().fec_locate_rows(code.ptr, uint_array(nums), len(nums), ctypes.cast(rows, _P)))
+    return bytes(rows)[:n]
 
 
 def repair_rows(code, present, targets):

@@ -1624,9 +1624,16 @@ int verify_reg_path(const uint8_t* P, unsigned k, unsigned c, const gf* src, siz
 // rows.  The scratch holds c rows of `pitch` bytes per stripe and at most
 // Config::verify_scratch bytes: a batch goes in runs of stripes that fit, a
 // stripe larger than that in byte ranges.  The bits OR together, so the
-// cutting is invisible.
+// cutting is invisible.  With `loc` (fec_locate_batch) rows_locate takes the
+// place of rows_differ: it also reads row 0's pair and ORs excluded bits from
+// bit loc->xbit on, against the Q tables at loc->qtab.
+struct LocateRows {
+    const uint32_t* qtab;  // device memory
+    unsigned xbit;
+};
 int verify_scratch_path(DevCtx& d, const uint8_t* P, unsigned k, unsigned c, const gf* src, size_t sbs, size_t sss,
-                        size_t sz, size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st) {
+                        size_t sz, size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st,
+                        const LocateRows* loc = nullptr) {
     const size_t cap = config().verify_scratch;
     size_t len = sz, run = 1;
     if (size_t(c) * align_up(sz, 128) <= cap)
@@ -1662,6 +1669,12 @@ int verify_scratch_path(DevCtx& d, const uint8_t* P, unsigned k, unsigned c, con
                 f.words = words;
                 f.bit0 = g0;
                 ++t_launches;
+                if (loc) {
+                    const hipError_t e =
+                        launch_rows_locate(f, out[0], base + size_t(k) * sbs, k, loc->xbit, loc->qtab, st);
+                    if (e != hipSuccess) return hip_fail(e, "launch_rows_locate");
+                    continue;
+                }
                 const hipError_t e = launch_rows_differ(f, st);
                 if (e != hipSuccess) return hip_fail(e, "launch_rows_differ");
             }
@@ -1759,6 +1772,155 @@ FEC_API int fec_verify_batch(const fec_t* code, const gf* src, size_t src_block_
     return guarded([&] {
         return run_verify(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
                           mismatch, stream, flags);
+    });
+}
+
+// ---- batched single-block error location ---------------------------------------------------
+namespace {
+// Q[i][j] = P[i][j] / P[0][j] for i = 1..c-1, (c-1) x k row-major: the ratios a
+// single corrupt basis slot j imposes on the syndromes.  P has no zero entry
+// (the held blocks form an MDS code).
+void locate_rows(const uint8_t* P, unsigned k, unsigned c, uint8_t* Q) {
+    const Field& f = field();
+    for (unsigned i = 1; i < c; ++i)
+        for (unsigned j = 0; j < k; ++j) Q[size_t(i - 1) * k + j] = f.mul[P[size_t(i) * k + j]][f.inv[P[j]]];
+}
+
+// The working words of a call (W = ceil(c/32) + ceil(k/32) per stripe, mismatch
+// bits from bit 0, excluded bits from bit 32*ceil(c/32)) live in the thread's
+// vmask buffer, under run_verify's ev_verify ordering; a host-side culprit is
+// gathered behind them.
+int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const unsigned* nums, size_t nb, size_t sz,
+               size_t nstripes, unsigned* culprit, void* stream, unsigned flags) {
+    const unsigned k = code->k, c = static_cast<unsigned>(nb - k), cw = (c + 31) / 32, words = cw + (k + 31) / 32;
+    const unsigned xbit = 32 * cw;
+    if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
+    const size_t work_bytes = nstripes * words * sizeof(uint32_t), out_bytes = nstripes * sizeof(uint32_t);
+    const int cdev = pointer_device(culprit);
+    int dev = -1;
+    const gf* zsrc = src;
+    if (sz) {
+        // device memory on one device, or page-locked host memory (read in place)
+        const size_t extent = (nstripes - 1) * sss + (nb - 1) * sbs + sz;
+        dev = pointer_device(src);
+        if (dev < 0 && !(zsrc = mapped_block(src, extent)))
+            return set_status(FEC_EINVAL, "fec_locate_batch takes device or page-locked host memory: src is pageable "
+                                          "host memory, which this call does not stage");
+        if (dev >= 0 && cdev >= 0 && cdev != dev)
+            return set_status(FEC_EINVAL, "culprit lives on device %d, the blocks on device %d", cdev, dev);
+    }
+    if (dev < 0) dev = cdev;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
+    DeviceGuard guard(dev);
+    DevCtx* d = nullptr;
+    if (dev_ctx(dev, &d)) return t_status;
+    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
+    if (stream_capturing(st))
+        return set_status(FEC_EINVAL, "fec_locate_batch: the stream is being captured into a graph (the call uses "
+                                      "memory the library owns and reuses)");
+    hipError_t e;
+    if (!d->ev_verify && (e = hipEventCreateWithFlags(&d->ev_verify, hipEventDisableTiming)) != hipSuccess)
+        return hip_fail(e, "hipEventCreateWithFlags");
+    // the thread's working words (and scratch): wait (on the GPU) for the call that used them last
+    if (d->verify_busy && (e = hipStreamWaitEvent(st, d->ev_verify, 0)) != hipSuccess)
+        return hip_fail(e, "hipStreamWaitEvent");
+    if (ensure_verify_buf(*d, d->vmask, d->vmask_cap, work_bytes + (cdev < 0 ? out_bytes : 0))) return t_status;
+    uint32_t* const bits = static_cast<uint32_t*>(d->vmask);
+    uint32_t* const out = cdev < 0 ? bits + nstripes * words : culprit;
+    if ((e = hipMemsetAsync(bits, 0, work_bytes, st)) != hipSuccess)
+        return hip_fail(e, "hipMemsetAsync (working words)");
+    int rc = FEC_OK;
+    if (sz) {
+        thread_local std::vector<uint8_t> P, Q;
+        P.resize(size_t(c) * k);
+        Q.resize(size_t(c - 1) * k);
+        rc = verify_rows(code, nums, nb, P.data());
+        if (!rc && c == 1) {
+            // one check cannot tell: the verify kernels' bit, then UNKNOWN
+            rc = k <= 4 ? verify_reg_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, bits, words, st)
+                        : verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, bits, words, st);
+        } else if (!rc && k <= 4 && c <= 8) {
+            locate_rows(P.data(), k, c, Q.data());
+            const uint8_t* in[4];
+            const uint8_t* chk[8];
+            for (unsigned j = 0; j < k; ++j) in[j] = zsrc + j * sbs;
+            for (unsigned i = 0; i < c; ++i) chk[i] = zsrc + size_t(k + i) * sbs;
+            VerifySpec v;
+            v.coef = P.data();
+            v.coef_stride = k;
+            v.k = k;
+            v.r = c;
+            v.in = in;
+            v.chk = chk;
+            v.sz = sz;
+            v.nstripes = nstripes;
+            v.sstride = sss;
+            v.mismatch = bits;
+            v.words = words;
+            v.bit0 = 0;
+            ++t_launches;
+            if ((e = launch_locate(v, Q.data(), xbit, st)) != hipSuccess) rc = hip_fail(e, "launch_locate");
+        } else if (!rc) {
+            locate_rows(P.data(), k, c, Q.data());
+            LocateTables tabs;
+            if ((e = locate_tables_upload(Q.data(), k, c, st, &tabs)) != hipSuccess) {
+                rc = hip_fail(e, "locate_tables_upload");
+            } else {
+                const LocateRows loc{tabs.dev, xbit};
+                rc = verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, bits, words, st, &loc);
+                locate_tables_release(tabs, st);
+            }
+        }
+    }
+    if (!rc) {
+        // the block-reading kernel stays fec_last_kernel_name()'s answer
+        ++t_launches;
+        if ((e = launch_locate_finish(bits, words, k, c, nstripes, out, st)) != hipSuccess)
+            rc = hip_fail(e, "launch_locate_finish");
+    }
+    if (!rc && cdev < 0 && (e = hipMemcpyAsync(culprit, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpyAsync D2H (culprit)");
+    // whatever was enqueued uses the shared buffers: they stay busy whatever happened
+    if (hipEventRecord(d->ev_verify, st) == hipSuccess)
+        d->verify_busy = true;
+    else
+        (void)hipStreamSynchronize(st);
+    if (rc) return rc;
+    if ((cdev < 0 || !(flags & FEC_FLAG_ASYNC)) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_locate_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
+    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
+    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+    return guarded([&] {
+        const unsigned k = code->k, c = static_cast<unsigned>(num_block_nums - k);
+        thread_local std::vector<uint8_t> P;
+        P.resize(size_t(c) * k);
+        if (verify_rows(code, block_nums, num_block_nums, P.data())) return t_status;
+        locate_rows(P.data(), k, c, rows);
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API int fec_locate_batch(const fec_t* code, const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                             const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
+                             unsigned* culprit, void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!src) return set_status(FEC_EINVAL, "NULL buffer: src");
+    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
+    if (!culprit) return set_status(FEC_EINVAL, "culprit is NULL");
+    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+    if (!gpu_available()) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_locate(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
+                          culprit, stream, flags);
     });
 }
 

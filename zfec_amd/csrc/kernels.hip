@@ -26,6 +26,11 @@
 //                       with the stored check blocks and only mismatch bits are
 //                       OR-ed out (fec_verify_batch); rows_differ compares rows
 //                       another kernel computed, for the shapes past k = 4.
+//   matlocate_reg<K, R> matverify_reg with the R syndromes kept in registers: waves
+//                       that saw a nonzero one test which single basis block
+//                       explains them (fec_locate_batch); rows_locate does the
+//                       same past k = 4 or 8 checks, locate_finish turns each
+//                       stripe's bits into its verdict.
 //   matrepair_mixed<K, R> matapply_mixed with R rows per pattern instead of K, each
 //                       row stored only where its pattern's live-row mask says
 //                       so (fec_repair_batch).
@@ -1183,6 +1188,306 @@ __global__ __launch_bounds__(kBlock) void rows_differ(const DifferJob job) {
             ++s;
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// matlocate_reg<K, R>: single-block error location (fec_locate_batch), k <= 4
+// and 2 <= R <= 8 checks, all in one launch.  It is matverify_reg<K, R> -- the
+// same walk, loads, zero-filled tail, dead lanes and overlapped last chunk --
+// except that computed ^ stored, the R syndromes of the unit (four words
+// each), stay in the registers that held the stored rows.  The ballots form
+// the wave-uniform mismatch mask as there.  Only under a scalar branch on
+// mask != 0 the K hypotheses "only basis slot j is corrupt" are tested: the
+// syndromes of such an error satisfy s_r = Q[r][j] . s_0 (Q[r][j] = P[r][j] /
+// P[0][j]) at every byte, so a lane where some s_r ^ Q[r][j] . s_0 is nonzero
+// refutes j, and one ballot per j gives the wave's excluded bits.  A wave whose
+// syndromes are all zero refutes nothing, so skipping it loses nothing.  The Q
+// tables sit behind the verify tables in the argument block and are read
+// through the kernel-argument pointer inside the branch only: the clean path
+// carries no SGPRs for them, performs no store and no atomic.  One lane then
+// ORs mismatch bits (from bit 0) and excluded bits (from bit xbit) into the
+// stripe's working words.
+// ---------------------------------------------------------------------------
+template <int K, int R>
+struct alignas(16) LocateJob {
+    uint64_t sz, sstride;
+    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
+    uint32_t wps;            // waves per stripe
+    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    uint32_t words;          // working words per stripe
+    uint32_t xbit;           // bit index of basis slot 0's excluded bit
+    uint32_t pad_;
+    uint32_t* bits;
+    const uint8_t* in[K];
+    const uint8_t* chk[R];
+    uint32_t tab[K * R * 5];         // the RegJob layout: row i, input j at (i*K + j)*5
+    uint32_t qtab[K * (R - 1) * 5];  // Q[r][j], r = 1..R-1, at ((r-1)*K + j)*5
+};
+
+// <1,8> and <3,3> sit at the SGPR limit as matverify_reg shapes (106 and 105)
+// and would spill with the dirty branch's registers on top: they too read
+// tables and pointers where they are used.
+constexpr bool locate_argload(int K, int R) { return reg_argload(K, R) || K * R * 5 + 2 * (K + R) >= 56; }
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matlocate_reg(const LocateJob<K, R> job) {
+    constexpr bool AL = locate_argload(K, R);  // each row's tables are read where they are used
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    while (s < job.nstripes) {
+        const uint32_t c = w * 64u + lane;
+        const bool live = c < job.cps;
+        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+        u32x4 x[K], y[R];
+#pragma unroll
+        for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < R; ++r) y[r] = u32x4{0u, 0u, 0u, 0u};
+        if (live) {
+            const uint64_t ib = s * job.sstride + sp.off;
+            const uint8_t* in[K];
+            const uint8_t* chk[R];
+            if constexpr (AL) {
+                const KPtr<LocateJob<K, R>> kj = kernarg_job<LocateJob<K, R>>();
+#pragma unroll
+                for (int j = 0; j < K; ++j) in[j] = kj->in[j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) chk[r] = kj->chk[r];
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) in[j] = job.in[j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) chk[r] = job.chk[r];
+            }
+            if (sp.full) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load16(in[j] + ib);
+#pragma unroll
+                for (int r = 0; r < R; ++r) y[r] = load16(chk[r] + ib);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = load_tail(in[j] + ib, sp.nb);
+#pragma unroll
+                for (int r = 0; r < R; ++r) y[r] = load_tail(chk[r] + ib, sp.nb);
+            }
+        }
+        Sel sel[4][K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            sel[0][j] = selectors(x[j].x);
+            sel[1][j] = selectors(x[j].y);
+            sel[2][j] = selectors(x[j].z);
+            sel[3][j] = selectors(x[j].w);
+        }
+        uint32_t mask = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            Tab t[K];
+            if constexpr (AL) {
+                const KPtr<LocateJob<K, R>> kj = kernarg_job<LocateJob<K, R>>();
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const uint32_t i = (r * K + j) * 5;
+                    t[j] = Tab{kj->tab[i], kj->tab[i + 1], kj->tab[i + 2], kj->tab[i + 3], kj->tab[i + 4]};
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const uint32_t* p = &job.tab[(r * K + j) * 5];
+                    t[j] = Tab{p[0], p[1], p[2], p[3], p[4]};
+                }
+            }
+            // the syndrome of row r replaces the stored row
+            y[r].x ^= gf_dot<K>(t, sel[0]);
+            y[r].y ^= gf_dot<K>(t, sel[1]);
+            y[r].z ^= gf_dot<K>(t, sel[2]);
+            y[r].w ^= gf_dot<K>(t, sel[3]);
+            const uint32_t d = y[r].x | y[r].y | y[r].z | y[r].w;
+            if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << r;
+        }
+        if (mask != 0u) {  // wave-uniform: a scalar branch, not taken on clean data
+            const Sel z[4][1] = {{selectors(y[0].x)}, {selectors(y[0].y)}, {selectors(y[0].z)}, {selectors(y[0].w)}};
+            uint32_t excl = 0;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                uint32_t d = 0;
+#pragma unroll
+                for (int r = 1; r < R; ++r) {
+                    const KPtr<LocateJob<K, R>> kj = kernarg_job<LocateJob<K, R>>();
+                    const uint32_t i = ((r - 1) * K + j) * 5;
+                    const Tab q[1] = {
+                        Tab{kj->qtab[i], kj->qtab[i + 1], kj->qtab[i + 2], kj->qtab[i + 3], kj->qtab[i + 4]}};
+                    d |= (y[r].x ^ gf_dot<1>(q, z[0])) | (y[r].y ^ gf_dot<1>(q, z[1])) |
+                         (y[r].z ^ gf_dot<1>(q, z[2])) | (y[r].w ^ gf_dot<1>(q, z[3]));
+                }
+                if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) excl |= 1u << j;
+            }
+            if (lane == 0u) {
+                uint32_t* const base = job.bits + size_t(s) * job.words;
+                mismatch_or(base, 0u, mask);
+                if (excl != 0u) mismatch_or(base, job.xbit, excl);
+            }
+        }
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// rows_locate: rows_differ's place in fec_locate_batch for the shapes
+// matlocate_reg does not take.  a holds the expected check rows (scratch), b
+// the stored ones; a launch takes rows [bit0, bit0 + r) of the c checks, r <=
+// kMaxOut, and always reads row 0's pair too, so every launch has s_0.  The
+// group's mismatch bits are OR-ed out as rows_differ does.  Only a wave that
+// saw a nonzero syndrome (s_0 or one of its rows) tests the k hypotheses
+// against its rows: the syndromes are re-read (from L2), Q[i][j]'s table comes
+// from device memory by wave-uniform scalar loads ((i-1)*k + j)*5 dwords into
+// qtab, written by a copy before the launch), and the excluded bits go out 32
+// basis slots at a time.  Dirty units are rare; their speed is not a goal.
+// ---------------------------------------------------------------------------
+struct alignas(16) LocateRowsJob {
+    uint64_t sz, a_sstride, b_sstride;
+    uint32_t nstripes, cps, wps, gs_w, gs_s;
+    uint32_t words, bit0, r;
+    uint32_t k, xbit, pad_;
+    uint32_t* bits;
+    const uint32_t* qtab;
+    const uint8_t* a0;  // row 0's pair
+    const uint8_t* b0;
+    const uint8_t* a[kMaxOut];
+    const uint8_t* b[kMaxOut];
+};
+
+__device__ __forceinline__ u32x4 load_unit(const uint8_t* p, bool live, const Span& sp) {
+    if (!live) return u32x4{0u, 0u, 0u, 0u};
+    return sp.full ? load16(p) : load_tail(p, sp.nb);
+}
+
+__global__ __launch_bounds__(kBlock) void rows_locate(const LocateRowsJob job) {
+    constexpr uint32_t G = 4;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    const CU32 qtab = (CU32)job.qtab;
+    while (s < job.nstripes) {
+        const uint32_t c = w * 64u + lane;
+        const bool live = c < job.cps;
+        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+        const uint64_t ao = s * job.a_sstride + sp.off, bo = s * job.b_sstride + sp.off;
+        uint32_t* const base = job.bits + size_t(s) * job.words;
+        // s_0: the first group has it as its row 0, a later group reads the pair again
+        u32x4 s0{0u, 0u, 0u, 0u};
+        bool dirty = false;
+        if (job.bit0 != 0u) {
+            s0 = load_unit(job.a0 + ao, live, sp) ^ load_unit(job.b0 + bo, live, sp);
+            dirty = __builtin_amdgcn_ballot_w64((s0.x | s0.y | s0.z | s0.w) != 0u) != 0ull;
+        }
+        for (uint32_t r0 = 0; r0 < job.r; r0 += G) {
+            const uint32_t n = job.r - r0 < G ? job.r - r0 : G;
+            u32x4 p[G], q[G];
+#pragma unroll
+            for (uint32_t i = 0; i < G; ++i) {
+                p[i] = q[i] = u32x4{0u, 0u, 0u, 0u};
+                if (i < n) {
+                    p[i] = load_unit(job.a[r0 + i] + ao, live, sp);
+                    q[i] = load_unit(job.b[r0 + i] + bo, live, sp);
+                }
+            }
+            if (r0 == 0u && job.bit0 == 0u) s0 = p[0] ^ q[0];
+            uint32_t mask = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < G; ++i) {
+                const u32x4 d = p[i] ^ q[i];
+                if (__builtin_amdgcn_ballot_w64((d.x | d.y | d.z | d.w) != 0u) != 0ull) mask |= 1u << i;
+            }
+            if (mask != 0u) {
+                dirty = true;
+                if (lane == 0u) mismatch_or(base, job.bit0 + r0, mask);
+            }
+        }
+        if (dirty) {  // wave-uniform
+            const Sel z[4][1] = {{selectors(s0.x)}, {selectors(s0.y)}, {selectors(s0.z)}, {selectors(s0.w)}};
+            for (uint32_t j0 = 0; j0 < job.k; j0 += 32u) {
+                const uint32_t nj = job.k - j0 < 32u ? job.k - j0 : 32u;
+                uint32_t excl = 0;
+                for (uint32_t i = 0; i < job.r; ++i) {
+                    const uint32_t gi = job.bit0 + i;
+                    if (gi == 0u) continue;  // s_0 against itself
+                    const u32x4 si = load_unit(job.a[i] + ao, live, sp) ^ load_unit(job.b[i] + bo, live, sp);
+                    const CU32 tp = qtab + (size_t(gi - 1u) * job.k + j0) * 5u;
+                    for (uint32_t jj = 0; jj < nj; ++jj) {
+                        const Tab t[1] = {Tab{tp[jj * 5u], tp[jj * 5u + 1u], tp[jj * 5u + 2u], tp[jj * 5u + 3u],
+                                              tp[jj * 5u + 4u]}};
+                        const uint32_t d = (si.x ^ gf_dot<1>(t, z[0])) | (si.y ^ gf_dot<1>(t, z[1])) |
+                                           (si.z ^ gf_dot<1>(t, z[2])) | (si.w ^ gf_dot<1>(t, z[3]));
+                        if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) excl |= 1u << jj;
+                    }
+                }
+                if (excl != 0u && lane == 0u) mismatch_or(base, job.xbit + j0, excl);
+            }
+        }
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// locate_finish: one lane per stripe turns the stripe's working words into its
+// verdict (include/zfec_hip.h, fec_locate_batch): no mismatch bit -> CLEAN; one
+// check only -> UNKNOWN; exactly one mismatch bit -> that check's slot; exactly
+// one basis slot not excluded -> that slot; else MANY.  A plain vector store.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLocateClean = 0xFFFFFFFFu, kLocateMany = 0xFFFFFFFEu, kLocateUnknown = 0xFFFFFFFDu;
+
+struct alignas(16) FinishJob {
+    const uint32_t* bits;
+    uint32_t* culprit;
+    uint32_t nstripes, k, c, words;
+};
+
+__device__ __forceinline__ uint32_t low_bits(uint32_t n) { return n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u; }
+
+__global__ __launch_bounds__(kBlock) void locate_finish(const FinishJob job) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= job.nstripes) return;
+    const uint32_t* const w = job.bits + size_t(s) * job.words;
+    const uint32_t cw = (job.c + 31u) / 32u, kw = (job.k + 31u) / 32u;
+    uint32_t nbad = 0, first = 0;
+    for (uint32_t i = 0; i < cw; ++i) {
+        const uint32_t v = w[i] & low_bits(job.c - 32u * i);
+        if (v != 0u && nbad == 0u) first = 32u * i + static_cast<uint32_t>(__builtin_ctz(v));
+        nbad += static_cast<uint32_t>(__builtin_popcount(v));
+    }
+    uint32_t verdict;
+    if (nbad == 0u) {
+        verdict = kLocateClean;
+    } else if (job.c == 1u) {
+        verdict = kLocateUnknown;
+    } else if (nbad == 1u) {
+        verdict = job.k + first;
+    } else {
+        uint32_t nleft = 0, slot = 0;
+        for (uint32_t i = 0; i < kw; ++i) {
+            const uint32_t v = ~w[cw + i] & low_bits(job.k - 32u * i);
+            if (v != 0u && nleft == 0u) slot = 32u * i + static_cast<uint32_t>(__builtin_ctz(v));
+            nleft += static_cast<uint32_t>(__builtin_popcount(v));
+        }
+        verdict = nleft == 1u ? slot : kLocateMany;
+    }
+    job.culprit[s] = verdict;
 }
 
 // ---------------------------------------------------------------------------
@@ -3837,6 +4142,57 @@ const std::array<VerifyLaunch, kRegR + 1> g_verify_launch[kRegK + 1] = {
     {}, verify_row<1>(std::make_integer_sequence<int, kRegR>()), verify_row<2>(std::make_integer_sequence<int, kRegR>()),
     verify_row<3>(std::make_integer_sequence<int, kRegR>()), verify_row<4>(std::make_integer_sequence<int, kRegR>())};
 
+// ---- error location dispatch (matlocate_reg) ------------------------------------------
+struct LocateArgs {
+    const uint8_t* q;  // (r-1) x k
+    uint32_t xbit;
+};
+
+char g_locate_names[kRegK + 1][kRegR + 1][24];
+
+template <int K, int R>
+hipError_t launch_locate_kr(const VerifySpec& v, const LocateArgs& a, hipStream_t stream) {
+    LocateJob<K, R> job;
+    job.sstride = v.sstride;
+    job.words = v.words;
+    job.xbit = a.xbit;
+    job.pad_ = 0;
+    for (int i = 0; i < R; ++i)
+        for (int j = 0; j < K; ++j)
+            std::memcpy(&job.tab[(i * K + j) * 5], &kHostBank.w[uint32_t(v.coef[size_t(i) * v.coef_stride + j]) * 8],
+                        5 * sizeof(uint32_t));
+    for (int i = 0; i < (R - 1) * K; ++i)
+        std::memcpy(&job.qtab[i * 5], &kHostBank.w[uint32_t(a.q[i]) * 8], 5 * sizeof(uint32_t));
+    const hipError_t e = verify_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const WaveWalk ww = wave_walk(len, ns);
+        job.sz = len;
+        job.nstripes = static_cast<uint32_t>(ns);
+        job.cps = ww.cps;
+        job.wps = ww.wps;
+        job.gs_w = ww.gs_w;
+        job.gs_s = ww.gs_s;
+        job.bits = v.mismatch + s0 * v.words;
+        for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
+        for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
+        return launch_job(reinterpret_cast<const void*>(matlocate_reg<K, R>), ww.grid, kBlock, 0, stream, job);
+    });
+    if (e == hipSuccess) t_last_kernel = g_locate_names[K][R];
+    return e;
+}
+
+typedef hipError_t (*LocateLaunch)(const VerifySpec&, const LocateArgs&, hipStream_t);
+
+template <int K, int... R>
+constexpr std::array<LocateLaunch, kRegR + 1> locate_row(std::integer_sequence<int, R...>) {
+    return {{nullptr, nullptr, launch_locate_kr<K, R + 2>...}};
+}
+
+const std::array<LocateLaunch, kRegR + 1> g_locate_launch[kRegK + 1] = {
+    {}, locate_row<1>(std::make_integer_sequence<int, kRegR - 1>()),
+    locate_row<2>(std::make_integer_sequence<int, kRegR - 1>()),
+    locate_row<3>(std::make_integer_sequence<int, kRegR - 1>()),
+    locate_row<4>(std::make_integer_sequence<int, kRegR - 1>())};
+
 // ---- matrepair_mixed dispatch ------------------------------------------------------
 // One upload through a MixedRing slot (the records, then any host-side ids)
 // serves every row group of a call.
@@ -3999,6 +4355,106 @@ hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream) {
     });
     if (e == hipSuccess) t_last_kernel = "rows_differ";
     return e;
+}
+
+hipError_t launch_locate(const VerifySpec& v, const uint8_t* q, uint32_t xbit, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    static std::once_flag names_once;
+    std::call_once(names_once, [] {
+        for (int k = 1; k <= kRegK; ++k)
+            for (int r = 2; r <= kRegR; ++r)
+                snprintf(g_locate_names[k][r], sizeof g_locate_names[k][r], "matlocate_reg<%d,%d>", k, r);
+    });
+    if (v.k < 1 || v.k > static_cast<uint32_t>(kRegK) || v.r < 2 || v.r > static_cast<uint32_t>(kRegR) ||
+        v.coef_stride < v.k || !q || !v.mismatch || v.sz == 0 || v.nstripes == 0 || v.nstripes >= (1ull << 32) ||
+        v.bit0 != 0 || v.r > xbit || uint64_t(xbit) + v.k > uint64_t(v.words) * 32)
+        return hipErrorInvalidValue;
+    t_signal_flag = nullptr;
+    t_signal_used = false;
+    return g_locate_launch[v.k][v.r](v, LocateArgs{q, xbit}, stream);
+}
+
+hipError_t locate_tables_upload(const uint8_t* q, uint32_t k, uint32_t c, hipStream_t stream, LocateTables* out) {
+    if (!q || !out || k < 1 || c < 2) return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    const size_t n = size_t(k) * (c - 1), bytes = n * 5 * sizeof(uint32_t);
+    MixedRing::Slot* slot = nullptr;
+    hipError_t e = mixed_slot(bytes, &slot);
+    if (e != hipSuccess) return e;
+    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
+    for (size_t i = 0; i < n; ++i) std::memcpy(ht + i * 5, &kHostBank.w[uint32_t(q[i]) * 8], 5 * sizeof(uint32_t));
+    if ((e = hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    out->dev = reinterpret_cast<const uint32_t*>(slot->dev);
+    out->slot = slot;
+    return hipSuccess;
+}
+
+void locate_tables_release(const LocateTables& t, hipStream_t stream) {
+    MixedRing::Slot* slot = static_cast<MixedRing::Slot*>(t.slot);
+    if (!slot) return;
+    // the copy (and any launch made) reads the slot: it stays busy whatever happened
+    if (hipEventRecord(slot->ev, stream) == hipSuccess)
+        slot->busy = true;
+    else
+        (void)hipStreamSynchronize(stream);
+}
+
+hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint8_t* b0, uint32_t k, uint32_t xbit,
+                              const uint32_t* qtab_dev, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (d.r < 1 || d.r > static_cast<uint32_t>(kMaxOut) || !d.mismatch || !a0 || !b0 || !qtab_dev || k < 1 ||
+        d.sz == 0 || d.nstripes == 0 || d.nstripes >= (1ull << 32) || uint64_t(d.bit0) + d.r > xbit ||
+        uint64_t(xbit) + k > uint64_t(d.words) * 32)
+        return hipErrorInvalidValue;
+    t_signal_flag = nullptr;
+    t_signal_used = false;
+    LocateRowsJob job;
+    job.a_sstride = d.a_sstride;
+    job.b_sstride = d.b_sstride;
+    job.words = d.words;
+    job.bit0 = d.bit0;
+    job.r = d.r;
+    job.k = k;
+    job.xbit = xbit;
+    job.pad_ = 0;
+    job.qtab = qtab_dev;
+    for (uint32_t i = d.r; i < static_cast<uint32_t>(kMaxOut); ++i) job.a[i] = job.b[i] = nullptr;
+    const hipError_t e = verify_pieces(d.sz, d.nstripes, [&](uint64_t b0off, uint64_t len, uint64_t s0, uint64_t ns) {
+        const WaveWalk ww = wave_walk(len, ns);
+        job.sz = len;
+        job.nstripes = static_cast<uint32_t>(ns);
+        job.cps = ww.cps;
+        job.wps = ww.wps;
+        job.gs_w = ww.gs_w;
+        job.gs_s = ww.gs_s;
+        job.bits = d.mismatch + s0 * d.words;
+        job.a0 = a0 + b0off + s0 * d.a_sstride;
+        job.b0 = b0 + b0off + s0 * d.b_sstride;
+        for (uint32_t i = 0; i < d.r; ++i) {
+            job.a[i] = d.a[i] + b0off + s0 * d.a_sstride;
+            job.b[i] = d.b[i] + b0off + s0 * d.b_sstride;
+        }
+        return launch_job(reinterpret_cast<const void*>(rows_locate), ww.grid, kBlock, 0, stream, job);
+    });
+    if (e == hipSuccess) t_last_kernel = "rows_locate";
+    return e;
+}
+
+hipError_t launch_locate_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
+                                uint32_t* culprit, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (!bits || !culprit || k < 1 || c < 1 || nstripes == 0 || nstripes >= (1ull << 32) ||
+        words != (c + 31) / 32 + (k + 31) / 32)
+        return hipErrorInvalidValue;
+    FinishJob job;
+    job.bits = bits;
+    job.culprit = culprit;
+    job.nstripes = static_cast<uint32_t>(nstripes);
+    job.k = k;
+    job.c = c;
+    job.words = words;
+    const uint32_t grid = static_cast<uint32_t>((nstripes + kBlock - 1) / kBlock);
+    return launch_job(reinterpret_cast<const void*>(locate_finish), grid, kBlock, 0, stream, job);
 }
 
 hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream) {

@@ -145,6 +145,34 @@ struct DifferSpec {
 };
 hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream);
 
+// Single-block error location (fec_locate_batch).  Every stripe has `words`
+// working words in device memory, cleared by the caller in stream order:
+// mismatch bit i at bit index i (as above), excluded bit j of basis slot j at
+// bit index xbit + j, OR-ed in when the hypothesis "only basis slot j is
+// corrupt" is refuted at some byte.  q: Q[i][j] = P[i][j] / P[0][j] for
+// i = 1..c-1, (c-1) x k row-major.
+//
+// launch_locate (matlocate_reg<K, R>, k <= 4, 2 <= r <= 8): all r = c checks in
+// one launch; `v` as for launch_verify with bit0 = 0.
+// locate_tables_upload: the k*(c-1) tables of q into device memory through the
+// thread's staging ring, by one stream-ordered copy; locate_tables_release
+// after the last launch that reads them (it records the slot's event).
+// launch_rows_locate (rows_locate): rows [d.bit0, d.bit0 + d.r) of the c checks,
+// a0 / b0 row 0's pair (stripe 0 of the launch, as a and b).
+// launch_locate_finish (locate_finish): the words of nstripes stripes into one
+// verdict dword each; it leaves matapply_last_kernel() as it was.
+struct LocateTables {
+    const uint32_t* dev = nullptr;
+    void* slot = nullptr;
+};
+hipError_t launch_locate(const VerifySpec& v, const uint8_t* q, uint32_t xbit, hipStream_t stream);
+hipError_t locate_tables_upload(const uint8_t* q, uint32_t k, uint32_t c, hipStream_t stream, LocateTables* out);
+void locate_tables_release(const LocateTables& t, hipStream_t stream);
+hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint8_t* b0, uint32_t k, uint32_t xbit,
+                              const uint32_t* qtab_dev, hipStream_t stream);
+hipError_t launch_locate_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
+                                uint32_t* culprit, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
