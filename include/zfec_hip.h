@@ -320,6 +320,69 @@ int fec_locate_batch(const fec_t* code,
  * FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
 int fec_locate_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
 
+/* Batched in-place correction: scrub, locate and heal in ONE call.  The
+ * arguments are exactly those of fec_locate_batch, except that `blocks` is
+ * writable.  Over all sz bytes of each stripe:
+ *
+ *   1. culprit[s] receives exactly the verdict fec_locate_batch would give for
+ *      the blocks as they were on entry (rules 1-5 above).
+ *   2. For a stripe whose verdict is a slot h < nb, the sz bytes of slot h are
+ *      rewritten from k other slots of that stripe: the sources S_h are slots
+ *      0..k-1 for h >= k; for h < k they are 0..k-1 with slot h replaced by
+ *      slot k (check 0).  The row applied is row h of the nb x k matrix
+ *      fec_correct_rows returns: P[h-k] for h >= k; for h < k,
+ *      R[l] = P[0][l] / P[0][h] for l != h and R[h] = 1 / P[0][h] (check 0's
+ *      equation solved for slot h).  Equivalently, row h is
+ *      fec_repair_rows(present = block_nums[S_h], targets = {block_nums[h]}).
+ *   3. Nothing else in caller memory is written: no byte of a CLEAN, MANY or
+ *      UNKNOWN stripe; in a corrected stripe no slot but h; no byte past sz of
+ *      slot h (row slack, other stripes); nothing around the nstripes verdict
+ *      words.  A stripe that is not corrected is not read again after the scrub.
+ *
+ * Every stripe that gets a slot verdict is a codeword afterwards.  Let e be
+ * what the rewrite adds to slot h at some byte position, and s_i the
+ * syndromes on entry.  A verdict h means s_i = P[i][h] . d at every byte for
+ * one d per byte (P[i][h] read as the unit column for a check slot: rule 3
+ * or rule 4), and the row above yields e = d.  So
+ *     s_i' = s_i ^ P[i][h] . e = 0   for every i,
+ * and fec_verify_batch on the stripe returns no bit, whatever the corruption
+ * was.  The correction guarantees are those of locate: with c >= 2, exactly one
+ * corrupt block is restored bit for bit; from c blocks corrupt at one byte
+ * position on, a MIScorrection is possible -- the stripe becomes a codeword, but
+ * not the one that was stored -- and with c = 2 that is already two blocks, so a
+ * caller who wants double errors refused passes c >= 3; with c = 1 no verdict
+ * is a slot and nothing is ever rewritten.
+ *
+ * Memory, streams, capture and validation follow fec_locate_batch: blocks are
+ * device memory on one device, or page-locked host memory read AND WRITTEN in
+ * place (plain vector stores only; the atomics stay aimed at device words the
+ * library owns); pageable memory returns FEC_EINVAL; a block-major layout is
+ * walked stripe by stripe; culprit in device memory is used in place and
+ * FEC_FLAG_ASYNC is honoured; culprit in host memory goes through device words
+ * the library owns (the correction reads those) and the call is then
+ * synchronous; under graph capture the call returns FEC_EINVAL.  The checks
+ * and their order are fec_locate_batch's, the messages naming
+ * fec_correct_batch.  nstripes == 0 returns FEC_OK; sz == 0 returns FEC_OK with
+ * every verdict FEC_LOCATE_CLEAN and nothing written.  Slots and stripes must
+ * not overlap in memory.
+ *
+ * The location runs exactly as in fec_locate_batch.  One correction follows it
+ * in the same stream over the verdict words in device memory (the host never
+ * sees them): matcorrect_reg<k> for k <= 4 -- whatever kernel located --
+ * and rows_correct past that.  A wave reads its stripe's verdict by a scalar
+ * load before anything else and skips the stripe unless it names a slot.
+ * fec_last_kernel_name() names the correction kernel. */
+int fec_correct_batch(const fec_t* code,
+                      gf* blocks, size_t block_stride, size_t stripe_stride,
+                      const unsigned* block_nums, size_t num_block_nums,
+                      size_t sz, size_t nstripes,
+                      unsigned* culprit, void* stream, unsigned flags);
+
+/* Host only, no GPU: the nb x k matrix fec_correct_batch applies (row h
+ * rebuilds slot h from its sources S_h, in slot order), row-major into
+ * rows[nb*k].  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
+int fec_correct_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
+
 /* Batched repair: rebuild any lost blocks of every stripe, primaries and parity
  * alike, from the k blocks the stripe still holds, in one call (the step after
  * fec_verify_batch in a store's scrub-and-repair cycle).

@@ -639,8 +639,37 @@ class Decoder(_fec.Decoder):
             _capi_code(self).locate_batch(ptr, sbs, sss, nums, sz, ns, out.data_ptr(), stream=stream, flags=flags)
         return out
 
+    def correct_batch(self, blocks, blocknums):
+        """Scrub, locate and heal in place, in one call (fec_correct_batch).
+
+        blocks and blocknums as in locate_batch, with the same preconditions.
+        Returns the torch.int32 verdict tensor [nstripes] locate_batch would
+        return for the blocks as they were on entry, and CORRECTS `blocks` IN
+        PLACE: in a stripe whose verdict is a slot h >= 0, the sz bytes of slot
+        h are rewritten from k other slots of that stripe (slots 0..k-1, check
+        0 standing in for h when h < k).  Nothing else is written: no byte of a
+        LOCATE_CLEAN, LOCATE_MANY or LOCATE_UNKNOWN stripe, no other slot of a
+        corrected stripe, nothing past a row's sz bytes.  Every corrected
+        stripe is consistent afterwards (verify_batch returns no bit for it).
+        With two or more checks a stripe with exactly one corrupt block is
+        restored bit for bit.  With exactly two checks, two blocks corrupt at
+        one byte position can be taken for a third and miscorrected: pass
+        nb >= k + 3 to have every double error refused (LOCATE_MANY) instead.
+        With one check nothing is ever rewritten.  The work is enqueued on the
+        current stream, without a host sync."""
+        import torch
+
+        nums, nb, ns, sz, sbs, sss, ptr = self._scrub_args(blocks, blocknums, "correct_batch")
+        if not (ns and sz):
+            return torch.full((ns,), LOCATE_CLEAN, dtype=torch.int32, device=blocks.device)
+        out = torch.empty((ns,), dtype=torch.int32, device=blocks.device)
+        stream, flags = _batch_call_args(blocks)
+        with _as_error():
+            _capi_code(self).correct_batch(ptr, sbs, sss, nums, sz, ns, out.data_ptr(), stream=stream, flags=flags)
+        return out
+
     def _scrub_args(self, blocks, blocknums, what):
-        """The preconditions verify_batch and locate_batch share; returns
+        """The preconditions verify_batch, locate_batch and correct_batch share; returns
         (nums, nb, nstripes, sz, block stride, stripe stride, address)."""
         import torch
 

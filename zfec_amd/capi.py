@@ -65,6 +65,8 @@ SYMBOLS = [
     ("fec_repair_rows", ctypes.c_int, [_P, _UP, _UP, _SZ, _P]),
     ("fec_locate_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
     ("fec_locate_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
+    ("fec_correct_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
+    ("fec_correct_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_REPAIR_NONE = 0xFFFFFFFF  # a target slot its pattern does not use
@@ -313,6 +315,15 @@ class Code(object):
         if st:
             check(st)
 
+    def correct_batch(self, blocks, bs, ss, block_nums, sz, nstripes, culprit_ptr, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_correct_batch: the arguments of locate_batch, `blocks` writable.
+        The verdicts go to `culprit_ptr` as there, and the slot a verdict names
+        is rewritten in place from k other slots of its stripe."""
+        st = lib().fec_correct_batch(self.ptr, blocks, bs, ss, _nums(block_nums), len(block_nums), sz, nstripes,
+                                     culprit_ptr or None, stream or None, flags)
+        if st:
+            check(st)
+
     def encode_batch_multi(self, src, sbs, sss, dst, dbs, dss, block_nums, sz, nstripes, devices, flags=0):
         """fec_encode_batch_multi: the stripes split over `devices` (host memory)."""
         devs = (ctypes.c_int * max(1, len(devices)))(*devices)
@@ -364,6 +375,17 @@ def locate_rows(code, block_nums):
     n = max(0, (len(nums) - code.k - 1) * code.k)
     rows = (ctypes.c_ubyte * max(1, n))()
     check(lib().fec_locate_rows(code.ptr, uint_array(nums), len(nums), ctypes.cast(rows, _P)))
+    return bytes(rows)[:n]
+
+
+def correct_rows(code, block_nums):
+    """fec_correct_rows: the nb*k bytes (row-major, nb = len(block_nums)) of
+    the matrix fec_correct_batch applies; row h rebuilds slot h from slots
+    0..k-1, slot k (check 0) standing in for slot h when h < k.  Host only."""
+    nums = list(block_nums)
+    n = len(nums) * code.k
+    rows = (ctypes.c_ubyte * max(1, n))()
+    check(lib().fec_correct_rows(code.ptr, uint_array(nums), len(nums), ctypes.cast(rows, _P)))
     return bytes(rows)[:n]
 
 

@@ -1786,12 +1786,30 @@ void locate_rows(const uint8_t* P, unsigned k, unsigned c, uint8_t* Q) {
         for (unsigned j = 0; j < k; ++j) Q[size_t(i - 1) * k + j] = f.mul[P[size_t(i) * k + j]][f.inv[P[j]]];
 }
 
+// The nb x k correction matrix (fec_correct_rows): row h rebuilds slot h from
+// slots 0..k-1, slot k (check 0) standing in for slot h when h < k.  Solving
+// check 0's equation c_0 = sum_l P[0][l] . b_l for b_h gives R[l] = P[0][l] /
+// P[0][h] for l != h and R[h] = 1 / P[0][h] (applied to c_0); rows k.. are P.
+void correct_rows(const uint8_t* P, unsigned k, unsigned c, uint8_t* R) {
+    const Field& f = field();
+    for (unsigned h = 0; h < k; ++h) {
+        const uint8_t ih = f.inv[P[h]];
+        for (unsigned l = 0; l < k; ++l) R[size_t(h) * k + l] = l == h ? ih : f.mul[P[l]][ih];
+    }
+    std::memcpy(R + size_t(k) * k, P, size_t(c) * k);
+}
+
 // The working words of a call (W = ceil(c/32) + ceil(k/32) per stripe, mismatch
 // bits from bit 0, excluded bits from bit 32*ceil(c/32)) live in the thread's
 // vmask buffer, under run_verify's ev_verify ordering; a host-side culprit is
 // gathered behind them.
+//
+// With `heal` (fec_correct_batch; `fn` names the call in messages) one
+// correction follows locate_finish in the same stream, over the verdict words
+// in device memory: the host never sees them.
 int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const unsigned* nums, size_t nb, size_t sz,
-               size_t nstripes, unsigned* culprit, void* stream, unsigned flags) {
+               size_t nstripes, unsigned* culprit, void* stream, unsigned flags, const char* fn = "fec_locate_batch",
+               bool heal = false) {
     const unsigned k = code->k, c = static_cast<unsigned>(nb - k), cw = (c + 31) / 32, words = cw + (k + 31) / 32;
     const unsigned xbit = 32 * cw;
     if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
@@ -1804,8 +1822,8 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
         const size_t extent = (nstripes - 1) * sss + (nb - 1) * sbs + sz;
         dev = pointer_device(src);
         if (dev < 0 && !(zsrc = mapped_block(src, extent)))
-            return set_status(FEC_EINVAL, "fec_locate_batch takes device or page-locked host memory: src is pageable "
-                                          "host memory, which this call does not stage");
+            return set_status(FEC_EINVAL, "%s takes device or page-locked host memory: %s is pageable "
+                                          "host memory, which this call does not stage", fn, heal ? "blocks" : "src");
         if (dev >= 0 && cdev >= 0 && cdev != dev)
             return set_status(FEC_EINVAL, "culprit lives on device %d, the blocks on device %d", cdev, dev);
     }
@@ -1816,8 +1834,8 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     if (dev_ctx(dev, &d)) return t_status;
     hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
     if (stream_capturing(st))
-        return set_status(FEC_EINVAL, "fec_locate_batch: the stream is being captured into a graph (the call uses "
-                                      "memory the library owns and reuses)");
+        return set_status(FEC_EINVAL, "%s: the stream is being captured into a graph (the call uses "
+                                      "memory the library owns and reuses)", fn);
     hipError_t e;
     if (!d->ev_verify && (e = hipEventCreateWithFlags(&d->ev_verify, hipEventDisableTiming)) != hipSuccess)
         return hip_fail(e, "hipEventCreateWithFlags");
@@ -1830,8 +1848,8 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     if ((e = hipMemsetAsync(bits, 0, work_bytes, st)) != hipSuccess)
         return hip_fail(e, "hipMemsetAsync (working words)");
     int rc = FEC_OK;
+    thread_local std::vector<uint8_t> P, Q, R;
     if (sz) {
-        thread_local std::vector<uint8_t> P, Q;
         P.resize(size_t(c) * k);
         Q.resize(size_t(c - 1) * k);
         rc = verify_rows(code, nums, nb, P.data());
@@ -1878,6 +1896,23 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
         if ((e = launch_locate_finish(bits, words, k, c, nstripes, out, st)) != hipSuccess)
             rc = hip_fail(e, "launch_locate_finish");
     }
+    if (!rc && heal && sz) {
+        // row h of the nb x k correction matrix rebuilds slot h (zsrc is the caller's writable blocks)
+        R.resize(nb * k);
+        correct_rows(P.data(), k, c, R.data());
+        CorrectSpec cs;
+        cs.k = k;
+        cs.nb = static_cast<uint32_t>(nb);
+        cs.rows = R.data();
+        cs.blocks = const_cast<uint8_t*>(zsrc);
+        cs.bstride = sbs;
+        cs.sstride = sss;
+        cs.sz = sz;
+        cs.nstripes = nstripes;
+        cs.verdict = out;
+        ++t_launches;
+        if ((e = launch_correct(cs, st)) != hipSuccess) rc = hip_fail(e, "launch_correct");
+    }
     if (!rc && cdev < 0 && (e = hipMemcpyAsync(culprit, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
         rc = hip_fail(e, "hipMemcpyAsync D2H (culprit)");
     // whatever was enqueued uses the shared buffers: they stay busy whatever happened
@@ -1921,6 +1956,39 @@ FEC_API int fec_locate_batch(const fec_t* code, const gf* src, size_t src_block_
     return guarded([&] {
         return run_locate(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
                           culprit, stream, flags);
+    });
+}
+
+// ---- batched in-place correction: scrub, locate and heal in one call ------------------------
+FEC_API int fec_correct_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
+    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
+    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+    return guarded([&] {
+        const unsigned k = code->k, c = static_cast<unsigned>(num_block_nums - k);
+        thread_local std::vector<uint8_t> P;
+        P.resize(size_t(c) * k);
+        if (verify_rows(code, block_nums, num_block_nums, P.data())) return t_status;
+        correct_rows(P.data(), k, c, rows);
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API int fec_correct_batch(const fec_t* code, gf* blocks, size_t block_stride, size_t stripe_stride,
+                              const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
+                              unsigned* culprit, void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!blocks) return set_status(FEC_EINVAL, "NULL buffer: blocks");
+    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
+    if (!culprit) return set_status(FEC_EINVAL, "culprit is NULL");
+    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+    if (!gpu_available()) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_locate(code, blocks, block_stride, stripe_stride, block_nums, num_block_nums, sz, nstripes, culprit,
+                          stream, flags, "fec_correct_batch", true);
     });
 }
 

@@ -1491,6 +1491,137 @@ __global__ __launch_bounds__(kBlock) void locate_finish(const FinishJob job) {
 }
 
 // ---------------------------------------------------------------------------
+// matcorrect_reg<K> / rows_correct: in-place correction (fec_correct_batch)
+// over the verdict words locate_finish wrote.  The walk is matrepair_mixed's
+// (a wave's 64 units lie in ONE stripe), but the stripe's verdict h is read
+// FIRST, wave-uniform through a constant-address-space pointer: a verdict >=
+// nb (CLEAN, MANY, UNKNOWN) takes a scalar branch around everything, so a
+// clean stripe costs one scalar load per wave and no vector memory
+// instruction (almost every stripe is clean; loading before the verdict is
+// known would read the whole batch a second time).
+//
+// For a slot verdict h the sources and the target are chosen per stripe by
+// wave-uniform address arithmetic: slot j sits at blocks + j * bstride, source
+// l is slot (l == h ? k : l) -- check 0 stands in for a bad basis slot, and for
+// h >= k no l equals h -- and the target is slot h.  Record h of the uploaded
+// tables (k coefficients, the Tab layout) is row h of fec_correct_rows; it comes
+// by scalar loads, so v_perm takes the tables as SGPR pairs.  The target is
+// never among its own sources: rewriting it in place has no read/write hazard,
+// and the overlapped last chunk's two lanes store identical bytes.
+//
+// matcorrect_reg<K> (k = K <= 4): K loads, gf_dot<K>, one streaming store (byte
+// by byte for a block shorter than a chunk, so no byte past sz is written).
+// rows_correct (any k): a loop over the k sources, each coefficient's table by
+// wave-uniform scalar loads, the result accumulated in registers.  Dirty
+// stripes are rare; its speed is not a goal.
+// ---------------------------------------------------------------------------
+struct alignas(16) CorrectJob {
+    uint64_t sz, bstride, sstride;
+    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
+    uint32_t wps;            // waves per stripe
+    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    uint32_t k, nb;
+    uint32_t pad_;
+    const uint32_t* tabs;     // nb records of k * 5 dwords
+    const uint32_t* verdict;  // nstripes verdict words
+    uint8_t* blocks;          // slot 0 of the launch's first stripe (and byte range)
+};
+
+template <int K>
+__global__ __launch_bounds__(kBlock) void matcorrect_reg(const CorrectJob job) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    const CU32 verdict = (CU32)job.verdict;
+    while (s < job.nstripes) {
+        const uint32_t h = __builtin_amdgcn_readfirstlane(verdict[s]);
+        if (h < job.nb) {  // wave-uniform: a scalar branch, not taken on clean data
+            const uint32_t c = w * 64u + lane;
+            const bool live = c < job.cps;
+            const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+            uint8_t* const base = job.blocks + s * job.sstride + sp.off;
+            u32x4 x[K];
+#pragma unroll
+            for (int l = 0; l < K; ++l) {
+                const uint32_t slot = static_cast<uint32_t>(l) == h ? static_cast<uint32_t>(K) : static_cast<uint32_t>(l);
+                x[l] = load_unit(base + slot * job.bstride, live, sp);
+            }
+            const CU32 tp = (CU32)job.tabs + size_t(h) * (K * 5);
+            Tab t[K];
+#pragma unroll
+            for (int l = 0; l < K; ++l) t[l] = Tab{tp[l * 5], tp[l * 5 + 1], tp[l * 5 + 2], tp[l * 5 + 3], tp[l * 5 + 4]};
+            Sel sel[4][K];
+#pragma unroll
+            for (int l = 0; l < K; ++l) {
+                sel[0][l] = selectors(x[l].x);
+                sel[1][l] = selectors(x[l].y);
+                sel[2][l] = selectors(x[l].z);
+                sel[3][l] = selectors(x[l].w);
+            }
+            const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]), gf_dot<K>(t, sel[3])};
+            if (live) {
+                uint8_t* const out = base + h * job.bstride;
+                if (sp.full)
+                    store16_pol<0>(out, y);
+                else
+                    store_tail(out, y, sp.nb);
+            }
+        }
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void rows_correct(const CorrectJob job) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t s = gw / job.wps, w = gw - s * job.wps;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    const CU32 verdict = (CU32)job.verdict;
+    while (s < job.nstripes) {
+        const uint32_t h = __builtin_amdgcn_readfirstlane(verdict[s]);
+        if (h < job.nb) {  // wave-uniform
+            const uint32_t c = w * 64u + lane;
+            const bool live = c < job.cps;
+            const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+            uint8_t* const base = job.blocks + s * job.sstride + sp.off;
+            const CU32 tp = (CU32)job.tabs + size_t(h) * job.k * 5u;
+            u32x4 y{0u, 0u, 0u, 0u};
+            for (uint32_t l = 0; l < job.k; ++l) {
+                const uint32_t slot = l == h ? job.k : l;
+                const u32x4 x = load_unit(base + slot * job.bstride, live, sp);
+                const Tab t[1] = {Tab{tp[l * 5u], tp[l * 5u + 1u], tp[l * 5u + 2u], tp[l * 5u + 3u], tp[l * 5u + 4u]}};
+                const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
+                y.x ^= gf_dot<1>(t, z[0]);
+                y.y ^= gf_dot<1>(t, z[1]);
+                y.z ^= gf_dot<1>(t, z[2]);
+                y.w ^= gf_dot<1>(t, z[3]);
+            }
+            if (live) {
+                uint8_t* const out = base + h * job.bstride;
+                if (sp.full)
+                    store16_pol<0>(out, y);
+                else
+                    store_tail(out, y, sp.nb);
+            }
+        }
+        w += job.gs_w;
+        s += job.gs_s;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // matapply_lds<ACC, NT, RT>: runtime k and r like matapply_gen, but each
 // workgroup first expands its k*r coefficients into LDS tables (32 bytes per
 // coefficient).  In the loop a table is two broadcast LDS reads off one base
@@ -4455,6 +4586,56 @@ hipError_t launch_locate_finish(const uint32_t* bits, uint32_t words, uint32_t k
     job.words = words;
     const uint32_t grid = static_cast<uint32_t>((nstripes + kBlock - 1) / kBlock);
     return launch_job(reinterpret_cast<const void*>(locate_finish), grid, kBlock, 0, stream, job);
+}
+
+hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream) {
+    static const char* const kNames[kRegK + 1] = {"", "matcorrect_reg<1>", "matcorrect_reg<2>", "matcorrect_reg<3>",
+                                                  "matcorrect_reg<4>"};
+    static const void* const kFns[kRegK + 1] = {
+        nullptr, reinterpret_cast<const void*>(matcorrect_reg<1>), reinterpret_cast<const void*>(matcorrect_reg<2>),
+        reinterpret_cast<const void*>(matcorrect_reg<3>), reinterpret_cast<const void*>(matcorrect_reg<4>)};
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (p.k < 1 || p.nb <= p.k || p.nb > 256 || !p.rows || !p.verdict || !p.blocks || p.sz == 0 || p.nstripes == 0 ||
+        p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    t_signal_flag = nullptr;
+    t_signal_used = false;
+    const bool reg = p.k <= static_cast<uint32_t>(kRegK);
+    const size_t n = size_t(p.nb) * p.k, bytes = n * 5 * sizeof(uint32_t);
+    MixedRing::Slot* slot = nullptr;
+    hipError_t e = mixed_slot(bytes, &slot);
+    if (e != hipSuccess) return e;
+    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
+    for (size_t i = 0; i < n; ++i) std::memcpy(ht + i * 5, &kHostBank.w[uint32_t(p.rows[i]) * 8], 5 * sizeof(uint32_t));
+    if ((e = hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    CorrectJob job;
+    job.bstride = p.bstride;
+    job.sstride = p.sstride;
+    job.k = p.k;
+    job.nb = p.nb;
+    job.pad_ = 0;
+    job.tabs = reinterpret_cast<const uint32_t*>(slot->dev);
+    const void* const fn = reg ? kFns[p.k] : reinterpret_cast<const void*>(rows_correct);
+    e = verify_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const WaveWalk ww = wave_walk(len, ns);
+        job.sz = len;
+        job.nstripes = static_cast<uint32_t>(ns);
+        job.cps = ww.cps;
+        job.wps = ww.wps;
+        job.gs_w = ww.gs_w;
+        job.gs_s = ww.gs_s;
+        job.verdict = p.verdict + s0;
+        job.blocks = p.blocks + b0 + s0 * p.sstride;
+        return launch_job(fn, ww.grid, kBlock, 0, stream, job);
+    });
+    // the copy (and any launch made) reads the slot: it stays busy whatever happened
+    if (hipEventRecord(slot->ev, stream) == hipSuccess)
+        slot->busy = true;
+    else
+        (void)hipStreamSynchronize(stream);
+    if (e == hipSuccess) t_last_kernel = reg ? kNames[p.k] : "rows_correct";
+    return e;
 }
 
 hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream) {

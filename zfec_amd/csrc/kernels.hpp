@@ -173,6 +173,25 @@ hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint
 hipError_t launch_locate_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
                                 uint32_t* culprit, hipStream_t stream);
 
+// In-place correction (fec_correct_batch) over the verdict words
+// launch_locate_finish wrote, in device memory: a stripe whose verdict h is
+// below nb has slot h (at blocks + h * bstride) rewritten as row h of `rows`
+// (nb x k coefficients, host memory) applied to slots 0..k-1, slot k taking
+// slot h's place when h < k; every other stripe costs one scalar load per wave
+// and is neither read nor written.  matcorrect_reg<k> for k <= 4, rows_correct
+// past that.  The nb x k tables go through the thread's staging ring by one
+// stream-ordered copy, the slot's event recorded after the last launch, so the
+// call declines under graph capture (hipErrorNotSupported).
+struct CorrectSpec {
+    uint32_t k, nb;
+    const uint8_t* rows;  // nb x k coefficients (host memory)
+    uint8_t* blocks;      // slot 0 of stripe 0, a kernel-visible address
+    uint64_t bstride, sstride;
+    uint64_t sz, nstripes;
+    const uint32_t* verdict;  // nstripes words, device memory
+};
+hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
