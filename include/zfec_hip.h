@@ -234,9 +234,17 @@ int fec_mixed_decode_rows(const fec_t* code, const unsigned* pattern, gf* rows);
  *
  * k <= 4 runs on matverify_reg<k, r> (at most 8 checks per launch): the check
  * rows are recomputed in registers and compared, so the call reads every block
- * once and, on clean data, writes nothing.  Other codes compute the expected
- * rows into library scratch (at most 64 MiB per device, batches cut to fit)
- * with the encode kernels and compare them with rows_differ. */
+ * once and, on clean data, writes nothing.  4 < k <= 32 with blocks of at
+ * least 2048 bytes in device memory runs on matverify_bsr<rt>, <rt,lds> or
+ * <rt,lds,tbl> (at most 40 checks per launch) once the call has
+ * ZFEC_HIP_VERIFY_FUSED_MIN units of 2 KiB (ceil(sz / 2048) x nstripes): the
+ * bit-sliced encode walk with the check rows kept as bit-planes in registers
+ * and compared there, so these calls too read every block once, write nothing
+ * on clean data and need no scratch (calls on different streams do not wait
+ * for each other).  Everything else -- smaller calls, shorter blocks, k > 32,
+ * page-locked host blocks -- computes the expected rows into library scratch
+ * (at most 64 MiB per device, batches cut to fit) with the encode kernels and
+ * compares them with rows_differ. */
 int fec_verify_batch(const fec_t* code,
                      const gf* src, size_t src_block_stride, size_t src_stripe_stride,
                      const unsigned* block_nums, size_t num_block_nums,

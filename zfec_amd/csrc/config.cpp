@@ -14,6 +14,15 @@ const char* env(const char* name) {
     return v && *v ? v : nullptr;
 }
 
+// Default of Config::verify_fused_min.  Never below 32: launches of up to 18
+// units are pinned to the two-step path by the scratch-path tests.  Measured
+// (tools/verify_wide_bench.py, profiles/verify_wide_bench.json; K=10/M=16, 4 KiB
+// blocks, cold): no crossover -- the fused call is ahead at every count tried,
+// 16 units 0.0106 against 0.0195 ms (0.54 x), 64 units 0.0107 / 0.0196, 256
+// units 0.0111 / 0.0175, 1024 units 0.0126 / 0.0223 -- so the default is the
+// smallest measured count above that floor.
+constexpr size_t kVerifyFusedMin = 64;
+
 size_t env_size(const char* name, size_t dflt) {
     const char* v = env(name);
     return v ? static_cast<size_t>(strtoull(v, nullptr, 10)) : dflt;
@@ -39,6 +48,10 @@ Config* read_env() {
     const size_t vs = env_size("ZFEC_HIP_VERIFY_SCRATCH", 0), vmax = size_t(64) << 20;
     // (255 check rows of at least 128 bytes each must fit)
     c->verify_scratch = vs >= (64u << 10) && vs < vmax ? vs : vmax;
+    // 2-KiB units (ceil(sz / 2048) x nstripes) from which fec_verify_batch's wide
+    // shapes take the fused kernel; 0 is read as 1, 4294967295 turns it off.
+    const size_t vf = env_size("ZFEC_HIP_VERIFY_FUSED_MIN", kVerifyFusedMin);
+    c->verify_fused_min = vf ? vf : 1;
     return c;
 }
 

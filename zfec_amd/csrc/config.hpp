@@ -34,6 +34,7 @@ struct Config {
     size_t stage_chunk;    // ZFEC_HIP_STAGE_CHUNK: bytes of each block per staged chunk (0: automatic)
     size_t grid_cap;       // ZFEC_HIP_GRID_CAP: most workgroups per launch of the unit kernels (reg, rows, pair, lds; 0: automatic)
     size_t verify_scratch; // ZFEC_HIP_VERIFY_SCRATCH: cap of fec_verify_batch's expected-row scratch, bytes (64 MiB; only lowered)
+    uint64_t verify_fused_min;  // ZFEC_HIP_VERIFY_FUSED_MIN: 2-KiB units from which a wide verify runs matverify_bsr (config.cpp)
 };
 
 const Config& config();

@@ -1683,6 +1683,57 @@ int verify_scratch_path(DevCtx& d, const uint8_t* P, unsigned k, unsigned c, con
     return FEC_OK;
 }
 
+// 4 < k <= 32 on device memory, from Config::verify_fused_min 2-KiB units up:
+// matverify_bsr computes the check rows as bit-planes in registers and
+// compares them with the stored rows in the same launch -- k + c rows read, no
+// scratch, so no cutting into runs and no buffer shared between streams.  More
+// than kVerifyBsrRows checks run as launches of at most that many, the bit
+// index advancing (the basis is re-read per launch: still fewer bytes than the
+// two-step path's k + 3c).  Every launch must have a shape the kernels take,
+// or the whole call keeps the two-step path.
+bool verify_fused_ok(unsigned k, unsigned c, size_t sz, size_t nstripes) {
+    if (k <= 4 || sz < 2048) return false;
+    for (unsigned g0 = 0; g0 < c; g0 += kVerifyBsrRows)
+        if (!verify_bsr_ok(k, std::min(kVerifyBsrRows, c - g0), sz)) return false;
+    const uint64_t units = uint64_t((sz + 2047) / 2048) * nstripes;
+    return units >= config().verify_fused_min && units < (1ull << 32) - (1ull << 24);
+}
+
+// *declined: a launch had no kernel on this device (hipErrorNotSupported);
+// whatever earlier launches OR-ed in stays valid, the caller runs the two-step path.
+int verify_fused_path(const uint8_t* P, unsigned k, unsigned c, const gf* src, size_t sbs, size_t sss, size_t sz,
+                      size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st, bool* declined) {
+    const uint8_t* in[kMaxIn];
+    const uint8_t* chk[kVerifyBsrRows];
+    for (unsigned j = 0; j < k; ++j) in[j] = src + j * sbs;
+    for (unsigned g0 = 0; g0 < c; g0 += kVerifyBsrRows) {
+        const unsigned rg = std::min(kVerifyBsrRows, c - g0);
+        for (unsigned i = 0; i < rg; ++i) chk[i] = src + size_t(k + g0 + i) * sbs;
+        VerifySpec v;
+        v.coef = P + size_t(g0) * k;
+        v.coef_stride = k;
+        v.k = k;
+        v.r = rg;
+        v.in = in;
+        v.chk = chk;
+        v.sz = sz;
+        v.nstripes = nstripes;
+        v.sstride = sss;
+        v.mismatch = mask;
+        v.words = words;
+        v.bit0 = g0;
+        const hipError_t e = launch_verify_bsr(v, st);
+        if (e == hipErrorNotSupported) {
+            (void)hipGetLastError();
+            *declined = true;
+            return FEC_OK;
+        }
+        ++t_launches;
+        if (e != hipSuccess) return hip_fail(e, "launch_verify_bsr");
+    }
+    return FEC_OK;
+}
+
 int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const unsigned* nums, size_t nb, size_t sz,
                size_t nstripes, unsigned* mismatch, void* stream, unsigned flags) {
     const unsigned k = code->k, c = static_cast<unsigned>(nb - k), words = (c + 31) / 32;
@@ -1690,11 +1741,13 @@ int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     const size_t mask_bytes = nstripes * words * sizeof(uint32_t);
     const int mdev = pointer_device(mismatch);
     int dev = -1;
+    bool src_dev = false;
     const gf* zsrc = src;
     if (sz) {
         // device memory on one device, or page-locked host memory (read in place)
         const size_t extent = (nstripes - 1) * sss + (nb - 1) * sbs + sz;
         dev = pointer_device(src);
+        src_dev = dev >= 0;
         if (dev < 0 && !(zsrc = mapped_block(src, extent)))
             return set_status(FEC_EINVAL, "fec_verify_batch takes device or page-locked host memory: src is pageable "
                                           "host memory, which this call does not stage");
@@ -1714,7 +1767,10 @@ int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     if (!d->ev_verify && (e = hipEventCreateWithFlags(&d->ev_verify, hipEventDisableTiming)) != hipSuccess)
         return hip_fail(e, "hipEventCreateWithFlags");
     // the thread's scratch and mask buffer: wait (on the GPU) for the call that used them last
-    const bool reg = k <= 4, shared = mdev < 0 || (!reg && sz);
+    // (the fused kernels read page-locked host blocks no better than the two
+    // steps do -- both move k + c over PCIe -- so those keep the two-step path)
+    const bool reg = k <= 4, fused = !reg && sz && src_dev && verify_fused_ok(k, c, sz, nstripes);
+    bool shared = mdev < 0 || (!reg && !fused && sz);
     if (shared && d->verify_busy && (e = hipStreamWaitEvent(st, d->ev_verify, 0)) != hipSuccess)
         return hip_fail(e, "hipStreamWaitEvent");
     // mismatch in host memory: the kernels' device-scope atomics must not aim
@@ -1727,9 +1783,19 @@ int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
         thread_local std::vector<uint8_t> P;
         P.resize(size_t(c) * k);
         rc = verify_rows(code, nums, nb, P.data());
-        if (!rc)
-            rc = reg ? verify_reg_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st)
-                     : verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st);
+        bool two_step = !reg && !fused;
+        if (!rc && fused) {
+            rc = verify_fused_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st, &two_step);
+            // declined: the scratch after all, ordered after its last user
+            if (!rc && two_step && !shared) {
+                shared = true;
+                if (d->verify_busy && (e = hipStreamWaitEvent(st, d->ev_verify, 0)) != hipSuccess)
+                    rc = hip_fail(e, "hipStreamWaitEvent");
+            }
+        }
+        if (!rc && reg) rc = verify_reg_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st);
+        if (!rc && two_step)
+            rc = verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st);
     }
     if (!rc && mdev < 0 && (e = hipMemcpyAsync(mismatch, mask, mask_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
         rc = hip_fail(e, "hipMemcpyAsync D2H (mismatch)");

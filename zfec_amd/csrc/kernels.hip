@@ -43,6 +43,10 @@
 //                       precompiled multiply-by-constant routines
 //                       (gf_routines.inc); past 32 inputs or 40 rows its
 //                       pointers and coefficients come from a device-side table.
+//   matverify_bsr<RT>   matapply_bsr's walk for 4 < k <= 32 with the rows kept as
+//                       bit-planes and compared with the stored check blocks
+//                       instead of stored: fec_verify_batch on wide codes reads
+//                       every block once and needs no scratch.
 //   matapply_bsg        bit-sliced, coefficients as run-time data, k <= 256
 //                       (past 32 inputs its pointers and coefficients come
 //                       from a device-side table).
@@ -2424,8 +2428,140 @@ __host__ __device__ constexpr uint32_t bsr_in_bytes() {
     return CMB ? 30u * 256u : 8u * 256u;
 }
 
+// Verify forms (matverify_bsr, fec_verify_batch): the argument blocks of
+// BsrJob / BsrTblJob with the stored check rows where the outputs were (they
+// share the inputs' stripe stride, so out_sstride's place holds the mismatch
+// words) and the words' geometry.  k <= 32 and r <= 40 only: 72 block pointers
+// in the table form.
+struct alignas(16) BsrVfyJob {
+    uint64_t sz, in_sstride;
+    uint32_t* mismatch;
+    uint32_t nstripes, k, r, cps, gs_c, gs_s;
+    uint32_t words, bit0;  // mismatch words per stripe; bit index of row 0
+    const uint8_t* in[kMaxIn];
+    const uint8_t* out[kBsrMaxOut];  // the stored check rows
+    uint64_t addr[kBsrArgAddrs];
+};
+static_assert(sizeof(BsrVfyJob) <= 4096, "kernel arguments are limited to 4 KiB");
+
+constexpr int kBsrVfyPtrs = kMaxIn + kBsrMaxOut;
+struct alignas(16) BsrVfyTblJob {
+    uint64_t sz, in_sstride;
+    uint32_t* mismatch;
+    uint32_t nstripes, k, r, cps, gs_c, gs_s;
+    uint32_t ngroups;  // 1
+    uint32_t words, bit0;
+    uint32_t pad_;
+    const uint64_t* addr;             // device: [wave][input][RT] routine addresses
+    const uint8_t* ptr[kBsrVfyPtrs];  // k input block pointers, then r stored check rows
+};
+static_assert(sizeof(BsrVfyTblJob) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// f(integral_constant<int, I>) for I = I0 .. N - 1: a loop whose index is a
+// compile-time value.
+template <int I, int N, class F>
+__device__ __forceinline__ void bsr_static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        bsr_static_for<I + 1, N>(f);
+    }
+}
+
+// A stored row's two pieces into the plane and combination registers the walk
+// has left dead (v8..v31, eight per prefetch slot), at the point of use: left
+// to itself the allocator put them in v0..v7 and spilled the unit loop's
+// invariants around the epilogue at RT = 10.
+template <int S>
+__device__ __forceinline__ void bsr_verify_pin(u32x4& a, u32x4& b) {
+    static_assert(S >= 0 && S < 3, "three prefetch slots");
+    if constexpr (S == 0)
+        asm volatile("" : "+{v[8:11]}"(a), "+{v[12:15]}"(b));
+    else if constexpr (S == 1)
+        asm volatile("" : "+{v[16:19]}"(a), "+{v[20:23]}"(b));
+    else
+        asm volatile("" : "+{v[24:27]}"(a), "+{v[28:31]}"(b));
+}
+
+// The verify epilogue of a wave's tile: the computed rows stay bit-planes in
+// acc; each live row's stored 32 bytes per lane (at chk(rr) + ib and + 1024)
+// are transposed into planes, XOR-ed in and OR-ed into one dword -- the
+// syndrome is nonzero iff some plane is, so acc is never transposed back --
+// and one ballot per row builds the wave-uniform mask that one lane ORs into
+// the stripe's words (mismatch_or; clean data: no store, no atomic).  Stored
+// rows are loaded two rows ahead of their use for RT <= 9 (rows rr + 1 and
+// rr + 2 in flight while row rr is compared: three slots of 8 VGPRs), one row
+// ahead at RT = 10; the loads are unconditional, past the tile's last row
+// they re-read it, so no load sits under a branch.
+template <int RT, class C>
+__device__ __forceinline__ void bsr_verify_rows(uint32_t (&acc)[RT][8], uint32_t rows, uint64_t ib, C chk,
+                                                uint32_t* words, uint32_t bit) {
+    if (rows == 0u) return;  // (wave-uniform; bsr_tiles never leaves a wave without rows)
+    // rows resident: the one compared and D - 1 in flight (one at RT = 10, where
+    // 80 accumulator registers leave the LDS form's 128 no room for the third)
+    constexpr int D = RT < 3 ? RT : RT < 10 ? 3 : 2;
+    // RT = 10: the next row's loads are issued after the current row's
+    // transpose (whose temporaries are dead by then), not before it, and the
+    // rows run straight-line -- a row past the tile is compared too, its
+    // result dropped -- so that the loads stay out of branches
+    constexpr bool LATE = RT >= 10;
+    u32x4 y0[D], y1[D];
+    auto fetch = [&](int slot, uint32_t rr) {
+        const uint8_t* p = chk(rr < rows ? rr : rows - 1u) + ib;
+        y0[slot] = load16(p);
+        y1[slot] = load16(p + 1024);
+    };
+#pragma unroll
+    for (int rr = 0; rr < D - 1; ++rr) fetch(rr, rr);
+    uint32_t mask = 0;
+    // (rows by compile-time index: the slot's registers are named in bsr_verify_pin)
+    bsr_static_for<0, RT>([&](auto rc) {
+        constexpr int rr = decltype(rc)::value, slot = rr % D, ahead = rr + D - 1;
+        if constexpr (LATE) {
+            u32x4 a = y0[slot], b = y1[slot];
+            bsr_verify_pin<slot>(a, b);
+            uint32_t v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+            transpose8(v);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (ahead < RT) fetch(ahead % D, ahead);
+            uint32_t d = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) d |= acc[rr][i] ^ v[i];
+            if (static_cast<uint32_t>(rr) < rows && __builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << rr;
+        } else {
+            if constexpr (ahead < RT) fetch(ahead % D, ahead);
+            if (static_cast<uint32_t>(rr) < rows) {  // wave-uniform
+                u32x4 a = y0[slot], b = y1[slot];
+                bsr_verify_pin<slot>(a, b);
+                uint32_t v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                transpose8(v);
+                uint32_t d = 0;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) d |= acc[rr][i] ^ v[i];
+                if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << rr;
+            }
+        }
+    });
+    if (mask != 0u) {  // wave-uniform; the rare path
+        // the lane number and the mask enter vector registers here: formed as
+        // loop invariants (the lane-0 flag, mismatch_or's 64-bit constants for
+        // a scalar mask) they were held across the walk and spilled at RT = 10
+        uint32_t l = 0u, m = mask;
+        asm volatile("" : "+v"(l), "+v"(m));
+        l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, l));  // the lane, formed here
+        if (l == 0u) mismatch_or(words, bit, m);
+    }
+}
+
+// The LDS-phase kernel.  Its verify form is this kernel instantiated on a
+// verify job (J = BsrVfyJob: matverify_bsr<RT,lds>; BsrVfyTblJob:
+// matverify_bsr<RT,lds,tbl>; CMB = false -- 2 or 4 waves for k <= 32): the
+// same walk, the epilogue comparing the rows with the stored check rows
+// instead of storing them (no store to block memory).  The mode hangs on the
+// job type so that the apply instantiations keep their symbols and their code.
 template <int RT, bool TBL, bool CMB, class J>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void matapply_bsr(const J job) {
+    constexpr bool VFY = std::is_same<J, BsrVfyJob>::value || std::is_same<J, BsrVfyTblJob>::value;
+    static_assert(!VFY || !CMB, "the verify forms share planes, not combinations");
     // [input][half][lane] planes, or (CMB) [input][7 x (4 dwords)][lane] + [2 dwords][lane] combinations
     extern __shared__ u32x4 bsr_planes[];
     constexpr uint32_t kIn = bsr_in_bytes<CMB>() / 16;  // u32x4 per input
@@ -2452,7 +2588,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
         if constexpr (PTR)
             return const_cast<uint8_t*>(kj->ptr[k + i]);
         else
-            return kj->out[i];
+            return const_cast<uint8_t*>(kj->out[i]);  // (VFY: the stored check rows, only read)
     };
     const uint64_t sz = job.sz;
     uint32_t s = blockIdx.x / job.cps, c = blockIdx.x - s * job.cps;
@@ -2471,7 +2607,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
         uint64_t off = static_cast<uint64_t>(c) * kBsrChunk;
         if (off > sz - kBsrChunk) off = sz - kBsrChunk;  // the last unit ends at sz (overlapping its neighbour)
         const uint64_t ib = stripe * job.in_sstride + off + lane * 16u;
-        const uint64_t ob = stripe * job.out_sstride + off + lane * 16u;
+        uint64_t ob = 0;
+        if constexpr (!VFY) ob = stripe * job.out_sstride + off + lane * 16u;
         uint32_t acc[RT][8];  // no zeroing: the wave's first input calls "set" routines (kBsrSetBase)
         // One input's calls: its planes (or, CMB, its 30 combinations) read from
         // LDS at b, its routine addresses in `cur`; the wave's first input
@@ -2731,13 +2868,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
             for (uint32_t ph = kp; ph < k; ph += kp) phase(BoolC<false>{}, ph);
         #endif
         }
+        if constexpr (VFY) {
+            (void)ob;
+            // the words' geometry is read here, after the walk (a fresh look at
+            // the arguments): held across it, it spilled at RT = 10
+            const KPtr<J> kv = kernarg_job<J>();
+            uint64_t so = stripe * kv->in_sstride + off;  // ib again, not held in vector registers meanwhile
+            asm volatile("" : "+s"(so));
+            bsr_verify_rows<RT>(acc, rows, so + lane * 16u, [&](uint32_t rr) { return out_ptr(r0 + rr); },
+                                kv->mismatch + static_cast<uint64_t>(stripe) * kv->words, kv->bit0 + r0);
+        } else {
 #pragma unroll
-        for (int rr = 0; rr < RT; ++rr) {
-            if (static_cast<uint32_t>(rr) < rows) {  // wave-uniform
-                transpose8(acc[rr]);
-                uint8_t* op = out_ptr(r0 + rr) + ob;
-                store16_out<true>(op, u32x4{acc[rr][0], acc[rr][1], acc[rr][2], acc[rr][3]});
-                store16_out<true>(op + 1024, u32x4{acc[rr][4], acc[rr][5], acc[rr][6], acc[rr][7]});
+            for (int rr = 0; rr < RT; ++rr) {
+                if (static_cast<uint32_t>(rr) < rows) {  // wave-uniform
+                    transpose8(acc[rr]);
+                    uint8_t* op = out_ptr(r0 + rr) + ob;
+                    store16_out<true>(op, u32x4{acc[rr][0], acc[rr][1], acc[rr][2], acc[rr][3]});
+                    store16_out<true>(op + 1024, u32x4{acc[rr][4], acc[rr][5], acc[rr][6], acc[rr][7]});
+                }
             }
         }
         c += job.gs_c;
@@ -2832,6 +2980,27 @@ __global__ __launch_bounds__(64) void matapply_bsr_solo(const BsrJob job) {
                 store16_out<true>(op + 1024, u32x4{acc[rr][4], acc[rr][5], acc[rr][6], acc[rr][7]});
             }
         }
+    }
+}
+
+// matverify_bsr<RT>: the one-wave form's walk (one tile: r <= 10), then the
+// verify epilogue instead of the stores.
+template <int RT>
+__global__ __launch_bounds__(64) void matverify_bsr_solo(const BsrVfyJob job) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t k = job.k, r = job.r;
+    const KPtr<BsrVfyJob> kj = kernarg_job<BsrVfyJob>();
+    const uint64_t sz = job.sz;
+    const uint64_t total = uint64_t(job.nstripes) * job.cps;
+    for (uint64_t u = blockIdx.x; u < total; u += gridDim.x) {
+        const uint32_t s = static_cast<uint32_t>(u / job.cps), c = static_cast<uint32_t>(u % job.cps);
+        uint64_t off = static_cast<uint64_t>(c) * kBsrChunk;
+        if (off > sz - kBsrChunk) off = sz - kBsrChunk;
+        const uint64_t ib = s * job.in_sstride + off + lane * 16u;
+        uint32_t acc[RT][8];  // no zeroing: the wave's first input calls "set" routines (kBsrSetBase)
+        bsr_walk<RT>(acc, k, ib, (CU64)kj->addr, [&](uint32_t j) { return kj->in[j]; });
+        bsr_verify_rows<RT>(acc, r, ib, [&](uint32_t rr) { return kj->out[rr]; },
+                            job.mismatch + static_cast<uint64_t>(s) * job.words, job.bit0);
     }
 }
 
@@ -4058,6 +4227,96 @@ hipError_t launch_bsr(const ApplySpec& a, hipStream_t stream) {
                       job);
 }
 
+// ---- matverify_bsr dispatch -------------------------------------------------------
+// launch_bsr's choices for the same (k, r, units) -- the same tiles, the same
+// walk order of the routine addresses, the same table cache -- with the verify
+// kernels: one wave (r <= 10), the LDS-phase form with the addresses in the
+// arguments, or in the device-side table past kBsrArgAddrs of them.
+struct BsrVfyVariant {
+    const void* fn_solo = nullptr;
+    const void* fn = nullptr;
+    const void* fn_tbl = nullptr;
+    char name_solo[24] = "";
+    char name[28] = "";
+    char name_tbl[32] = "";
+};
+BsrVfyVariant g_bsr_vfy[kBsrMaxRows + 1];
+std::once_flag g_bsr_vfy_once;
+
+template <int RT>
+void fill_bsr_vfy() {
+    g_bsr_vfy[RT].fn_solo = reinterpret_cast<const void*>(matverify_bsr_solo<RT>);
+    g_bsr_vfy[RT].fn = reinterpret_cast<const void*>(matapply_bsr<RT, false, false, BsrVfyJob>);
+    g_bsr_vfy[RT].fn_tbl = reinterpret_cast<const void*>(matapply_bsr<RT, true, false, BsrVfyTblJob>);
+    snprintf(g_bsr_vfy[RT].name_solo, sizeof g_bsr_vfy[RT].name_solo, "matverify_bsr<%d>", RT);
+    snprintf(g_bsr_vfy[RT].name, sizeof g_bsr_vfy[RT].name, "matverify_bsr<%d,lds>", RT);
+    snprintf(g_bsr_vfy[RT].name_tbl, sizeof g_bsr_vfy[RT].name_tbl, "matverify_bsr<%d,lds,tbl>", RT);
+    if constexpr (RT < kBsrMaxRows) fill_bsr_vfy<RT + 1>();
+}
+
+// The header every verify job shares, and the grid (launch_bsr's).
+template <class J>
+uint32_t bsr_vfy_header(J& job, const VerifySpec& v, uint64_t cps, uint64_t units) {
+    job.sz = v.sz;
+    job.in_sstride = v.sstride;
+    job.mismatch = v.mismatch;
+    job.nstripes = static_cast<uint32_t>(v.nstripes);
+    job.k = v.k;
+    job.r = v.r;
+    job.words = v.words;
+    job.bit0 = v.bit0;
+    const uint64_t cap = uint64_t(g_num_cu) * 1024;
+    const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
+    job.cps = static_cast<uint32_t>(cps);
+    job.gs_s = static_cast<uint32_t>(grid / cps);
+    job.gs_c = static_cast<uint32_t>(grid % cps);
+    return grid;
+}
+
+hipError_t launch_verify_bsr_one(const VerifySpec& v, hipStream_t stream) {
+    std::call_once(g_bsr_vfy_once, [] { fill_bsr_vfy<1>(); });
+    uint64_t base = 0;
+    if (bsr_routine_base(&base, stream) != hipSuccess) return hipErrorNotSupported;
+    const uint32_t k = v.k, r = v.r;
+    const uint64_t cps = (v.sz + kBsrChunk - 1) / kBsrChunk;
+    const uint64_t units = cps * v.nstripes;
+    if (units >= (1ull << 32) - (1ull << 24)) return hipErrorNotSupported;
+    uint32_t nw, rt;
+    bsr_tiles(r, units, &nw, &rt);
+    ApplySpec a{};  // what fill_bsr_addrs and the table cache read: the matrix
+    a.coef = v.coef;
+    a.coef_stride = v.coef_stride;
+    a.k = k;
+    a.r = r;
+    if (size_t(nw) * k * rt > static_cast<size_t>(kBsrArgAddrs)) {
+        if (nw == 1 || k + r > static_cast<uint32_t>(kBsrVfyPtrs)) return hipErrorNotSupported;
+        BsrVfyTblJob job;
+        BsrTblRef t;
+        hipError_t e = bsr_addr_table(a, stream, base, 1, nw, rt, 1, &t);
+        if (e != hipSuccess) return e == hipErrorInvalidValue ? hipErrorNotSupported : e;
+        const uint32_t grid = bsr_vfy_header(job, v, cps, units);
+        job.ngroups = 1;
+        job.pad_ = 0;
+        job.addr = t.dev;
+        for (uint32_t j = 0; j < k; ++j) job.ptr[j] = v.in[j];
+        for (uint32_t i = 0; i < r; ++i) job.ptr[k + i] = v.chk[i];
+        e = launch_job(g_bsr_vfy[rt].fn_tbl, grid, 64 * nw, bsr_lds_bytes(k, nw, false), stream, job);
+        const hipError_t te = bsr_table_done(t, stream);  // also when the launch failed: the upload is a reader
+        if (e != hipSuccess) return e;
+        t_last_kernel = g_bsr_vfy[rt].name_tbl;
+        return te;
+    }
+    BsrVfyJob job;
+    const uint32_t grid = bsr_vfy_header(job, v, cps, units);
+    for (uint32_t j = 0; j < k; ++j) job.in[j] = v.in[j];
+    for (uint32_t i = 0; i < r; ++i) job.out[i] = v.chk[i];
+    if (!fill_bsr_addrs(job.addr, a, base, 1, nw, rt, 1)) return hipErrorNotSupported;
+    const hipError_t e = nw == 1 ? launch_job(g_bsr_vfy[rt].fn_solo, grid, 64, 0, stream, job)
+                                 : launch_job(g_bsr_vfy[rt].fn, grid, 64 * nw, bsr_lds_bytes(k, nw, false), stream, job);
+    if (e == hipSuccess) t_last_kernel = nw == 1 ? g_bsr_vfy[rt].name_solo : g_bsr_vfy[rt].name;
+    return e;
+}
+
 // ---- matapply_mixed dispatch ------------------------------------------------------
 // Staging of a mixed call's pattern tables and host-side ids, per thread and
 // device.  The TableRing pattern -- a pinned host slot, its device twin filled
@@ -4453,6 +4712,21 @@ hipError_t launch_verify(const VerifySpec& v, hipStream_t stream) {
     t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
     t_signal_used = false;
     return g_verify_launch[v.k][v.r](v, stream);
+}
+
+bool verify_bsr_ok(uint32_t k, uint32_t r, uint64_t sz) {
+    return k > 4 && r >= 1 && bsr_shape_ok(k, r < kVerifyBsrRows ? r : kVerifyBsrRows, sz);
+}
+
+hipError_t launch_verify_bsr(const VerifySpec& v, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (!v.mismatch || v.coef_stride < v.k || v.nstripes == 0 || v.nstripes >= (1ull << 32) ||
+        uint64_t(v.bit0) + v.r > uint64_t(v.words) * 32)
+        return hipErrorInvalidValue;
+    if (v.r > kVerifyBsrRows || !verify_bsr_ok(v.k, v.r, v.sz)) return hipErrorNotSupported;
+    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
+    t_signal_used = false;
+    return launch_verify_bsr_one(v, stream);
 }
 
 hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream) {

@@ -135,6 +135,21 @@ struct VerifySpec {
 };
 hipError_t launch_verify(const VerifySpec& v, hipStream_t stream);
 
+// launch_verify_bsr (matverify_bsr<RT>, <RT,lds>, <RT,lds,tbl>; 4 < k <= 32,
+// r <= kVerifyBsrRows, sz >= 2048, generic_mode() == 2): the run-time-data
+// bit-sliced kernels' walk over the k basis blocks with the r computed rows
+// kept as bit-planes in registers and compared with the stored check blocks in
+// place -- every block read once, no scratch, nothing stored to block memory.
+// The kernel form, tiles and routine-address table are launch_apply's for the
+// same (k, r, units).  hipErrorNotSupported wherever that path would decline
+// (shape, no routine table on the device, a table past its cache slot, 2^32
+// units): the caller takes the two-step path.  verify_bsr_ok: the shape part
+// of that decision (no device needed); r past kVerifyBsrRows stands for a
+// first launch of kVerifyBsrRows rows.
+constexpr uint32_t kVerifyBsrRows = 40;
+bool verify_bsr_ok(uint32_t k, uint32_t r, uint64_t sz);
+hipError_t launch_verify_bsr(const VerifySpec& v, hipStream_t stream);
+
 struct DifferSpec {
     uint32_t r;
     const uint8_t* const* a;  // r row bases (stripe 0)
