@@ -22,6 +22,7 @@
 #include <mutex>
 #include <memory>
 #include <new>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <sys/mman.h>
@@ -447,6 +448,60 @@ const uint8_t* mapped_block(const void* p, size_t n) {
     if (static_cast<char*>(db) - static_cast<char*>(da) != last - static_cast<const char*>(p)) return nullptr;
     return static_cast<const uint8_t*>(da);
 }
+
+// ---- the memory and stream of a batched call ------------------------------------------
+// One block buffer of a batched call: [p, p + extent), `label` in messages.
+struct BatchBuf {
+    const gf* p;
+    size_t extent;
+    const char* label;
+};
+
+// What resolve_batch yields: the kernel-visible address of each buffer (device
+// memory as it is, page-locked host memory as the device maps it), the device
+// -- current while `guard` lives -- its per-thread context and the stream.
+struct BatchMem {
+    const gf* z[2] = {nullptr, nullptr};
+    int bdev[2] = {-1, -1};  // each buffer's device, -1: host memory
+    int dev = -1;
+    DevCtx* d = nullptr;
+    hipStream_t st = nullptr;
+    std::optional<DeviceGuard> guard;
+};
+
+// Resolves the buffers (at most two) of the call `fn`: one pointer query per
+// buffer, a second pair for a page-locked one.  Pageable host memory is
+// refused -- except with fn == nullptr (fec_encode_batch / fec_decode_batch,
+// which stage it): its z stays null.  `side` (may be null) names a further
+// pointer the caller found on device side_dev (-1: host memory), which must
+// not be another device than the blocks'.  no_capture (may be null): why the
+// call cannot be captured into a graph.
+int resolve_batch(BatchMem& m, const char* fn, const BatchBuf* bufs, int nbufs, const char* side, int side_dev,
+                  void* stream, unsigned flags, const char* no_capture) {
+    for (int i = 0; i < nbufs; ++i) m.bdev[i] = pointer_device(bufs[i].p);
+    for (int i = 0; i < nbufs; ++i) {
+        m.z[i] = m.bdev[i] >= 0 ? bufs[i].p : mapped_block(bufs[i].p, bufs[i].extent);
+        if (!m.z[i] && fn)
+            return set_status(FEC_EINVAL, "%s takes device or page-locked host memory: %s is pageable host memory, "
+                                          "which this call does not stage", fn, bufs[i].label);
+    }
+    if (m.bdev[0] >= 0 && m.bdev[1] >= 0 && m.bdev[0] != m.bdev[1])
+        return set_status(FEC_EINVAL, "batched entry points take memory on one device");
+    m.dev = m.bdev[0] >= 0 ? m.bdev[0] : m.bdev[1];
+    if (m.dev >= 0 && side_dev >= 0 && side_dev != m.dev)
+        return set_status(FEC_EINVAL, "%s lives on device %d, the blocks on device %d", side, side_dev, m.dev);
+    if (m.dev < 0) m.dev = side_dev;
+    if (m.dev < 0 && hipGetDevice(&m.dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
+    m.guard.emplace(m.dev);
+    if (dev_ctx(m.dev, &m.d)) return t_status;
+    m.st = (flags & FEC_FLAG_LIBRARY_STREAM) ? m.d->stream : static_cast<hipStream_t>(stream);
+    if (no_capture && stream_capturing(m.st))
+        return set_status(FEC_EINVAL, "%s: the stream is being captured into a graph (%s)", fn, no_capture);
+    return FEC_OK;
+}
+
+constexpr char kCaptureTables[] = "the pattern tables are uploaded when the call is made";
+constexpr char kCaptureMemory[] = "the call uses memory the library owns and reuses";
 
 // Bytes of every host block per staged chunk: ZFEC_HIP_STAGE_CHUNK, else
 // at most a quarter of the block (so that copy-in, kernel and copy-out of
@@ -1284,58 +1339,28 @@ int run_batch(const fec_t* code, const uint8_t* coef, unsigned r, const gf* src,
     if (!gpu_available()) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
     if (!src || !dst) return set_status(FEC_EINVAL, "NULL buffer");
     // one pointer query per side: device memory (its device), or host memory
-    const int sdev = pointer_device(src), ddev0 = pointer_device(dst);
+    const BatchBuf bufs[2] = {{src, (nstripes - 1) * sss + (k - 1) * sbs + sz, "src"},
+                              {dst, (nstripes - 1) * dss + (r - 1) * dbs + sz, "dst"}};
+    BatchMem m;
+    if (resolve_batch(m, nullptr, bufs, 2, nullptr, -1, stream, flags, nullptr)) return t_status;
     // pageable host memory on either side: staged through pinned slots
     // (synchronous whatever the flags; FEC_FLAG_ROW_PADDING does not apply)
-    if (sz && nstripes && r && (sdev < 0 || ddev0 < 0)) {
-        const size_t src_ext = (nstripes - 1) * sss + (k - 1) * sbs + sz;
-        const size_t dst_ext = (nstripes - 1) * dss + (r - 1) * dbs + sz;
-        const uint8_t* zs = sdev >= 0 ? src : mapped_block(src, src_ext);
-        const uint8_t* zd = ddev0 >= 0 ? dst : mapped_block(dst, dst_ext);
-        if (!zs || !zd) {
-            if (sdev >= 0 && ddev0 >= 0 && sdev != ddev0)
-                return set_status(FEC_EINVAL, "batched entry points take memory on one device");
-            int dev = sdev >= 0 ? sdev : ddev0;
-            if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
-            DeviceGuard guard(dev);
-            DevCtx* d = nullptr;
-            if (dev_ctx(dev, &d)) return t_status;
-            hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
-            return run_batch_staged(*d, coef, k, r, zs ? zs : src, sbs, sss, !zs, zd ? const_cast<gf*>(zd) : dst, dbs,
-                                    dss, !zd, sz, nstripes, st);
-        }
-    }
+    if (sz && nstripes && r && (!m.z[0] || !m.z[1]))
+        return run_batch_staged(*m.d, coef, k, r, m.z[0] ? m.z[0] : src, sbs, sss, !m.z[0],
+                                m.z[1] ? const_cast<gf*>(m.z[1]) : dst, dbs, dss, !m.z[1], sz, nstripes, m.st);
     batch_geometry(k, r, sbs, sss, dbs, dss, flags, sz, nstripes);
-    // device memory on one device, or page-locked host memory (zero-copy)
-    const size_t src_extent = (nstripes - 1) * sss + (k - 1) * sbs + sz;
-    const size_t dst_extent = (nstripes - 1) * dss + (r - 1) * dbs + sz;
-    int dev = sdev;
-    const int ddev = ddev0;
-    if (dev < 0) {
-        const uint8_t* z = mapped_block(src, src_extent);
-        if (!z) return set_status(FEC_EINVAL, "batched entry points take device or page-locked host memory");
-        src = z;
-    }
-    if (ddev < 0) {
-        const uint8_t* z = mapped_block(dst, dst_extent);
-        if (!z) return set_status(FEC_EINVAL, "batched entry points take device or page-locked host memory");
-        dst = const_cast<gf*>(z);
-    }
-    if (dev < 0) dev = ddev;
-    if (dev >= 0 && ddev >= 0 && ddev != dev)
-        return set_status(FEC_EINVAL, "batched entry points take memory on one device");
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
-    DeviceGuard guard(dev);
-    DevCtx* d = nullptr;
-    if (dev_ctx(dev, &d)) return t_status;
-    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
+    // page-locked host memory (zero-copy) has to cover the rows as the geometry lengthened them
+    if (m.bdev[0] < 0 && !(m.z[0] = mapped_block(src, (nstripes - 1) * sss + (k - 1) * sbs + sz)))
+        return set_status(FEC_EINVAL, "batched entry points take device or page-locked host memory");
+    if (m.bdev[1] < 0 && !(m.z[1] = mapped_block(dst, (nstripes - 1) * dss + (r - 1) * dbs + sz)))
+        return set_status(FEC_EINVAL, "batched entry points take device or page-locked host memory");
     const uint8_t* in[kMaxWideIn];
     uint8_t* out[kMaxWideIn];
-    for (unsigned j = 0; j < k; ++j) in[j] = src + j * sbs;
-    for (unsigned i = 0; i < r; ++i) out[i] = dst + i * dbs;
-    if (apply_matrix(coef, k, r, in, out, sz, nstripes, sss, dss, st)) return t_status;
+    for (unsigned j = 0; j < k; ++j) in[j] = m.z[0] + j * sbs;
+    for (unsigned i = 0; i < r; ++i) out[i] = const_cast<gf*>(m.z[1]) + i * dbs;
+    if (apply_matrix(coef, k, r, in, out, sz, nstripes, sss, dss, m.st)) return t_status;
     if (!(flags & FEC_FLAG_ASYNC)) {
-        hipError_t e = hipStreamSynchronize(st);
+        hipError_t e = hipStreamSynchronize(m.st);
         if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     }
     return set_status(FEC_OK);
@@ -1394,36 +1419,75 @@ int mixed_rows(const fec_t* code, const unsigned* pat, uint8_t* rows) {
     return FEC_OK;
 }
 
+// The pattern and id checks of the pattern-per-stripe calls (fec_decode_batch_mixed,
+// fec_repair_batch), which need no GPU: the number of patterns, the call's own
+// checks of them (check_each), then the ids.  Ids in host memory are checked
+// here; ids in device memory (*idev >= 0) cannot be -- the kernels leave a
+// stripe with an id >= npatterns unwritten.  pattern_of may be null (repair).
+template <class F>
+int check_patterns_and_ids(size_t npatterns, size_t nstripes, const unsigned* pattern_of, int* idev, F check_each) {
+    if (npatterns == 0 && nstripes > 0)
+        return set_status(FEC_EINVAL, "npatterns is 0: stripe 0 of %zu has no pattern", nstripes);
+    if (npatterns > kMixedMaxPatterns)
+        return set_status(FEC_EINVAL, "%zu patterns: a call takes at most %u", npatterns, unsigned(kMixedMaxPatterns));
+    if (check_each()) return t_status;
+    const int ngpu = gpu_available();
+    *idev = ngpu && pattern_of ? pointer_device(pattern_of) : -1;
+    if (pattern_of && *idev < 0)
+        for (size_t s = 0; s < nstripes; ++s)
+            if (pattern_of[s] >= npatterns)
+                return set_status(FEC_EINVAL, "stripe %zu: pattern id %u out of range (npatterns = %zu)", s,
+                                  pattern_of[s], npatterns);
+    if (!ngpu) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    return FEC_OK;
+}
+
+// The k > kMixedMaxK fallback of those calls: maximal runs of consecutive
+// stripes with one id.  Ids in device memory come to the host first; a run
+// whose id names no pattern is skipped (device ids are not checked: such
+// stripes stay unwritten, as on the kernels).  make(id, entry) builds the id's
+// rows, once per call; apply(entry, s0, s1) runs stripes [s0, s1).
+template <class Entry, class Make, class Apply>
+int for_each_id_run(const unsigned* pattern_of, int idev, size_t nstripes, size_t npatterns, hipStream_t st, Make make,
+                    Apply apply) {
+    thread_local std::vector<unsigned> hids;
+    const unsigned* ids = pattern_of;
+    if (idev >= 0) {
+        hipError_t e;
+        hids.resize(nstripes);
+        if ((e = hipMemcpyAsync(hids.data(), pattern_of, nstripes * sizeof(unsigned), hipMemcpyDeviceToHost, st)) !=
+            hipSuccess)
+            return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+        ids = hids.data();
+    }
+    std::unordered_map<unsigned, Entry> cache;
+    for (size_t s0 = 0; s0 < nstripes;) {
+        size_t s1 = s0 + 1;
+        while (s1 < nstripes && ids[s1] == ids[s0]) ++s1;
+        if (ids[s0] < npatterns) {
+            const auto ins = cache.try_emplace(ids[s0]);
+            if (ins.second && make(ids[s0], ins.first->second)) return t_status;
+            if (apply(ins.first->second, s0, s1)) return t_status;
+        }
+        s0 = s1;
+    }
+    return FEC_OK;
+}
+
 int run_mixed(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst, size_t dbs, size_t dss,
               const unsigned* patterns, size_t npatterns, const unsigned* pattern_of, int idev, size_t sz,
               size_t nstripes, void* stream, unsigned flags) {
     const unsigned k = code->k;
     // device memory on one device, or page-locked host memory (read and written in place)
-    const size_t src_extent = (nstripes - 1) * sss + (k - 1) * sbs + sz;
-    const size_t dst_extent = (nstripes - 1) * dss + (k - 1) * dbs + sz;
-    const int sdev = pointer_device(src), ddev = pointer_device(dst);
-    const gf* zsrc = src;
-    gf* zdst = dst;
-    if (sdev < 0 && !(zsrc = mapped_block(src, src_extent)))
-        return set_status(FEC_EINVAL, "fec_decode_batch_mixed takes device or page-locked host memory: src is "
-                                      "pageable host memory, which this call does not stage");
-    if (ddev < 0 && !(zdst = const_cast<gf*>(mapped_block(dst, dst_extent))))
-        return set_status(FEC_EINVAL, "fec_decode_batch_mixed takes device or page-locked host memory: dst is "
-                                      "pageable host memory, which this call does not stage");
-    if (sdev >= 0 && ddev >= 0 && sdev != ddev)
-        return set_status(FEC_EINVAL, "batched entry points take memory on one device");
-    int dev = sdev >= 0 ? sdev : ddev;
-    if (dev < 0) dev = idev;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
-    if (idev >= 0 && idev != dev)
-        return set_status(FEC_EINVAL, "pattern_of lives on device %d, the blocks on device %d", idev, dev);
-    DeviceGuard guard(dev);
-    DevCtx* d = nullptr;
-    if (dev_ctx(dev, &d)) return t_status;
-    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
-    if (stream_capturing(st))
-        return set_status(FEC_EINVAL, "fec_decode_batch_mixed: the stream is being captured into a graph (the "
-                                      "pattern tables are uploaded when the call is made)");
+    const BatchBuf bufs[2] = {{src, (nstripes - 1) * sss + (k - 1) * sbs + sz, "src"},
+                              {dst, (nstripes - 1) * dss + (k - 1) * dbs + sz, "dst"}};
+    BatchMem mem;
+    if (resolve_batch(mem, "fec_decode_batch_mixed", bufs, 2, "pattern_of", idev, stream, flags, kCaptureTables))
+        return t_status;
+    const gf* const zsrc = mem.z[0];
+    gf* const zdst = const_cast<gf*>(mem.z[1]);
+    hipStream_t st = mem.st;
     hipError_t e;
     if (k <= kMixedMaxK) {
         thread_local std::vector<uint8_t> rows;
@@ -1451,36 +1515,19 @@ int run_mixed(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst,
         ++t_launches;
         if ((e = launch_mixed(m, st)) != hipSuccess) return hip_fail(e, "launch_mixed");
     } else {
-        // codes past the register shapes: maximal runs of consecutive stripes
-        // with one id, each through the shared-pattern batched path
-        thread_local std::vector<unsigned> hids;
-        const unsigned* ids = pattern_of;
-        if (idev >= 0) {
-            hids.resize(nstripes);
-            if ((e = hipMemcpyAsync(hids.data(), pattern_of, nstripes * sizeof(unsigned), hipMemcpyDeviceToHost,
-                                    st)) != hipSuccess)
-                return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-            ids = hids.data();
-        }
-        std::unordered_map<unsigned, std::vector<uint8_t>> rows_of;
+        // codes past the register shapes: each run through the shared-pattern batched path
         const unsigned jf = (flags & FEC_FLAG_LIBRARY_STREAM) | FEC_FLAG_ASYNC;
-        for (size_t s0 = 0; s0 < nstripes;) {
-            size_t s1 = s0 + 1;
-            while (s1 < nstripes && ids[s1] == ids[s0]) ++s1;
-            const unsigned id = ids[s0];
-            if (id < npatterns) {  // (device ids are not checked: such stripes stay unwritten, as on the kernel)
-                std::vector<uint8_t>& rows = rows_of[id];
-                if (rows.empty()) {
+        if (for_each_id_run<std::vector<uint8_t>>(
+                pattern_of, idev, nstripes, npatterns, st,
+                [&](unsigned id, std::vector<uint8_t>& rows) {
                     rows.resize(size_t(k) * k);
-                    if (mixed_rows(code, patterns + size_t(id) * k, rows.data())) return t_status;
-                }
-                if (run_batch(code, rows.data(), k, src + s0 * sss, sbs, sss, dst + s0 * dss, dbs, dss, sz, s1 - s0,
-                              stream, jf))
-                    return t_status;
-            }
-            s0 = s1;
-        }
+                    return mixed_rows(code, patterns + size_t(id) * k, rows.data());
+                },
+                [&](const std::vector<uint8_t>& rows, size_t s0, size_t s1) {
+                    return run_batch(code, rows.data(), k, src + s0 * sss, sbs, sss, dst + s0 * dss, dbs, dss, sz,
+                                     s1 - s0, stream, jf);
+                }))
+            return t_status;
     }
     if (!(flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "hipStreamSynchronize");
@@ -1509,22 +1556,13 @@ FEC_API int fec_decode_batch_mixed(const fec_t* code, const gf* src, size_t src_
     if (!src || !dst) return set_status(FEC_EINVAL, "NULL buffer");
     if (!patterns) return set_status(FEC_EINVAL, "patterns is NULL");
     if (!pattern_of) return set_status(FEC_EINVAL, "pattern_of is NULL");
-    if (npatterns == 0 && nstripes > 0)
-        return set_status(FEC_EINVAL, "npatterns is 0: stripe 0 of %zu has no pattern", nstripes);
-    if (npatterns > kMixedMaxPatterns)
-        return set_status(FEC_EINVAL, "%zu patterns: a call takes at most %u", npatterns, unsigned(kMixedMaxPatterns));
-    for (size_t p = 0; p < npatterns; ++p)
-        if (check_pattern(code, patterns + p * code->k, p)) return t_status;
-    // ids in host memory are checked here; ids in device memory cannot be (the
-    // kernel leaves a stripe with an id >= npatterns unwritten)
-    const int ngpu = gpu_available();
-    const int idev = ngpu ? pointer_device(pattern_of) : -1;
-    if (idev < 0)
-        for (size_t s = 0; s < nstripes; ++s)
-            if (pattern_of[s] >= npatterns)
-                return set_status(FEC_EINVAL, "stripe %zu: pattern id %u out of range (npatterns = %zu)", s,
-                                  pattern_of[s], npatterns);
-    if (!ngpu) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    int idev = -1;
+    if (check_patterns_and_ids(npatterns, nstripes, pattern_of, &idev, [&] {
+            for (size_t p = 0; p < npatterns; ++p)
+                if (check_pattern(code, patterns + p * code->k, p)) return t_status;
+            return int(FEC_OK);
+        }))
+        return t_status;
     if (sz == 0 || nstripes == 0) return set_status(FEC_OK);
     return guarded([&] {
         return run_mixed(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,
@@ -1549,6 +1587,22 @@ int check_verify_nums(const fec_t* code, const unsigned* nums, size_t nb) {
         if (seen[nums[j]]) return set_status(FEC_EINVAL, "duplicate block number %u", nums[j]);
         seen[nums[j]] = 1;
     }
+    return FEC_OK;
+}
+
+// The argument checks of the verify / locate / correct family, none of which
+// needs a GPU.  A *_batch call names its block buffer (`blocks`, "src" or
+// "blocks") and needs a GPU in the end; a *_rows call passes blocks_name null.
+// `out` is the call's result pointer (rows, mismatch, culprit).
+int check_verify_call(const fec_t* code, const void* blocks, const char* blocks_name, const unsigned* nums, size_t nb,
+                      const void* out, const char* out_name) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (blocks_name && !blocks) return set_status(FEC_EINVAL, "NULL buffer: %s", blocks_name);
+    if (!nums) return set_status(FEC_EINVAL, "block_nums is NULL");
+    if (!out) return set_status(FEC_EINVAL, "%s is NULL", out_name);
+    if (check_verify_nums(code, nums, nb)) return t_status;
+    if (blocks_name && !gpu_available())
+        return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
     return FEC_OK;
 }
 
@@ -1590,31 +1644,51 @@ int ensure_verify_buf(DevCtx& d, void*& buf, size_t& cap, size_t bytes) {
     return FEC_OK;
 }
 
-// k <= 4: matverify_reg, at most 8 check rows per launch, the bit index advancing.
-int verify_reg_path(const uint8_t* P, unsigned k, unsigned c, const gf* src, size_t sbs, size_t sss, size_t sz,
-                    size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st) {
-    const uint8_t* in[4];
-    const uint8_t* chk[8];
-    for (unsigned j = 0; j < k; ++j) in[j] = src + j * sbs;
-    for (unsigned g0 = 0; g0 < c; g0 += 8) {
-        const unsigned rg = std::min(8u, c - g0);
-        for (unsigned i = 0; i < rg; ++i) chk[i] = src + size_t(k + g0 + i) * sbs;
+// The blocks and words of a verify / locate call, as the kernels see them.
+struct VerifyArgs {
+    const uint8_t* P;  // c x k
+    unsigned k, c;
+    const gf* src;
+    size_t sbs, sss, sz, nstripes;
+    uint32_t* mask;
+    unsigned words;
+    hipStream_t st;
+};
+
+// The c check rows against the k basis blocks in launches of at most `rows`
+// rows, the bit index advancing: launch(spec, stream), named `what` in a
+// failure's message.  declined (may be null): a launch may find no kernel on
+// this device (hipErrorNotSupported); *declined is set, whatever earlier
+// launches OR-ed in stays valid, and the caller runs the two-step path.
+template <class Launch>
+int verify_groups(const VerifyArgs& a, unsigned rows, Launch launch, const char* what, bool* declined = nullptr) {
+    const uint8_t* in[kMaxIn];
+    const uint8_t* chk[kVerifyBsrRows];
+    for (unsigned j = 0; j < a.k; ++j) in[j] = a.src + j * a.sbs;
+    for (unsigned g0 = 0; g0 < a.c; g0 += rows) {
+        const unsigned rg = std::min(rows, a.c - g0);
+        for (unsigned i = 0; i < rg; ++i) chk[i] = a.src + size_t(a.k + g0 + i) * a.sbs;
         VerifySpec v;
-        v.coef = P + size_t(g0) * k;
-        v.coef_stride = k;
-        v.k = k;
+        v.coef = a.P + size_t(g0) * a.k;
+        v.coef_stride = a.k;
+        v.k = a.k;
         v.r = rg;
         v.in = in;
         v.chk = chk;
-        v.sz = sz;
-        v.nstripes = nstripes;
-        v.sstride = sss;
-        v.mismatch = mask;
-        v.words = words;
+        v.sz = a.sz;
+        v.nstripes = a.nstripes;
+        v.sstride = a.sss;
+        v.mismatch = a.mask;
+        v.words = a.words;
         v.bit0 = g0;
-        ++t_launches;
-        const hipError_t e = launch_verify(v, st);
-        if (e != hipSuccess) return hip_fail(e, "launch_verify");
+        const hipError_t e = launch(v, a.st);
+        if (declined && e == hipErrorNotSupported) {
+            (void)hipGetLastError();
+            *declined = true;
+            return FEC_OK;
+        }
+        ++t_launches;  // every launch made, failed or not
+        if (e != hipSuccess) return hip_fail(e, what);
     }
     return FEC_OK;
 }
@@ -1631,9 +1705,8 @@ struct LocateRows {
     const uint32_t* qtab;  // device memory
     unsigned xbit;
 };
-int verify_scratch_path(DevCtx& d, const uint8_t* P, unsigned k, unsigned c, const gf* src, size_t sbs, size_t sss,
-                        size_t sz, size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st,
-                        const LocateRows* loc = nullptr) {
+int verify_scratch_path(DevCtx& d, const VerifyArgs& a, const LocateRows* loc = nullptr) {
+    const auto [P, k, c, src, sbs, sss, sz, nstripes, mask, words, st] = a;
     const size_t cap = config().verify_scratch;
     size_t len = sz, run = 1;
     if (size_t(c) * align_up(sz, 128) <= cap)
@@ -1699,40 +1772,37 @@ bool verify_fused_ok(unsigned k, unsigned c, size_t sz, size_t nstripes) {
     return units >= config().verify_fused_min && units < (1ull << 32) - (1ull << 24);
 }
 
-// *declined: a launch had no kernel on this device (hipErrorNotSupported);
-// whatever earlier launches OR-ed in stays valid, the caller runs the two-step path.
-int verify_fused_path(const uint8_t* P, unsigned k, unsigned c, const gf* src, size_t sbs, size_t sss, size_t sz,
-                      size_t nstripes, uint32_t* mask, unsigned words, hipStream_t st, bool* declined) {
-    const uint8_t* in[kMaxIn];
-    const uint8_t* chk[kVerifyBsrRows];
-    for (unsigned j = 0; j < k; ++j) in[j] = src + j * sbs;
-    for (unsigned g0 = 0; g0 < c; g0 += kVerifyBsrRows) {
-        const unsigned rg = std::min(kVerifyBsrRows, c - g0);
-        for (unsigned i = 0; i < rg; ++i) chk[i] = src + size_t(k + g0 + i) * sbs;
-        VerifySpec v;
-        v.coef = P + size_t(g0) * k;
-        v.coef_stride = k;
-        v.k = k;
-        v.r = rg;
-        v.in = in;
-        v.chk = chk;
-        v.sz = sz;
-        v.nstripes = nstripes;
-        v.sstride = sss;
-        v.mismatch = mask;
-        v.words = words;
-        v.bit0 = g0;
-        const hipError_t e = launch_verify_bsr(v, st);
-        if (e == hipErrorNotSupported) {
-            (void)hipGetLastError();
-            *declined = true;
-            return FEC_OK;
-        }
-        ++t_launches;
-        if (e != hipSuccess) return hip_fail(e, "launch_verify_bsr");
+// The order of the thread's shared verify buffers (vbuf, vmask) among calls on
+// any streams.  acquire(): `st` waits, on the GPU, for the call that used them
+// last.  release(), once this call has enqueued all it will: whatever was
+// enqueued uses the buffers, so they stay busy whatever happened; it does
+// nothing for a call that never acquired them.
+struct VerifyOrder {
+    DevCtx& d;
+    hipStream_t st;
+    bool held = false;
+    int init() {
+        hipError_t e;
+        if (!d.ev_verify && (e = hipEventCreateWithFlags(&d.ev_verify, hipEventDisableTiming)) != hipSuccess)
+            return hip_fail(e, "hipEventCreateWithFlags");
+        return FEC_OK;
     }
-    return FEC_OK;
-}
+    int acquire() {
+        hipError_t e;
+        if (held) return FEC_OK;
+        held = true;
+        if (d.verify_busy && (e = hipStreamWaitEvent(st, d.ev_verify, 0)) != hipSuccess)
+            return hip_fail(e, "hipStreamWaitEvent");
+        return FEC_OK;
+    }
+    void release() {
+        if (!held) return;
+        if (hipEventRecord(d.ev_verify, st) == hipSuccess)
+            d.verify_busy = true;
+        else
+            (void)hipStreamSynchronize(st);
+    }
+};
 
 int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const unsigned* nums, size_t nb, size_t sz,
                size_t nstripes, unsigned* mismatch, void* stream, unsigned flags) {
@@ -1740,39 +1810,21 @@ int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
     const size_t mask_bytes = nstripes * words * sizeof(uint32_t);
     const int mdev = pointer_device(mismatch);
-    int dev = -1;
-    bool src_dev = false;
-    const gf* zsrc = src;
-    if (sz) {
-        // device memory on one device, or page-locked host memory (read in place)
-        const size_t extent = (nstripes - 1) * sss + (nb - 1) * sbs + sz;
-        dev = pointer_device(src);
-        src_dev = dev >= 0;
-        if (dev < 0 && !(zsrc = mapped_block(src, extent)))
-            return set_status(FEC_EINVAL, "fec_verify_batch takes device or page-locked host memory: src is pageable "
-                                          "host memory, which this call does not stage");
-        if (dev >= 0 && mdev >= 0 && mdev != dev)
-            return set_status(FEC_EINVAL, "mismatch lives on device %d, the blocks on device %d", mdev, dev);
-    }
-    if (dev < 0) dev = mdev;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
-    DeviceGuard guard(dev);
-    DevCtx* d = nullptr;
-    if (dev_ctx(dev, &d)) return t_status;
-    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
-    if (stream_capturing(st))
-        return set_status(FEC_EINVAL, "fec_verify_batch: the stream is being captured into a graph (the call uses "
-                                      "memory the library owns and reuses)");
+    // device memory on one device, or page-locked host memory (read in place); sz == 0 reads no block
+    const BatchBuf buf = {src, (nstripes - 1) * sss + (nb - 1) * sbs + sz, "src"};
+    BatchMem mem;
+    if (resolve_batch(mem, "fec_verify_batch", &buf, sz ? 1 : 0, "mismatch", mdev, stream, flags, kCaptureMemory))
+        return t_status;
+    DevCtx* const d = mem.d;
+    hipStream_t st = mem.st;
     hipError_t e;
-    if (!d->ev_verify && (e = hipEventCreateWithFlags(&d->ev_verify, hipEventDisableTiming)) != hipSuccess)
-        return hip_fail(e, "hipEventCreateWithFlags");
+    VerifyOrder order{*d, st};
+    if (order.init()) return t_status;
     // the thread's scratch and mask buffer: wait (on the GPU) for the call that used them last
     // (the fused kernels read page-locked host blocks no better than the two
     // steps do -- both move k + c over PCIe -- so those keep the two-step path)
-    const bool reg = k <= 4, fused = !reg && sz && src_dev && verify_fused_ok(k, c, sz, nstripes);
-    bool shared = mdev < 0 || (!reg && !fused && sz);
-    if (shared && d->verify_busy && (e = hipStreamWaitEvent(st, d->ev_verify, 0)) != hipSuccess)
-        return hip_fail(e, "hipStreamWaitEvent");
+    const bool reg = k <= 4, fused = !reg && sz && mem.bdev[0] >= 0 && verify_fused_ok(k, c, sz, nstripes);
+    if ((mdev < 0 || (!reg && !fused && sz)) && order.acquire()) return t_status;
     // mismatch in host memory: the kernels' device-scope atomics must not aim
     // at host memory over PCIe, so the words are gathered in device memory
     if (mdev < 0 && ensure_verify_buf(*d, d->vmask, d->vmask_cap, mask_bytes)) return t_status;
@@ -1783,29 +1835,19 @@ int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
         thread_local std::vector<uint8_t> P;
         P.resize(size_t(c) * k);
         rc = verify_rows(code, nums, nb, P.data());
+        const VerifyArgs a = {P.data(), k, c, mem.z[0], sbs, sss, sz, nstripes, mask, words, st};
         bool two_step = !reg && !fused;
         if (!rc && fused) {
-            rc = verify_fused_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st, &two_step);
+            rc = verify_groups(a, kVerifyBsrRows, launch_verify_bsr, "launch_verify_bsr", &two_step);
             // declined: the scratch after all, ordered after its last user
-            if (!rc && two_step && !shared) {
-                shared = true;
-                if (d->verify_busy && (e = hipStreamWaitEvent(st, d->ev_verify, 0)) != hipSuccess)
-                    rc = hip_fail(e, "hipStreamWaitEvent");
-            }
+            if (!rc && two_step) rc = order.acquire();
         }
-        if (!rc && reg) rc = verify_reg_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st);
-        if (!rc && two_step)
-            rc = verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, mask, words, st);
+        if (!rc && reg) rc = verify_groups(a, 8, launch_verify, "launch_verify");  // matverify_reg
+        if (!rc && two_step) rc = verify_scratch_path(*d, a);
     }
     if (!rc && mdev < 0 && (e = hipMemcpyAsync(mismatch, mask, mask_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
         rc = hip_fail(e, "hipMemcpyAsync D2H (mismatch)");
-    // whatever was enqueued uses the shared buffers: they stay busy whatever happened
-    if (shared) {
-        if (hipEventRecord(d->ev_verify, st) == hipSuccess)
-            d->verify_busy = true;
-        else
-            (void)hipStreamSynchronize(st);
-    }
+    order.release();
     if (rc) return rc;
     if ((mdev < 0 || !(flags & FEC_FLAG_ASYNC)) && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "hipStreamSynchronize");
@@ -1814,10 +1856,7 @@ int run_verify(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
 }  // namespace
 
 FEC_API int fec_verify_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
-    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
-    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
-    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
-    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+    if (check_verify_call(code, nullptr, nullptr, block_nums, num_block_nums, rows, "rows")) return t_status;
     return guarded([&] {
         if (verify_rows(code, block_nums, num_block_nums, rows)) return t_status;
         return set_status(FEC_OK);
@@ -1828,12 +1867,7 @@ FEC_API int fec_verify_batch(const fec_t* code, const gf* src, size_t src_block_
                              const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
                              unsigned* mismatch, void* stream, unsigned flags) {
     // every check that needs no GPU comes first
-    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
-    if (!src) return set_status(FEC_EINVAL, "NULL buffer: src");
-    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
-    if (!mismatch) return set_status(FEC_EINVAL, "mismatch is NULL");
-    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
-    if (!gpu_available()) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (check_verify_call(code, src, "src", block_nums, num_block_nums, mismatch, "mismatch")) return t_status;
     if (nstripes == 0) return set_status(FEC_OK);
     return guarded([&] {
         return run_verify(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
@@ -1881,33 +1915,17 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
     const size_t work_bytes = nstripes * words * sizeof(uint32_t), out_bytes = nstripes * sizeof(uint32_t);
     const int cdev = pointer_device(culprit);
-    int dev = -1;
-    const gf* zsrc = src;
-    if (sz) {
-        // device memory on one device, or page-locked host memory (read in place)
-        const size_t extent = (nstripes - 1) * sss + (nb - 1) * sbs + sz;
-        dev = pointer_device(src);
-        if (dev < 0 && !(zsrc = mapped_block(src, extent)))
-            return set_status(FEC_EINVAL, "%s takes device or page-locked host memory: %s is pageable "
-                                          "host memory, which this call does not stage", fn, heal ? "blocks" : "src");
-        if (dev >= 0 && cdev >= 0 && cdev != dev)
-            return set_status(FEC_EINVAL, "culprit lives on device %d, the blocks on device %d", cdev, dev);
-    }
-    if (dev < 0) dev = cdev;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
-    DeviceGuard guard(dev);
-    DevCtx* d = nullptr;
-    if (dev_ctx(dev, &d)) return t_status;
-    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
-    if (stream_capturing(st))
-        return set_status(FEC_EINVAL, "%s: the stream is being captured into a graph (the call uses "
-                                      "memory the library owns and reuses)", fn);
+    // device memory on one device, or page-locked host memory (read in place); sz == 0 reads no block
+    const BatchBuf buf = {src, (nstripes - 1) * sss + (nb - 1) * sbs + sz, heal ? "blocks" : "src"};
+    BatchMem mem;
+    if (resolve_batch(mem, fn, &buf, sz ? 1 : 0, "culprit", cdev, stream, flags, kCaptureMemory)) return t_status;
+    DevCtx* const d = mem.d;
+    const gf* const zsrc = mem.z[0];
+    hipStream_t st = mem.st;
     hipError_t e;
-    if (!d->ev_verify && (e = hipEventCreateWithFlags(&d->ev_verify, hipEventDisableTiming)) != hipSuccess)
-        return hip_fail(e, "hipEventCreateWithFlags");
     // the thread's working words (and scratch): wait (on the GPU) for the call that used them last
-    if (d->verify_busy && (e = hipStreamWaitEvent(st, d->ev_verify, 0)) != hipSuccess)
-        return hip_fail(e, "hipStreamWaitEvent");
+    VerifyOrder order{*d, st};
+    if (order.init() || order.acquire()) return t_status;
     if (ensure_verify_buf(*d, d->vmask, d->vmask_cap, work_bytes + (cdev < 0 ? out_bytes : 0))) return t_status;
     uint32_t* const bits = static_cast<uint32_t*>(d->vmask);
     uint32_t* const out = cdev < 0 ? bits + nstripes * words : culprit;
@@ -1919,31 +1937,16 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
         P.resize(size_t(c) * k);
         Q.resize(size_t(c - 1) * k);
         rc = verify_rows(code, nums, nb, P.data());
+        const VerifyArgs a = {P.data(), k, c, zsrc, sbs, sss, sz, nstripes, bits, words, st};
         if (!rc && c == 1) {
             // one check cannot tell: the verify kernels' bit, then UNKNOWN
-            rc = k <= 4 ? verify_reg_path(P.data(), k, c, zsrc, sbs, sss, sz, nstripes, bits, words, st)
-                        : verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, bits, words, st);
+            rc = k <= 4 ? verify_groups(a, 8, launch_verify, "launch_verify") : verify_scratch_path(*d, a);
         } else if (!rc && k <= 4 && c <= 8) {
+            // matlocate_reg: all c checks in one launch
             locate_rows(P.data(), k, c, Q.data());
-            const uint8_t* in[4];
-            const uint8_t* chk[8];
-            for (unsigned j = 0; j < k; ++j) in[j] = zsrc + j * sbs;
-            for (unsigned i = 0; i < c; ++i) chk[i] = zsrc + size_t(k + i) * sbs;
-            VerifySpec v;
-            v.coef = P.data();
-            v.coef_stride = k;
-            v.k = k;
-            v.r = c;
-            v.in = in;
-            v.chk = chk;
-            v.sz = sz;
-            v.nstripes = nstripes;
-            v.sstride = sss;
-            v.mismatch = bits;
-            v.words = words;
-            v.bit0 = 0;
-            ++t_launches;
-            if ((e = launch_locate(v, Q.data(), xbit, st)) != hipSuccess) rc = hip_fail(e, "launch_locate");
+            rc = verify_groups(
+                a, 8, [&](const VerifySpec& v, hipStream_t s) { return launch_locate(v, Q.data(), xbit, s); },
+                "launch_locate");
         } else if (!rc) {
             locate_rows(P.data(), k, c, Q.data());
             LocateTables tabs;
@@ -1951,7 +1954,7 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
                 rc = hip_fail(e, "locate_tables_upload");
             } else {
                 const LocateRows loc{tabs.dev, xbit};
-                rc = verify_scratch_path(*d, P.data(), k, c, zsrc, sbs, sss, sz, nstripes, bits, words, st, &loc);
+                rc = verify_scratch_path(*d, a, &loc);
                 locate_tables_release(tabs, st);
             }
         }
@@ -1981,43 +1984,37 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     }
     if (!rc && cdev < 0 && (e = hipMemcpyAsync(culprit, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
         rc = hip_fail(e, "hipMemcpyAsync D2H (culprit)");
-    // whatever was enqueued uses the shared buffers: they stay busy whatever happened
-    if (hipEventRecord(d->ev_verify, st) == hipSuccess)
-        d->verify_busy = true;
-    else
-        (void)hipStreamSynchronize(st);
+    order.release();
     if (rc) return rc;
     if ((cdev < 0 || !(flags & FEC_FLAG_ASYNC)) && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "hipStreamSynchronize");
     return set_status(FEC_OK);
 }
-}  // namespace
 
-FEC_API int fec_locate_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
-    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
-    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
-    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
-    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
+// fec_locate_rows / fec_correct_rows: `derive` (locate_rows, correct_rows) of the block numbers' P.
+int rows_from_P(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows,
+                void (*derive)(const uint8_t*, unsigned, unsigned, uint8_t*)) {
+    if (check_verify_call(code, nullptr, nullptr, block_nums, num_block_nums, rows, "rows")) return t_status;
     return guarded([&] {
         const unsigned k = code->k, c = static_cast<unsigned>(num_block_nums - k);
         thread_local std::vector<uint8_t> P;
         P.resize(size_t(c) * k);
         if (verify_rows(code, block_nums, num_block_nums, P.data())) return t_status;
-        locate_rows(P.data(), k, c, rows);
+        derive(P.data(), k, c, rows);
         return set_status(FEC_OK);
     });
+}
+}  // namespace
+
+FEC_API int fec_locate_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
+    return rows_from_P(code, block_nums, num_block_nums, rows, locate_rows);
 }
 
 FEC_API int fec_locate_batch(const fec_t* code, const gf* src, size_t src_block_stride, size_t src_stripe_stride,
                              const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
                              unsigned* culprit, void* stream, unsigned flags) {
     // every check that needs no GPU comes first
-    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
-    if (!src) return set_status(FEC_EINVAL, "NULL buffer: src");
-    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
-    if (!culprit) return set_status(FEC_EINVAL, "culprit is NULL");
-    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
-    if (!gpu_available()) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (check_verify_call(code, src, "src", block_nums, num_block_nums, culprit, "culprit")) return t_status;
     if (nstripes == 0) return set_status(FEC_OK);
     return guarded([&] {
         return run_locate(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
@@ -2027,30 +2024,14 @@ FEC_API int fec_locate_batch(const fec_t* code, const gf* src, size_t src_block_
 
 // ---- batched in-place correction: scrub, locate and heal in one call ------------------------
 FEC_API int fec_correct_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
-    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
-    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
-    if (!rows) return set_status(FEC_EINVAL, "rows is NULL");
-    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
-    return guarded([&] {
-        const unsigned k = code->k, c = static_cast<unsigned>(num_block_nums - k);
-        thread_local std::vector<uint8_t> P;
-        P.resize(size_t(c) * k);
-        if (verify_rows(code, block_nums, num_block_nums, P.data())) return t_status;
-        correct_rows(P.data(), k, c, rows);
-        return set_status(FEC_OK);
-    });
+    return rows_from_P(code, block_nums, num_block_nums, rows, correct_rows);
 }
 
 FEC_API int fec_correct_batch(const fec_t* code, gf* blocks, size_t block_stride, size_t stripe_stride,
                               const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
                               unsigned* culprit, void* stream, unsigned flags) {
     // every check that needs no GPU comes first
-    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
-    if (!blocks) return set_status(FEC_EINVAL, "NULL buffer: blocks");
-    if (!block_nums) return set_status(FEC_EINVAL, "block_nums is NULL");
-    if (!culprit) return set_status(FEC_EINVAL, "culprit is NULL");
-    if (check_verify_nums(code, block_nums, num_block_nums)) return t_status;
-    if (!gpu_available()) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (check_verify_call(code, blocks, "blocks", block_nums, num_block_nums, culprit, "culprit")) return t_status;
     if (nstripes == 0) return set_status(FEC_OK);
     return guarded([&] {
         return run_locate(code, blocks, block_stride, stripe_stride, block_nums, num_block_nums, sz, nstripes, culprit,
@@ -2130,29 +2111,17 @@ int run_repair(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst
                const unsigned* pattern_of, int idev, size_t sz, size_t nstripes, void* stream, unsigned flags) {
     const unsigned k = code->k;
     if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
-    // device memory on one device, or page-locked host memory (read and written in place)
-    const size_t src_extent = (nstripes - 1) * sss + (k - 1) * sbs + sz;
-    const size_t dst_extent = (nstripes - 1) * dss + (nt - 1) * dbs + sz;
-    const int sdev = pointer_device(src), ddev = pointer_device(dst);
-    const gf* zsrc = src;
-    gf* zdst = dst;
-    if (sdev < 0 && !(zsrc = mapped_block(src, src_extent)))
-        return set_status(FEC_EINVAL, "fec_repair_batch takes device or page-locked host memory: src is pageable "
-                                      "host memory, which this call does not stage");
-    if (ddev < 0 && !(zdst = const_cast<gf*>(mapped_block(dst, dst_extent))))
-        return set_status(FEC_EINVAL, "fec_repair_batch takes device or page-locked host memory: dst is pageable "
-                                      "host memory, which this call does not stage");
-    if (sdev >= 0 && ddev >= 0 && sdev != ddev)
-        return set_status(FEC_EINVAL, "batched entry points take memory on one device");
-    int dev = sdev >= 0 ? sdev : ddev;
-    if (dev < 0) dev = idev;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
-    if (idev >= 0 && idev != dev)
-        return set_status(FEC_EINVAL, "pattern_of lives on device %d, the blocks on device %d", idev, dev);
-    DeviceGuard guard(dev);
-    DevCtx* d = nullptr;
-    if (dev_ctx(dev, &d)) return t_status;
-    hipStream_t st = (flags & FEC_FLAG_LIBRARY_STREAM) ? d->stream : static_cast<hipStream_t>(stream);
+    // device memory on one device, or page-locked host memory (read and written in place);
+    // with ids the pattern tables are uploaded, so the call cannot be captured
+    const BatchBuf bufs[2] = {{src, (nstripes - 1) * sss + (k - 1) * sbs + sz, "src"},
+                              {dst, (nstripes - 1) * dss + (nt - 1) * dbs + sz, "dst"}};
+    BatchMem mem;
+    if (resolve_batch(mem, "fec_repair_batch", bufs, 2, "pattern_of", idev, stream, flags,
+                      pattern_of ? kCaptureTables : nullptr))
+        return t_status;
+    const gf* const zsrc = mem.z[0];
+    gf* const zdst = const_cast<gf*>(mem.z[1]);
+    hipStream_t st = mem.st;
     hipError_t e;
     thread_local std::vector<uint8_t> rows;
     thread_local std::vector<uint32_t> masks;
@@ -2162,69 +2131,47 @@ int run_repair(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst
         uint32_t mask = 0;
         if (repair_rows(code, present, targets, nt, rows.data(), &mask)) return t_status;
         if (repair_shared(rows.data(), mask, k, nt, zsrc, sbs, sss, zdst, dbs, dss, sz, nstripes, st)) return t_status;
+    } else if (k <= kMixedMaxK) {
+        rows.resize(npatterns * nt * k);
+        masks.resize(npatterns);
+        for (size_t p = 0; p < npatterns; ++p)
+            if (repair_rows(code, present + p * k, targets + p * nt, nt, &rows[p * nt * k], &masks[p]))
+                return t_status;
+        const uint8_t* in[kMixedMaxK];
+        uint8_t* out[kRepairMaxRows];
+        for (unsigned j = 0; j < k; ++j) in[j] = zsrc + j * sbs;
+        for (size_t i = 0; i < nt; ++i) out[i] = zdst + i * dbs;
+        RepairSpec r;
+        r.k = k;
+        r.t = static_cast<uint32_t>(nt);
+        r.rows = rows.data();
+        r.masks = masks.data();
+        r.npatterns = static_cast<uint32_t>(npatterns);
+        r.ids_host = idev < 0 ? pattern_of : nullptr;
+        r.ids_dev = idev < 0 ? nullptr : pattern_of;
+        r.in = in;
+        r.out = out;
+        r.sz = sz;
+        r.nstripes = nstripes;
+        r.in_sstride = sss;
+        r.out_sstride = dss;
+        ++t_launches;
+        if ((e = launch_repair(r, st)) != hipSuccess) return hip_fail(e, "launch_repair");
     } else {
-        if (stream_capturing(st))
-            return set_status(FEC_EINVAL, "fec_repair_batch: the stream is being captured into a graph (the "
-                                          "pattern tables are uploaded when the call is made)");
-        if (k <= kMixedMaxK) {
-            rows.resize(npatterns * nt * k);
-            masks.resize(npatterns);
-            for (size_t p = 0; p < npatterns; ++p)
-                if (repair_rows(code, present + p * k, targets + p * nt, nt, &rows[p * nt * k], &masks[p]))
-                    return t_status;
-            const uint8_t* in[kMixedMaxK];
-            uint8_t* out[kRepairMaxRows];
-            for (unsigned j = 0; j < k; ++j) in[j] = zsrc + j * sbs;
-            for (size_t i = 0; i < nt; ++i) out[i] = zdst + i * dbs;
-            RepairSpec r;
-            r.k = k;
-            r.t = static_cast<uint32_t>(nt);
-            r.rows = rows.data();
-            r.masks = masks.data();
-            r.npatterns = static_cast<uint32_t>(npatterns);
-            r.ids_host = idev < 0 ? pattern_of : nullptr;
-            r.ids_dev = idev < 0 ? nullptr : pattern_of;
-            r.in = in;
-            r.out = out;
-            r.sz = sz;
-            r.nstripes = nstripes;
-            r.in_sstride = sss;
-            r.out_sstride = dss;
-            ++t_launches;
-            if ((e = launch_repair(r, st)) != hipSuccess) return hip_fail(e, "launch_repair");
-        } else {
-            // codes past the register shapes: maximal runs of consecutive stripes
-            // with one id, each one shared-matrix application of that pattern's live rows
-            thread_local std::vector<unsigned> hids;
-            const unsigned* ids = pattern_of;
-            if (idev >= 0) {
-                hids.resize(nstripes);
-                if ((e = hipMemcpyAsync(hids.data(), pattern_of, nstripes * sizeof(unsigned), hipMemcpyDeviceToHost,
-                                        st)) != hipSuccess)
-                    return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
-                if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-                ids = hids.data();
-            }
-            std::unordered_map<unsigned, std::pair<std::vector<uint8_t>, uint32_t>> rows_of;
-            for (size_t s0 = 0; s0 < nstripes;) {
-                size_t s1 = s0 + 1;
-                while (s1 < nstripes && ids[s1] == ids[s0]) ++s1;
-                const unsigned id = ids[s0];
-                if (id < npatterns) {  // (device ids are not checked: such stripes stay unwritten, as on the kernel)
-                    std::pair<std::vector<uint8_t>, uint32_t>& pr = rows_of[id];
-                    if (pr.first.empty()) {
-                        pr.first.resize(nt * k);
-                        if (repair_rows(code, present + size_t(id) * k, targets + size_t(id) * nt, nt,
-                                        pr.first.data(), &pr.second))
-                            return t_status;
-                    }
-                    if (repair_shared(pr.first.data(), pr.second, k, nt, zsrc + s0 * sss, sbs, sss, zdst + s0 * dss,
-                                      dbs, dss, sz, s1 - s0, st))
-                        return t_status;
-                }
-                s0 = s1;
-            }
-        }
+        // codes past the register shapes: each run one shared-matrix application of its pattern's live rows
+        typedef std::pair<std::vector<uint8_t>, uint32_t> RowsAndMask;
+        if (for_each_id_run<RowsAndMask>(
+                pattern_of, idev, nstripes, npatterns, st,
+                [&](unsigned id, RowsAndMask& pr) {
+                    pr.first.resize(nt * k);
+                    return repair_rows(code, present + size_t(id) * k, targets + size_t(id) * nt, nt,
+                                       pr.first.data(), &pr.second);
+                },
+                [&](const RowsAndMask& pr, size_t s0, size_t s1) {
+                    return repair_shared(pr.first.data(), pr.second, k, nt, zsrc + s0 * sss, sbs, sss,
+                                         zdst + s0 * dss, dbs, dss, sz, s1 - s0, st);
+                }))
+            return t_status;
     }
     if (!(flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "hipStreamSynchronize");
@@ -2260,24 +2207,14 @@ FEC_API int fec_repair_batch(const fec_t* code, const gf* src, size_t src_block_
     if (ntargets == 0 || ntargets > kRepairMaxRows)
         return set_status(FEC_EINVAL, "ntargets is %zu: a call takes between 1 and %u targets per stripe", ntargets,
                           unsigned(kRepairMaxRows));
-    if (npatterns == 0 && nstripes > 0)
-        return set_status(FEC_EINVAL, "npatterns is 0: stripe 0 of %zu has no pattern", nstripes);
-    if (npatterns > kMixedMaxPatterns)
-        return set_status(FEC_EINVAL, "%zu patterns: a call takes at most %u", npatterns, unsigned(kMixedMaxPatterns));
-    if (!pattern_of && npatterns != 1)
-        return set_status(FEC_EINVAL, "pattern_of is NULL with %zu patterns: without ids every stripe uses pattern 0, "
-                                      "so npatterns must be 1", npatterns);
-    if (check_repair_patterns(code, present, targets, ntargets, npatterns)) return t_status;
-    // ids in host memory are checked here; ids in device memory cannot be (the
-    // kernel leaves a stripe with an id >= npatterns unwritten)
-    const int ngpu = gpu_available();
-    const int idev = ngpu && pattern_of ? pointer_device(pattern_of) : -1;
-    if (pattern_of && idev < 0)
-        for (size_t s = 0; s < nstripes; ++s)
-            if (pattern_of[s] >= npatterns)
-                return set_status(FEC_EINVAL, "stripe %zu: pattern id %u out of range (npatterns = %zu)", s,
-                                  pattern_of[s], npatterns);
-    if (!ngpu) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    int idev = -1;
+    if (check_patterns_and_ids(npatterns, nstripes, pattern_of, &idev, [&] {
+            if (!pattern_of && npatterns != 1)
+                return set_status(FEC_EINVAL, "pattern_of is NULL with %zu patterns: without ids every stripe uses "
+                                              "pattern 0, so npatterns must be 1", npatterns);
+            return check_repair_patterns(code, present, targets, ntargets, npatterns);
+        }))
+        return t_status;
     if (sz == 0 || nstripes == 0) return set_status(FEC_OK);
     return guarded([&] {
         return run_repair(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,

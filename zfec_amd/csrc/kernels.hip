@@ -136,6 +136,11 @@ __constant__ TableBank g_bank = make_bank();
 // tables in the kernel arguments.
 constexpr TableBank kHostBank = make_bank();
 
+// dst[0..5) = the table of coefficient `coef`.
+inline void host_tab(uint32_t* dst, uint8_t coef) {
+    std::memcpy(dst, &kHostBank.w[uint32_t(coef) * 8], 5 * sizeof(uint32_t));
+}
+
 struct Tab {
     uint32_t w0, w1, w2, w3, w4;
 };
@@ -3212,6 +3217,12 @@ thread_local uint32_t* t_signal_flag = nullptr;
 thread_local uint32_t t_signal_seq = 0;
 thread_local bool t_signal_used = false;
 
+// Every public launcher: an unconsumed launch_apply request must not outlive this launch.
+void reset_signal() {
+    t_signal_flag = nullptr;
+    t_signal_used = false;
+}
+
 // ---- register kernels (k <= 4, r <= 8) ----------------------------------------
 constexpr int kRegK = 4, kRegR = 8;
 const char* const kRegNames[kRegK + 1][kRegR + 1] = {
@@ -3258,15 +3269,7 @@ uint32_t fill_regjob(const ApplySpec& a, RegJob<K, R>& job, bool rows) {
     for (int j = 0; j < K; ++j) job.in[j] = a.in[j];
     for (int i = 0; i < R; ++i) job.out[i] = a.out[i];
     for (int i = 0; i < R; ++i)
-        for (int j = 0; j < K; ++j) {
-            const uint32_t* w = &kHostBank.w[uint32_t(a.coef[size_t(i) * a.coef_stride + j]) * 8];
-            uint32_t* t = &job.tab[(i * K + j) * 5];
-            t[0] = w[0];
-            t[1] = w[1];
-            t[2] = w[2];
-            t[3] = w[3];
-            t[4] = w[4];
-        }
+        for (int j = 0; j < K; ++j) host_tab(&job.tab[(i * K + j) * 5], a.coef[size_t(i) * a.coef_stride + j]);
     const uint64_t cps = (a.sz + kChunk - 1) / kChunk;
     if (cps * a.nstripes >= (1ull << 32) - (1ull << 24)) return 0;
     job.cps = static_cast<uint32_t>(cps);
@@ -4381,102 +4384,48 @@ hipError_t mixed_slot(size_t bytes, MixedRing::Slot** out) {
     return hipSuccess;
 }
 
-template <int K>
-hipError_t launch_mixed_k(const MixedSpec& m, hipStream_t stream) {
-    static const char* const kNames[kMixedMaxK + 1] = {"", "matapply_mixed<1>", "matapply_mixed<2>",
-                                                       "matapply_mixed<3>", "matapply_mixed<4>"};
-    constexpr uint32_t TD = mixed_tab_dwords<K>();
-    const size_t tab_bytes = (size_t(m.npatterns) * TD * 4 + 255) / 256 * 256;
-    const size_t ids_bytes = m.ids_host ? size_t(m.nstripes) * 4 : 0;
+// One stream-ordered upload through a MixedRing slot: acquire(), fill host(),
+// copy(), launch what reads dev(), then done() -- also after a failed launch,
+// since the copy reads the slot whatever happened.
+struct StagedUpload {
     MixedRing::Slot* slot = nullptr;
-    hipError_t e = mixed_slot(tab_bytes + ids_bytes, &slot);
-    if (e != hipSuccess) return e;
-    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
-    for (size_t p = 0; p < m.npatterns; ++p) {
-        uint32_t* t = ht + p * TD;
-        for (int i = 0; i < K * K; ++i)
-            std::memcpy(t + i * 5, &kHostBank.w[uint32_t(m.rows[p * K * K + i]) * 8], 5 * sizeof(uint32_t));
-        for (uint32_t i = K * K * 5; i < TD; ++i) t[i] = 0;
+    hipError_t acquire(size_t bytes) { return mixed_slot(bytes, &slot); }
+    uint8_t* host() const { return slot->host; }
+    const uint8_t* dev() const { return slot->dev; }
+    hipError_t copy(size_t bytes, hipStream_t stream) const {
+        return hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream);
     }
-    if (ids_bytes) std::memcpy(slot->host + tab_bytes, m.ids_host, ids_bytes);
-    if ((e = hipMemcpyAsync(slot->dev, slot->host, tab_bytes + ids_bytes, hipMemcpyHostToDevice, stream)) !=
-        hipSuccess)
-        return e;
-    const uint32_t* ids = m.ids_host ? reinterpret_cast<const uint32_t*>(slot->dev + tab_bytes) : m.ids_dev;
-    // Launches of at most Config::launch_units lanes: blocks longer than that
-    // many 16-byte chunks are cut into byte ranges (whole waves of 1 KiB),
-    // batches into stripe groups, the id pointer advanced per group.
-    const uint64_t max_units = config().launch_units;
-    const uint64_t piece = (max_units & ~uint64_t(63)) * kChunk;
-    const uint64_t cap = unit_grid_cap();
-    auto launches = [&]() -> hipError_t {
-        for (uint64_t b0 = 0; b0 < m.sz; b0 += piece) {
-            const uint64_t len = std::min(piece, m.sz - b0);
-            const uint64_t cps = (len + kChunk - 1) / kChunk, wps = (cps + 63) / 64;
-            const uint64_t group = std::max<uint64_t>(1, max_units / (wps * 64));
-            for (uint64_t s0 = 0; s0 < m.nstripes; s0 += group) {
-                const uint64_t ns = std::min(group, m.nstripes - s0);
-                MixedJob<K> job;
-                job.sz = len;
-                job.in_sstride = m.in_sstride;
-                job.out_sstride = m.out_sstride;
-                job.nstripes = static_cast<uint32_t>(ns);
-                job.cps = static_cast<uint32_t>(cps);
-                job.wps = static_cast<uint32_t>(wps);
-                job.npatterns = m.npatterns;
-                job.tables = reinterpret_cast<const uint32_t*>(slot->dev);
-                job.ids = ids + s0;
-                for (int j = 0; j < K; ++j) {
-                    job.in[j] = m.in[j] + b0 + s0 * m.in_sstride;
-                    job.out[j] = m.out[j] + b0 + s0 * m.out_sstride;
-                }
-                const uint64_t waves = ns * wps, need = (waves + kBlock / 64 - 1) / (kBlock / 64);
-                const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
-                const uint64_t gstride = uint64_t(grid) * (kBlock / 64);
-                job.gs_s = static_cast<uint32_t>(gstride / wps);
-                job.gs_w = static_cast<uint32_t>(gstride % wps);
-                const hipError_t le =
-                    launch_job(reinterpret_cast<const void*>(matapply_mixed<K>), grid, kBlock, 0, stream, job);
-                if (le != hipSuccess) return le;
-            }
-        }
-        return hipSuccess;
-    };
-    e = launches();
-    // the copy (and any launch made) reads the slot: it stays busy whatever happened
-    if (hipEventRecord(slot->ev, stream) == hipSuccess)
-        slot->busy = true;
-    else
-        (void)hipStreamSynchronize(stream);
-    if (e == hipSuccess) t_last_kernel = kNames[K];
-    return e;
-}
-
-// ---- parity verification dispatch (matverify_reg, rows_differ) ---------------------
-// The wave-inside-one-stripe walk of a launch over ns stripes of len bytes.
-struct WaveWalk {
-    uint32_t cps, wps, grid, gs_w, gs_s;
+    void done(hipStream_t stream) const {
+        if (hipEventRecord(slot->ev, stream) == hipSuccess)
+            slot->busy = true;
+        else
+            (void)hipStreamSynchronize(stream);
+    }
 };
 
-WaveWalk wave_walk(uint64_t len, uint64_t ns) {
-    WaveWalk k;
+// The wave-inside-one-stripe walk of a launch over ns stripes of len bytes,
+// into any job with the six walk fields; returns the grid.
+template <class J>
+uint32_t fill_walk(J& job, uint64_t len, uint64_t ns) {
     const uint64_t cps = (len + kChunk - 1) / kChunk, wps = (cps + 63) / 64;
     const uint64_t waves = ns * wps, need = (waves + kBlock / 64 - 1) / (kBlock / 64);
     const uint64_t cap = unit_grid_cap();
-    k.cps = static_cast<uint32_t>(cps);
-    k.wps = static_cast<uint32_t>(wps);
-    k.grid = static_cast<uint32_t>(need < cap ? need : cap);
-    const uint64_t gstride = uint64_t(k.grid) * (kBlock / 64);
-    k.gs_s = static_cast<uint32_t>(gstride / wps);
-    k.gs_w = static_cast<uint32_t>(gstride % wps);
-    return k;
+    const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
+    const uint64_t gstride = uint64_t(grid) * (kBlock / 64);
+    job.sz = len;
+    job.nstripes = static_cast<uint32_t>(ns);
+    job.cps = static_cast<uint32_t>(cps);
+    job.wps = static_cast<uint32_t>(wps);
+    job.gs_s = static_cast<uint32_t>(gstride / wps);
+    job.gs_w = static_cast<uint32_t>(gstride % wps);
+    return grid;
 }
 
-// Launches of at most Config::launch_units lanes, as launch_mixed_k cuts them:
-// blocks longer than that many 16-byte chunks into byte ranges (whole waves of
-// 1 KiB), batches into stripe groups.  f(b0, len, s0, ns) makes one launch.
+// Launches of at most Config::launch_units lanes: blocks longer than that many
+// 16-byte chunks are cut into byte ranges (whole waves of 1 KiB), batches into
+// stripe groups.  f(b0, len, s0, ns) makes one launch.
 template <class F>
-hipError_t verify_pieces(uint64_t sz, uint64_t nstripes, F&& f) {
+hipError_t launch_pieces(uint64_t sz, uint64_t nstripes, F&& f) {
     const uint64_t max_units = config().launch_units;
     const uint64_t piece = (max_units & ~uint64_t(63)) * kChunk;
     for (uint64_t b0 = 0; b0 < sz; b0 += piece) {
@@ -4491,46 +4440,105 @@ hipError_t verify_pieces(uint64_t sz, uint64_t nstripes, F&& f) {
     return hipSuccess;
 }
 
-char g_verify_names[kRegK + 1][kRegR + 1][24];
-
-template <int K, int R>
-hipError_t launch_verify_kr(const VerifySpec& v, hipStream_t stream) {
-    VerifyJob<K, R> job;
-    job.sstride = v.sstride;
-    job.words = v.words;
-    job.bit0 = v.bit0;
-    job.pad_ = 0;
-    for (int i = 0; i < R; ++i)
-        for (int j = 0; j < K; ++j)
-            std::memcpy(&job.tab[(i * K + j) * 5], &kHostBank.w[uint32_t(v.coef[size_t(i) * v.coef_stride + j]) * 8],
-                        5 * sizeof(uint32_t));
-    const hipError_t e = verify_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const WaveWalk ww = wave_walk(len, ns);
-        job.sz = len;
-        job.nstripes = static_cast<uint32_t>(ns);
-        job.cps = ww.cps;
-        job.wps = ww.wps;
-        job.gs_w = ww.gs_w;
-        job.gs_s = ww.gs_s;
-        job.mismatch = v.mismatch + s0 * v.words;
-        for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
-        for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
-        return launch_job(reinterpret_cast<const void*>(matverify_reg<K, R>), ww.grid, kBlock, 0, stream, job);
+template <int K>
+hipError_t launch_mixed_k(const MixedSpec& m, hipStream_t stream) {
+    static const char* const kNames[kMixedMaxK + 1] = {"", "matapply_mixed<1>", "matapply_mixed<2>",
+                                                       "matapply_mixed<3>", "matapply_mixed<4>"};
+    constexpr uint32_t TD = mixed_tab_dwords<K>();
+    const size_t tab_bytes = (size_t(m.npatterns) * TD * 4 + 255) / 256 * 256;
+    const size_t ids_bytes = m.ids_host ? size_t(m.nstripes) * 4 : 0;
+    StagedUpload up;
+    hipError_t e = up.acquire(tab_bytes + ids_bytes);
+    if (e != hipSuccess) return e;
+    uint32_t* ht = reinterpret_cast<uint32_t*>(up.host());
+    for (size_t p = 0; p < m.npatterns; ++p) {
+        uint32_t* t = ht + p * TD;
+        for (int i = 0; i < K * K; ++i) host_tab(t + i * 5, m.rows[p * K * K + i]);
+        for (uint32_t i = K * K * 5; i < TD; ++i) t[i] = 0;
+    }
+    if (ids_bytes) std::memcpy(up.host() + tab_bytes, m.ids_host, ids_bytes);
+    if ((e = up.copy(tab_bytes + ids_bytes, stream)) != hipSuccess) return e;
+    const uint32_t* ids = m.ids_host ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : m.ids_dev;
+    MixedJob<K> job;
+    job.in_sstride = m.in_sstride;
+    job.out_sstride = m.out_sstride;
+    job.npatterns = m.npatterns;
+    job.tables = reinterpret_cast<const uint32_t*>(up.dev());
+    // the id pointer advances per stripe group
+    e = launch_pieces(m.sz, m.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const uint32_t grid = fill_walk(job, len, ns);
+        job.ids = ids + s0;
+        for (int j = 0; j < K; ++j) {
+            job.in[j] = m.in[j] + b0 + s0 * m.in_sstride;
+            job.out[j] = m.out[j] + b0 + s0 * m.out_sstride;
+        }
+        return launch_job(reinterpret_cast<const void*>(matapply_mixed<K>), grid, kBlock, 0, stream, job);
     });
-    if (e == hipSuccess) t_last_kernel = g_verify_names[K][R];
+    up.done(stream);
+    if (e == hipSuccess) t_last_kernel = kNames[K];
     return e;
 }
 
-typedef hipError_t (*VerifyLaunch)(const VerifySpec&, hipStream_t);
+// ---- parity verification dispatch (matverify_reg, rows_differ) ---------------------
+// The three <K, R> families (matverify_reg, matlocate_reg, matrepair_mixed):
+// name[k][r] = "kernel<k,r>", and table(k, r) = L::launch<k, r> for 1 <= k <=
+// kRegK, RMin <= r <= kRegR (null at k = 0 and below RMin).
+struct KrNames {
+    char name[kRegK + 1][kRegR + 1][28];
+    explicit KrNames(const char* kernel) {
+        for (int k = 1; k <= kRegK; ++k)
+            for (int r = 1; r <= kRegR; ++r) snprintf(name[k][r], sizeof name[k][r], "%s<%d,%d>", kernel, k, r);
+    }
+};
 
-template <int K, int... R>
-constexpr std::array<VerifyLaunch, kRegR + 1> verify_row(std::integer_sequence<int, R...>) {
-    return {{nullptr, launch_verify_kr<K, R + 1>...}};
+template <class L, int RMin = 1>
+struct KrTable {
+    typedef decltype(&L::template launch<1, RMin>) Fn;
+    template <int K, int R>
+    static constexpr Fn pick() {
+        if constexpr (K >= 1 && R >= RMin)
+            return &L::template launch<K, R>;
+        else
+            return nullptr;
+    }
+    template <int... I>
+    static constexpr std::array<Fn, sizeof...(I)> all(std::integer_sequence<int, I...>) {
+        return {{pick<I / (kRegR + 1), I % (kRegR + 1)>()...}};
+    }
+    std::array<Fn, (kRegK + 1) * (kRegR + 1)> fn = all(std::make_integer_sequence<int, (kRegK + 1) * (kRegR + 1)>());
+    constexpr Fn operator()(uint32_t k, uint32_t r) const { return fn[k * (kRegR + 1) + r]; }
+};
+
+// The r x k tables of `v.coef` in the RegJob layout.
+template <int K, int R>
+void fill_tabs(uint32_t* tab, const VerifySpec& v) {
+    for (int i = 0; i < R; ++i)
+        for (int j = 0; j < K; ++j) host_tab(&tab[(i * K + j) * 5], v.coef[size_t(i) * v.coef_stride + j]);
 }
 
-const std::array<VerifyLaunch, kRegR + 1> g_verify_launch[kRegK + 1] = {
-    {}, verify_row<1>(std::make_integer_sequence<int, kRegR>()), verify_row<2>(std::make_integer_sequence<int, kRegR>()),
-    verify_row<3>(std::make_integer_sequence<int, kRegR>()), verify_row<4>(std::make_integer_sequence<int, kRegR>())};
+const KrNames g_verify_names("matverify_reg");
+
+struct VerifyKr {
+    template <int K, int R>
+    static hipError_t launch(const VerifySpec& v, hipStream_t stream) {
+        VerifyJob<K, R> job;
+        job.sstride = v.sstride;
+        job.words = v.words;
+        job.bit0 = v.bit0;
+        job.pad_ = 0;
+        fill_tabs<K, R>(job.tab, v);
+        const hipError_t e = launch_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+            const uint32_t grid = fill_walk(job, len, ns);
+            job.mismatch = v.mismatch + s0 * v.words;
+            for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
+            for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
+            return launch_job(reinterpret_cast<const void*>(matverify_reg<K, R>), grid, kBlock, 0, stream, job);
+        });
+        if (e == hipSuccess) t_last_kernel = g_verify_names.name[K][R];
+        return e;
+    }
+};
+constexpr KrTable<VerifyKr> g_verify_launch;
 
 // ---- error location dispatch (matlocate_reg) ------------------------------------------
 struct LocateArgs {
@@ -4538,50 +4546,30 @@ struct LocateArgs {
     uint32_t xbit;
 };
 
-char g_locate_names[kRegK + 1][kRegR + 1][24];
+const KrNames g_locate_names("matlocate_reg");
 
-template <int K, int R>
-hipError_t launch_locate_kr(const VerifySpec& v, const LocateArgs& a, hipStream_t stream) {
-    LocateJob<K, R> job;
-    job.sstride = v.sstride;
-    job.words = v.words;
-    job.xbit = a.xbit;
-    job.pad_ = 0;
-    for (int i = 0; i < R; ++i)
-        for (int j = 0; j < K; ++j)
-            std::memcpy(&job.tab[(i * K + j) * 5], &kHostBank.w[uint32_t(v.coef[size_t(i) * v.coef_stride + j]) * 8],
-                        5 * sizeof(uint32_t));
-    for (int i = 0; i < (R - 1) * K; ++i)
-        std::memcpy(&job.qtab[i * 5], &kHostBank.w[uint32_t(a.q[i]) * 8], 5 * sizeof(uint32_t));
-    const hipError_t e = verify_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const WaveWalk ww = wave_walk(len, ns);
-        job.sz = len;
-        job.nstripes = static_cast<uint32_t>(ns);
-        job.cps = ww.cps;
-        job.wps = ww.wps;
-        job.gs_w = ww.gs_w;
-        job.gs_s = ww.gs_s;
-        job.bits = v.mismatch + s0 * v.words;
-        for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
-        for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
-        return launch_job(reinterpret_cast<const void*>(matlocate_reg<K, R>), ww.grid, kBlock, 0, stream, job);
-    });
-    if (e == hipSuccess) t_last_kernel = g_locate_names[K][R];
-    return e;
-}
-
-typedef hipError_t (*LocateLaunch)(const VerifySpec&, const LocateArgs&, hipStream_t);
-
-template <int K, int... R>
-constexpr std::array<LocateLaunch, kRegR + 1> locate_row(std::integer_sequence<int, R...>) {
-    return {{nullptr, nullptr, launch_locate_kr<K, R + 2>...}};
-}
-
-const std::array<LocateLaunch, kRegR + 1> g_locate_launch[kRegK + 1] = {
-    {}, locate_row<1>(std::make_integer_sequence<int, kRegR - 1>()),
-    locate_row<2>(std::make_integer_sequence<int, kRegR - 1>()),
-    locate_row<3>(std::make_integer_sequence<int, kRegR - 1>()),
-    locate_row<4>(std::make_integer_sequence<int, kRegR - 1>())};
+struct LocateKr {
+    template <int K, int R>
+    static hipError_t launch(const VerifySpec& v, const LocateArgs& a, hipStream_t stream) {
+        LocateJob<K, R> job;
+        job.sstride = v.sstride;
+        job.words = v.words;
+        job.xbit = a.xbit;
+        job.pad_ = 0;
+        fill_tabs<K, R>(job.tab, v);
+        for (int i = 0; i < (R - 1) * K; ++i) host_tab(&job.qtab[i * 5], a.q[i]);
+        const hipError_t e = launch_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+            const uint32_t grid = fill_walk(job, len, ns);
+            job.bits = v.mismatch + s0 * v.words;
+            for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
+            for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
+            return launch_job(reinterpret_cast<const void*>(matlocate_reg<K, R>), grid, kBlock, 0, stream, job);
+        });
+        if (e == hipSuccess) t_last_kernel = g_locate_names.name[K][R];
+        return e;
+    }
+};
+constexpr KrTable<LocateKr, 2> g_locate_launch;
 
 // ---- matrepair_mixed dispatch ------------------------------------------------------
 // One upload through a MixedRing slot (the records, then any host-side ids)
@@ -4594,47 +4582,33 @@ struct RepairUpload {
 
 constexpr uint32_t repair_rec_dwords(uint32_t k, uint32_t t) { return (t * k * 5 + 1 + 3) / 4 * 4; }
 
-char g_repair_names[kRegK + 1][kRegR + 1][28];
+const KrNames g_repair_names("matrepair_mixed");
 
-// Rows [g0, g0 + R) of every stripe, cut into launches as verify_pieces cuts them.
-template <int K, int R>
-hipError_t launch_repair_kr(const RepairSpec& p, const RepairUpload& u, uint32_t g0, hipStream_t stream) {
-    RepairJob<K, R> job;
-    job.in_sstride = p.in_sstride;
-    job.out_sstride = p.out_sstride;
-    job.npatterns = p.npatterns;
-    job.rec_dwords = u.rec_dwords;
-    job.tab_off = g0 * K * 5;
-    job.mask_off = u.mask_off;
-    job.bit0 = g0;
-    job.records = u.records;
-    const hipError_t e = verify_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const WaveWalk ww = wave_walk(len, ns);
-        job.sz = len;
-        job.nstripes = static_cast<uint32_t>(ns);
-        job.cps = ww.cps;
-        job.wps = ww.wps;
-        job.gs_w = ww.gs_w;
-        job.gs_s = ww.gs_s;
-        job.ids = u.ids + s0;
-        for (int j = 0; j < K; ++j) job.in[j] = p.in[j] + b0 + s0 * p.in_sstride;
-        for (int i = 0; i < R; ++i) job.out[i] = p.out[g0 + i] + b0 + s0 * p.out_sstride;
-        return launch_job(reinterpret_cast<const void*>(matrepair_mixed<K, R>), ww.grid, kBlock, 0, stream, job);
-    });
-    if (e == hipSuccess) t_last_kernel = g_repair_names[K][R];
-    return e;
-}
-
-typedef hipError_t (*RepairLaunch)(const RepairSpec&, const RepairUpload&, uint32_t, hipStream_t);
-
-template <int K, int... R>
-constexpr std::array<RepairLaunch, kRegR + 1> repair_row(std::integer_sequence<int, R...>) {
-    return {{nullptr, launch_repair_kr<K, R + 1>...}};
-}
-
-const std::array<RepairLaunch, kRegR + 1> g_repair_launch[kRegK + 1] = {
-    {}, repair_row<1>(std::make_integer_sequence<int, kRegR>()), repair_row<2>(std::make_integer_sequence<int, kRegR>()),
-    repair_row<3>(std::make_integer_sequence<int, kRegR>()), repair_row<4>(std::make_integer_sequence<int, kRegR>())};
+// Rows [g0, g0 + R) of every stripe.
+struct RepairKr {
+    template <int K, int R>
+    static hipError_t launch(const RepairSpec& p, const RepairUpload& u, uint32_t g0, hipStream_t stream) {
+        RepairJob<K, R> job;
+        job.in_sstride = p.in_sstride;
+        job.out_sstride = p.out_sstride;
+        job.npatterns = p.npatterns;
+        job.rec_dwords = u.rec_dwords;
+        job.tab_off = g0 * K * 5;
+        job.mask_off = u.mask_off;
+        job.bit0 = g0;
+        job.records = u.records;
+        const hipError_t e = launch_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+            const uint32_t grid = fill_walk(job, len, ns);
+            job.ids = u.ids + s0;
+            for (int j = 0; j < K; ++j) job.in[j] = p.in[j] + b0 + s0 * p.in_sstride;
+            for (int i = 0; i < R; ++i) job.out[i] = p.out[g0 + i] + b0 + s0 * p.out_sstride;
+            return launch_job(reinterpret_cast<const void*>(matrepair_mixed<K, R>), grid, kBlock, 0, stream, job);
+        });
+        if (e == hipSuccess) t_last_kernel = g_repair_names.name[K][R];
+        return e;
+    }
+};
+constexpr KrTable<RepairKr> g_repair_launch;
 
 hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
     const uint32_t k = p.k, t = p.t;
@@ -4647,33 +4621,26 @@ hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
     u.mask_off = t * k * 5;
     const size_t tab_bytes = (size_t(p.npatterns) * u.rec_dwords * 4 + 255) / 256 * 256;
     const size_t ids_bytes = p.ids_host ? size_t(p.nstripes) * 4 : 0;
-    MixedRing::Slot* slot = nullptr;
-    hipError_t e = mixed_slot(tab_bytes + ids_bytes, &slot);
+    StagedUpload up;
+    hipError_t e = up.acquire(tab_bytes + ids_bytes);
     if (e != hipSuccess) return e;
-    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
+    uint32_t* ht = reinterpret_cast<uint32_t*>(up.host());
     for (size_t q = 0; q < p.npatterns; ++q) {
         uint32_t* rec = ht + q * u.rec_dwords;
-        for (uint32_t i = 0; i < t * k; ++i)
-            std::memcpy(rec + i * 5, &kHostBank.w[uint32_t(p.rows[q * t * k + i]) * 8], 5 * sizeof(uint32_t));
+        for (uint32_t i = 0; i < t * k; ++i) host_tab(rec + i * 5, p.rows[q * t * k + i]);
         rec[u.mask_off] = p.masks[q];
         for (uint32_t i = u.mask_off + 1; i < u.rec_dwords; ++i) rec[i] = 0;
     }
-    if (ids_bytes) std::memcpy(slot->host + tab_bytes, p.ids_host, ids_bytes);
-    if ((e = hipMemcpyAsync(slot->dev, slot->host, tab_bytes + ids_bytes, hipMemcpyHostToDevice, stream)) !=
-        hipSuccess)
-        return e;
-    u.records = reinterpret_cast<const uint32_t*>(slot->dev);
-    u.ids = p.ids_host ? reinterpret_cast<const uint32_t*>(slot->dev + tab_bytes) : p.ids_dev;
+    if (ids_bytes) std::memcpy(up.host() + tab_bytes, p.ids_host, ids_bytes);
+    if ((e = up.copy(tab_bytes + ids_bytes, stream)) != hipSuccess) return e;
+    u.records = reinterpret_cast<const uint32_t*>(up.dev());
+    u.ids = p.ids_host ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : p.ids_dev;
     for (uint32_t g0 = 0; g0 < t && e == hipSuccess; g0 += kRegR) {
         const uint32_t rg = std::min<uint32_t>(kRegR, t - g0);
         if (!((any >> g0) & ((1u << rg) - 1u))) continue;  // rows no pattern stores
-        e = g_repair_launch[k][rg](p, u, g0, stream);
+        e = g_repair_launch(k, rg)(p, u, g0, stream);
     }
-    // the copy (and any launch made) reads the slot: it stays busy whatever happened
-    if (hipEventRecord(slot->ev, stream) == hipSuccess)
-        slot->busy = true;
-    else
-        (void)hipStreamSynchronize(stream);
+    up.done(stream);
     return e;
 }
 
@@ -4681,37 +4648,23 @@ hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
 
 hipError_t launch_repair(const RepairSpec& p, hipStream_t stream) {
     std::call_once(g_dispatch_once, init_dispatch);
-    static std::once_flag names_once;
-    std::call_once(names_once, [] {
-        for (int k = 1; k <= kRegK; ++k)
-            for (int r = 1; r <= kRegR; ++r)
-                snprintf(g_repair_names[k][r], sizeof g_repair_names[k][r], "matrepair_mixed<%d,%d>", k, r);
-    });
     if (p.k < 1 || p.k > kMixedMaxK || p.t < 1 || p.t > kRepairMaxRows || p.npatterns < 1 ||
         p.npatterns > kMixedMaxPatterns || !p.rows || !p.masks || (!p.ids_host && !p.ids_dev) || p.sz == 0 ||
         p.nstripes == 0 || p.nstripes >= (1ull << 32))
         return hipErrorInvalidValue;
     if (stream_capturing(stream)) return hipErrorNotSupported;
-    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
-    t_signal_used = false;
+    reset_signal();
     return launch_repair_all(p, stream);
 }
 
 hipError_t launch_verify(const VerifySpec& v, hipStream_t stream) {
     std::call_once(g_dispatch_once, init_dispatch);
-    static std::once_flag names_once;
-    std::call_once(names_once, [] {
-        for (int k = 1; k <= kRegK; ++k)
-            for (int r = 1; r <= kRegR; ++r)
-                snprintf(g_verify_names[k][r], sizeof g_verify_names[k][r], "matverify_reg<%d,%d>", k, r);
-    });
     if (v.k < 1 || v.k > static_cast<uint32_t>(kRegK) || v.r < 1 || v.r > static_cast<uint32_t>(kRegR) ||
         v.coef_stride < v.k || !v.mismatch || v.sz == 0 || v.nstripes == 0 || v.nstripes >= (1ull << 32) ||
         uint64_t(v.bit0) + v.r > uint64_t(v.words) * 32)
         return hipErrorInvalidValue;
-    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
-    t_signal_used = false;
-    return g_verify_launch[v.k][v.r](v, stream);
+    reset_signal();
+    return g_verify_launch(v.k, v.r)(v, stream);
 }
 
 bool verify_bsr_ok(uint32_t k, uint32_t r, uint64_t sz) {
@@ -4724,8 +4677,7 @@ hipError_t launch_verify_bsr(const VerifySpec& v, hipStream_t stream) {
         uint64_t(v.bit0) + v.r > uint64_t(v.words) * 32)
         return hipErrorInvalidValue;
     if (v.r > kVerifyBsrRows || !verify_bsr_ok(v.k, v.r, v.sz)) return hipErrorNotSupported;
-    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
-    t_signal_used = false;
+    reset_signal();
     return launch_verify_bsr_one(v, stream);
 }
 
@@ -4734,8 +4686,7 @@ hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream) {
     if (d.r < 1 || d.r > static_cast<uint32_t>(kMaxOut) || !d.mismatch || d.sz == 0 || d.nstripes == 0 ||
         d.nstripes >= (1ull << 32) || uint64_t(d.bit0) + d.r > uint64_t(d.words) * 32)
         return hipErrorInvalidValue;
-    t_signal_flag = nullptr;
-    t_signal_used = false;
+    reset_signal();
     DifferJob job;
     job.a_sstride = d.a_sstride;
     job.b_sstride = d.b_sstride;
@@ -4743,20 +4694,14 @@ hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream) {
     job.bit0 = d.bit0;
     job.r = d.r;
     for (uint32_t i = d.r; i < static_cast<uint32_t>(kMaxOut); ++i) job.a[i] = job.b[i] = nullptr;
-    const hipError_t e = verify_pieces(d.sz, d.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const WaveWalk ww = wave_walk(len, ns);
-        job.sz = len;
-        job.nstripes = static_cast<uint32_t>(ns);
-        job.cps = ww.cps;
-        job.wps = ww.wps;
-        job.gs_w = ww.gs_w;
-        job.gs_s = ww.gs_s;
+    const hipError_t e = launch_pieces(d.sz, d.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const uint32_t grid = fill_walk(job, len, ns);
         job.mismatch = d.mismatch + s0 * d.words;
         for (uint32_t i = 0; i < d.r; ++i) {
             job.a[i] = d.a[i] + b0 + s0 * d.a_sstride;
             job.b[i] = d.b[i] + b0 + s0 * d.b_sstride;
         }
-        return launch_job(reinterpret_cast<const void*>(rows_differ), ww.grid, kBlock, 0, stream, job);
+        return launch_job(reinterpret_cast<const void*>(rows_differ), grid, kBlock, 0, stream, job);
     });
     if (e == hipSuccess) t_last_kernel = "rows_differ";
     return e;
@@ -4764,44 +4709,36 @@ hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream) {
 
 hipError_t launch_locate(const VerifySpec& v, const uint8_t* q, uint32_t xbit, hipStream_t stream) {
     std::call_once(g_dispatch_once, init_dispatch);
-    static std::once_flag names_once;
-    std::call_once(names_once, [] {
-        for (int k = 1; k <= kRegK; ++k)
-            for (int r = 2; r <= kRegR; ++r)
-                snprintf(g_locate_names[k][r], sizeof g_locate_names[k][r], "matlocate_reg<%d,%d>", k, r);
-    });
     if (v.k < 1 || v.k > static_cast<uint32_t>(kRegK) || v.r < 2 || v.r > static_cast<uint32_t>(kRegR) ||
         v.coef_stride < v.k || !q || !v.mismatch || v.sz == 0 || v.nstripes == 0 || v.nstripes >= (1ull << 32) ||
         v.bit0 != 0 || v.r > xbit || uint64_t(xbit) + v.k > uint64_t(v.words) * 32)
         return hipErrorInvalidValue;
-    t_signal_flag = nullptr;
-    t_signal_used = false;
-    return g_locate_launch[v.k][v.r](v, LocateArgs{q, xbit}, stream);
+    reset_signal();
+    return g_locate_launch(v.k, v.r)(v, LocateArgs{q, xbit}, stream);
+}
+
+// The n tables of `coefs` into device memory, by one staged upload.
+static hipError_t upload_tabs(StagedUpload& up, const uint8_t* coefs, size_t n, hipStream_t stream) {
+    const hipError_t e = up.acquire(n * 5 * sizeof(uint32_t));
+    if (e != hipSuccess) return e;
+    uint32_t* ht = reinterpret_cast<uint32_t*>(up.host());
+    for (size_t i = 0; i < n; ++i) host_tab(ht + i * 5, coefs[i]);
+    return up.copy(n * 5 * sizeof(uint32_t), stream);
 }
 
 hipError_t locate_tables_upload(const uint8_t* q, uint32_t k, uint32_t c, hipStream_t stream, LocateTables* out) {
     if (!q || !out || k < 1 || c < 2) return hipErrorInvalidValue;
     if (stream_capturing(stream)) return hipErrorNotSupported;
-    const size_t n = size_t(k) * (c - 1), bytes = n * 5 * sizeof(uint32_t);
-    MixedRing::Slot* slot = nullptr;
-    hipError_t e = mixed_slot(bytes, &slot);
+    StagedUpload up;
+    const hipError_t e = upload_tabs(up, q, size_t(k) * (c - 1), stream);
     if (e != hipSuccess) return e;
-    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
-    for (size_t i = 0; i < n; ++i) std::memcpy(ht + i * 5, &kHostBank.w[uint32_t(q[i]) * 8], 5 * sizeof(uint32_t));
-    if ((e = hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-    out->dev = reinterpret_cast<const uint32_t*>(slot->dev);
-    out->slot = slot;
+    out->dev = reinterpret_cast<const uint32_t*>(up.dev());
+    out->slot = up.slot;
     return hipSuccess;
 }
 
 void locate_tables_release(const LocateTables& t, hipStream_t stream) {
-    MixedRing::Slot* slot = static_cast<MixedRing::Slot*>(t.slot);
-    if (!slot) return;
-    // the copy (and any launch made) reads the slot: it stays busy whatever happened
-    if (hipEventRecord(slot->ev, stream) == hipSuccess)
-        slot->busy = true;
-    else
-        (void)hipStreamSynchronize(stream);
+    if (t.slot) StagedUpload{static_cast<MixedRing::Slot*>(t.slot)}.done(stream);
 }
 
 hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint8_t* b0, uint32_t k, uint32_t xbit,
@@ -4811,8 +4748,7 @@ hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint
         d.sz == 0 || d.nstripes == 0 || d.nstripes >= (1ull << 32) || uint64_t(d.bit0) + d.r > xbit ||
         uint64_t(xbit) + k > uint64_t(d.words) * 32)
         return hipErrorInvalidValue;
-    t_signal_flag = nullptr;
-    t_signal_used = false;
+    reset_signal();
     LocateRowsJob job;
     job.a_sstride = d.a_sstride;
     job.b_sstride = d.b_sstride;
@@ -4824,14 +4760,8 @@ hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint
     job.pad_ = 0;
     job.qtab = qtab_dev;
     for (uint32_t i = d.r; i < static_cast<uint32_t>(kMaxOut); ++i) job.a[i] = job.b[i] = nullptr;
-    const hipError_t e = verify_pieces(d.sz, d.nstripes, [&](uint64_t b0off, uint64_t len, uint64_t s0, uint64_t ns) {
-        const WaveWalk ww = wave_walk(len, ns);
-        job.sz = len;
-        job.nstripes = static_cast<uint32_t>(ns);
-        job.cps = ww.cps;
-        job.wps = ww.wps;
-        job.gs_w = ww.gs_w;
-        job.gs_s = ww.gs_s;
+    const hipError_t e = launch_pieces(d.sz, d.nstripes, [&](uint64_t b0off, uint64_t len, uint64_t s0, uint64_t ns) {
+        const uint32_t grid = fill_walk(job, len, ns);
         job.bits = d.mismatch + s0 * d.words;
         job.a0 = a0 + b0off + s0 * d.a_sstride;
         job.b0 = b0 + b0off + s0 * d.b_sstride;
@@ -4839,7 +4769,7 @@ hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint
             job.a[i] = d.a[i] + b0off + s0 * d.a_sstride;
             job.b[i] = d.b[i] + b0off + s0 * d.b_sstride;
         }
-        return launch_job(reinterpret_cast<const void*>(rows_locate), ww.grid, kBlock, 0, stream, job);
+        return launch_job(reinterpret_cast<const void*>(rows_locate), grid, kBlock, 0, stream, job);
     });
     if (e == hipSuccess) t_last_kernel = "rows_locate";
     return e;
@@ -4873,41 +4803,26 @@ hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream) {
         p.nstripes >= (1ull << 32))
         return hipErrorInvalidValue;
     if (stream_capturing(stream)) return hipErrorNotSupported;
-    t_signal_flag = nullptr;
-    t_signal_used = false;
+    reset_signal();
     const bool reg = p.k <= static_cast<uint32_t>(kRegK);
-    const size_t n = size_t(p.nb) * p.k, bytes = n * 5 * sizeof(uint32_t);
-    MixedRing::Slot* slot = nullptr;
-    hipError_t e = mixed_slot(bytes, &slot);
+    StagedUpload up;
+    hipError_t e = upload_tabs(up, p.rows, size_t(p.nb) * p.k, stream);
     if (e != hipSuccess) return e;
-    uint32_t* ht = reinterpret_cast<uint32_t*>(slot->host);
-    for (size_t i = 0; i < n; ++i) std::memcpy(ht + i * 5, &kHostBank.w[uint32_t(p.rows[i]) * 8], 5 * sizeof(uint32_t));
-    if ((e = hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     CorrectJob job;
     job.bstride = p.bstride;
     job.sstride = p.sstride;
     job.k = p.k;
     job.nb = p.nb;
     job.pad_ = 0;
-    job.tabs = reinterpret_cast<const uint32_t*>(slot->dev);
+    job.tabs = reinterpret_cast<const uint32_t*>(up.dev());
     const void* const fn = reg ? kFns[p.k] : reinterpret_cast<const void*>(rows_correct);
-    e = verify_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const WaveWalk ww = wave_walk(len, ns);
-        job.sz = len;
-        job.nstripes = static_cast<uint32_t>(ns);
-        job.cps = ww.cps;
-        job.wps = ww.wps;
-        job.gs_w = ww.gs_w;
-        job.gs_s = ww.gs_s;
+    e = launch_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const uint32_t grid = fill_walk(job, len, ns);
         job.verdict = p.verdict + s0;
         job.blocks = p.blocks + b0 + s0 * p.sstride;
-        return launch_job(fn, ww.grid, kBlock, 0, stream, job);
+        return launch_job(fn, grid, kBlock, 0, stream, job);
     });
-    // the copy (and any launch made) reads the slot: it stays busy whatever happened
-    if (hipEventRecord(slot->ev, stream) == hipSuccess)
-        slot->busy = true;
-    else
-        (void)hipStreamSynchronize(stream);
+    up.done(stream);
     if (e == hipSuccess) t_last_kernel = reg ? kNames[p.k] : "rows_correct";
     return e;
 }
@@ -4918,8 +4833,7 @@ hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream) {
         (!m.ids_host && !m.ids_dev) || m.sz == 0 || m.nstripes == 0)
         return hipErrorInvalidValue;
     if (stream_capturing(stream)) return hipErrorNotSupported;
-    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
-    t_signal_used = false;
+    reset_signal();
     switch (m.k) {
     case 1: return launch_mixed_k<1>(m, stream);
     case 2: return launch_mixed_k<2>(m, stream);
@@ -4979,8 +4893,7 @@ bool wide_launch_ok(uint32_t k, uint32_t r, uint64_t sz, uint64_t nstripes) {
 
 hipError_t launch_apply(const ApplySpec& a, hipStream_t stream) {
     uint32_t* const sig = t_signal_flag;  // a request covers this launch only
-    t_signal_flag = nullptr;
-    t_signal_used = false;
+    reset_signal();
     std::call_once(g_dispatch_once, init_dispatch);
     const uint32_t k = a.k, r = a.r;
     const bool wide = k > static_cast<uint32_t>(kMaxIn);
@@ -5045,8 +4958,7 @@ hipError_t launch_one(const ApplySpec& a, hipStream_t stream, uint32_t* flag_dev
     if (a.k < 1 || a.k > 4 || a.r < 1 || a.r > 8 || a.nstripes != 1 || a.sz == 0 || a.sz % 16 || a.sz > 4096 ||
         a.accumulate || a.coef_stride < a.k)
         return hipErrorInvalidValue;
-    t_signal_flag = nullptr;  // an unconsumed launch_apply request must not outlive this launch
-    t_signal_used = false;
+    reset_signal();
     const uint32_t units = static_cast<uint32_t>(a.sz / 16);
     // host_in: the caller has NOT copied the inputs anywhere the kernel can
     // read; they must fit the argument block, or the launch is refused (no
@@ -5063,10 +4975,7 @@ hipError_t launch_one(const ApplySpec& a, hipStream_t stream, uint32_t* flag_dev
     job.units = units;
     job.r = a.r;
     for (uint32_t i = 0; i < a.r; ++i)
-        for (uint32_t j = 0; j < a.k; ++j) {
-            const uint32_t* w = &kHostBank.w[uint32_t(a.coef[size_t(i) * a.coef_stride + j]) * 8];
-            std::memcpy(&job.tab[(i * a.k + j) * 5], w, 5 * sizeof(uint32_t));
-        }
+        for (uint32_t j = 0; j < a.k; ++j) host_tab(&job.tab[(i * a.k + j) * 5], a.coef[size_t(i) * a.coef_stride + j]);
     typedef void (*OneFn)(const OneJob);
     typedef void (*OneInlFn)(const OneJobInline);
     static const OneFn kOne[5] = {nullptr, matapply_one<1, false, OneJob>, matapply_one<2, false, OneJob>,
@@ -5107,8 +5016,7 @@ hipError_t launch_apply_pair(const ApplySpec& x, const ApplySpec& y, hipStream_t
     const ApplySpec& b = x.r >= y.r ? y : x;
     const PairLaunch f = g_pair_launch[a.k][a.r][b.r];
     if (!f) return hipErrorNotSupported;
-    t_signal_flag = nullptr;
-    t_signal_used = false;
+    reset_signal();
     return f(a, b, stream);
 }
 
