@@ -7,10 +7,10 @@ inputs all fit keeps its single register-loaded phase.  No GPU: the kernels are
 generated and compiled for gfx950 by hipRTC here."""
 import os
 import re
-import subprocess
-import sys
 
 import pytest
+
+import jit_forms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,18 +31,10 @@ def generated(tmp_path, monkeypatch, k, m, decode):
     registry is per process, and another test's code may already hold the
     kernel in memory (fec_new prefetches the kernels the in-tree cache holds),
     which would compile -- and dump -- nothing."""
-    dump = tmp_path / "dump"
-    dump.mkdir()
-    env = dict(os.environ, ZFEC_HIP_JIT_CACHE=str(tmp_path / "cache"), ZFEC_HIP_JIT_DUMP=str(dump))
     nums = place(list(range(m - k, m)), k) if decode else list(range(k, m))
-    prog = ("import sys; sys.path.insert(0, %r)\n"
-            "from zfec_amd import capi\n"
-            "c = capi.Code(%d, %d)\n"
-            "c.%s(%r)\n" % (ROOT, k, m, "jit_prepare_decode" if decode else "jit_prepare_encode", nums))
-    subprocess.run([sys.executable, "-c", prog], env=env, check=True, timeout=300)
-    files = list(dump.glob("zfec_hip_bitslice_k%d_r*.hip" % k))
+    files = list(jit_forms.generated_sources(tmp_path, k, m, "dec" if decode else "enc", nums).values())
     assert len(files) == 1, files
-    return files[0].read_text()
+    return files[0]
 
 
 # decodes from the last k blocks: r = 18 / 27 / 20 rows on 2 / 3 / 2 tiles, phases of 4 with a

@@ -1096,7 +1096,8 @@ hipError_t launch_matapply_jit(const ApplySpec& a, hipStream_t stream, const cha
     const uint64_t waves = cps * a.nstripes;
     if (waves >= (1ull << 32) - (1ull << 24)) return hipErrorNotSupported;
     const uint64_t need = (waves + upb - 1) / upb;
-    const uint64_t cap = uint64_t(L.num_cu) * L.blocks_per_cu * 64;
+    uint64_t cap = uint64_t(L.num_cu) * L.blocks_per_cu * 64;
+    if (cfg->grid_cap) cap = std::min<uint64_t>(cap, cfg->grid_cap);  // test hook: walk grid-stride at small shapes
     const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
     const uint64_t gwaves = uint64_t(grid) * upb;  // units per grid-stride step
     // struct Args of the generated source: 3 x u64, 4 x u32, k + r pointers
