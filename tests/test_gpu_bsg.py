@@ -3,13 +3,21 @@ coefficient matrix as run-time data (zfec_amd/csrc/kernels.hip): it serves
 every wide-code launch no compiled JIT kernel serves -- above all decodes of an
 erasure pattern seen for the first time (zfec/fec.c:527-557 decodes every
 pattern with one code path).  Bit-exact against the CPU oracle across code
-shapes (every rows-per-wave instantiation, rows not a multiple of 4, k up to
-32), block sizes around the 4 KiB unit and its overlapping last unit, batched
-strided stripes at misaligned bases with guard bytes, and random erasure
-patterns; and codes of more than 32 inputs in one pass, their block pointers
-and coefficients read from a device-side table (the reference takes any
-1 <= k <= m <= 256, zfec/fec.c:437-440; its own benchmark times 94/100,
-benchmark-zfec/Main.hs:17)."""
+shapes (rows not a multiple of 4, k up to 32), block sizes around the 4 KiB
+unit and its overlapping last unit, batched strided stripes at misaligned
+bases with guard bytes, and random erasure patterns; and codes of more than 32
+inputs in one pass, their block pointers and coefficients read from a
+device-side table (the reference takes any 1 <= k <= m <= 256,
+zfec/fec.c:437-440; its own benchmark times 94/100, benchmark-zfec/Main.hs:17).
+
+launch_bsg shrinks the rows per wave of a launch with little work, so the small
+shapes above all run matapply_bsg<2,2...> (<1,2...> for r <= 4).  Every
+rows-per-wave instantiation, RT = 1, 2, 3, 4, 5, 6, 8, 10, 12 in the arguments
+form and the table form, is launched by name by test_bsg_every_instantiation,
+whose batches have the >= 4 x CUs units that keep a large RT; bsg_name mirrors
+the launcher's choice, and every test asserts the exact name.  The grid-stride
+walk with its carry and its prefetch across units runs under
+ZFEC_HIP_GRID_CAP, and every coefficient 1..255 goes through the offset bank."""
 
 import numpy as np
 import pytest
@@ -17,6 +25,7 @@ import pytest
 import zfec_amd
 from zfec_amd import capi
 from oracle import oracle
+from guarded_batch import Batch, check_rows, encode_case, walk_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +58,39 @@ def place(nums, k):
     return [s if s is not None else next(sec) for s in slots]
 
 
-# (k, m), k * (m - k) >= 24: rows per wave RT = ceil((m - k) / 4) covers 1, 2, 3, 4, 5, 6, 8, 10, 12
+BSG_RT = (1, 2, 3, 4, 5, 6, 8, 10, 12)
+CHUNK = 4096  # bytes of each block per unit (kernels.hip kBsgChunk)
+
+
+def cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def bsg_groups(r, rt):
+    return -(-r // (4 * rt))
+
+
+def bsg_name(k, r, units, ncu):
+    """kernels.hip launch_bsg: the smallest instantiated RT >= ceil(r / 4); a
+    launch of fewer than 4 x CUs (unit, row group) pairs steps down to smaller
+    row groups, not below RT 2.  Pointers and coefficients come from a
+    device-side table when there is more than one row group, past 32 inputs and
+    past 48 rows; else from the kernel arguments."""
+    ri = 0
+    while ri + 1 < len(BSG_RT) and BSG_RT[ri] < -(-r // 4):
+        ri += 1
+    while ri > 1 and units * bsg_groups(r, BSG_RT[ri]) < 4 * ncu:
+        ri -= 1
+    tbl = bsg_groups(r, BSG_RT[ri]) > 1 or k > 32 or r > 48
+    return "matapply_bsg<%d,2%s>" % (BSG_RT[ri], ",tbl" if tbl else "")
+
+
+def units_of(sz, ns=1):
+    return ns * -(-sz // CHUNK)
+
+
+# (k, m), k * (m - k) >= 24: ceil((m - k) / 4) covers 1..12, but at one to three units per launch
+# the launcher steps every one of them down to RT 2 (RT 1 for r <= 4), most in the table form
 SHAPES = [(7, 11), (6, 12), (6, 13), (10, 16), (4, 16), (5, 20), (7, 24), (20, 40), (8, 31), (6, 37), (20, 60),
           (32, 70), (12, 60)]
 
@@ -62,7 +103,7 @@ def test_bsg_encode_decode_vs_oracle(bsg_only, k, m):
         ins = [torch.from_numpy(data[i]).cuda() for i in range(k)]
         out = zfec_amd.Encoder(k, m).encode(ins)
         torch.cuda.synchronize()
-        assert capi.last_kernel_name().startswith("matapply_bsg"), capi.last_kernel_name()
+        assert capi.last_kernel_name() == bsg_name(k, m - k, units_of(sz), cus()), capi.last_kernel_name()
         par = torch.stack(out[k:]).cpu().numpy()
         assert (par == oracle.encode(k, m, data)).all(), (k, m, sz)
         nums = sorted(int(x) for x in rng.choice(m, size=k, replace=False))
@@ -90,7 +131,7 @@ def test_bsg_batched_strided_misaligned(bsg_only, k, m, sz, ns):
     code.encode_batch(src.data_ptr() + base_in, ld, k * ld, dst.data_ptr() + base_out, ld, r * ld,
                       list(range(k, m)), sz, ns, stream=st)
     torch.cuda.synchronize()
-    assert capi.last_kernel_name().startswith("matapply_bsg"), capi.last_kernel_name()
+    assert capi.last_kernel_name() == bsg_name(k, r, units_of(sz, ns), cus()), capi.last_kernel_name()
     d = dst.cpu().numpy()
     assert (d[:base_out] == 0xA5).all() and (d[base_out + ns * r * ld:] == 0xA5).all()
     out = d[base_out:base_out + ns * r * ld].reshape(ns, r, ld)
@@ -124,7 +165,7 @@ def test_bsg_fresh_erasure_patterns(bsg_only):
         code.decode_batch(rv.data_ptr(), ld, k * ld, rec.data_ptr(), ld, len(miss) * ld, sl, sz, ns, stream=st)
         torch.cuda.synchronize()
         if len(miss) * k >= 24:
-            assert capi.last_kernel_name().startswith("matapply_bsg"), capi.last_kernel_name()
+            assert capi.last_kernel_name() == bsg_name(k, len(miss), units_of(sz, ns), cus()), capi.last_kernel_name()
         assert bool(torch.equal(rec[:, :, :sz], data[:, miss, :sz])), nums
         s = int(rng.integers(0, ns))
         want = oracle.decode(k, m, rv[s, :, :sz].cpu().numpy(), sl)
@@ -145,7 +186,10 @@ def test_bsg_off_gives_identical_bytes():
             try:
                 outs[gen] = torch.stack(zfec_amd.Encoder(k, m).encode(ins)[k:])
                 torch.cuda.synchronize()
-                assert capi.last_kernel_name().startswith("matapply_bsg" if gen else "matapply_lds")
+                if gen:
+                    assert capi.last_kernel_name() == bsg_name(k, m - k, units_of(sz), cus()), capi.last_kernel_name()
+                else:
+                    assert capi.last_kernel_name().startswith("matapply_lds")
             finally:
                 capi.generic_mode(prev)
     finally:
@@ -166,8 +210,8 @@ def test_bsg_wide_k_vs_oracle(bsg_only, k, m):
         ins = [torch.from_numpy(data[i]).cuda() for i in range(k)]
         out = zfec_amd.Encoder(k, m).encode(ins)
         torch.cuda.synchronize()
-        assert capi.last_kernel_name().startswith("matapply_bsg") and capi.last_kernel_name().endswith(",tbl>"), \
-            capi.last_kernel_name()
+        want = bsg_name(k, m - k, units_of(sz), cus())
+        assert capi.last_kernel_name() == want and want.endswith(",tbl>"), capi.last_kernel_name()
         par = torch.stack(out[k:]).cpu().numpy()
         assert (par == oracle.encode(k, m, data)).all(), (k, m, sz)
         # decode from a random k of the m blocks
@@ -196,7 +240,10 @@ def test_bsg_wide_k_batched_guards(bsg_only):
         code.encode_batch(src.data_ptr() + 7, ld, k * ld, dst.data_ptr() + 9, ld, r * ld, list(range(k, m)), sz, ns,
                           stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
-        assert capi.last_kernel_name().startswith("matapply_bsg" if gen else "matapply_lds"), capi.last_kernel_name()
+        if gen:
+            assert capi.last_kernel_name() == bsg_name(k, r, units_of(sz, ns), cus()), capi.last_kernel_name()
+        else:
+            assert capi.last_kernel_name().startswith("matapply_lds"), capi.last_kernel_name()
         outs.append(dst.cpu().numpy())
     capi.generic_mode(1)
     assert np.array_equal(outs[0], outs[1])
@@ -225,3 +272,166 @@ def test_bsg_wide_k_table_ring_reuse(bsg_only):
     torch.cuda.synchronize()
     for nums, got in results:
         assert (torch.stack(got).cpu().numpy() == data).all(), nums
+
+
+# ---- the grid-stride walk, under ZFEC_HIP_GRID_CAP ---------------------------------------------
+# (sz, cap): 20481 bytes are 6 units of 4 KiB (cps), the last overlapping its neighbour by 4095
+# bytes; 5 workgroups give gs_s = 0, gs_c = 5.  8193 bytes are 3 units, the last overlapping by
+# 1; 7 workgroups give gs_s = 2, gs_c = 1.
+WALK_GEOM = [(20481, 5), (8193, 7)]
+WALK_NS = 7
+# (k, m): the arguments form; the table form in 5 row groups of 8 rows (the launcher's cut of 40
+# rows at this size); the table form because k > 32, 6 rows in one group
+WALK_SHAPES = [(6, 13), (20, 60), (94, 100)]
+
+
+def run_walk(knobs, k, m, ns, sz, cap):
+    """One encode of every parity block under the capped grid: each workgroup
+    makes at least three steps with gs_c != 0; every stripe against the oracle,
+    guard bytes included; without the hook, the same kernel and bytes."""
+    r = m - k
+    cps = units_of(sz)
+    name = bsg_name(k, r, ns * cps, cus())
+    ng = bsg_groups(r, int(name[13:name.index(",")])) if name.endswith(",tbl>") else 1
+    steps = walk_steps(ns * ng * cps, cps, cap)
+    rng = np.random.default_rng(k * 1000 + m + sz)
+    blocks, want, index = encode_case(k, m, rng.integers(0, 256, size=(ns, k, sz), dtype=np.uint8))
+    job = Batch(k, m, "enc", index, blocks, r)
+    knobs(ZFEC_HIP_GRID_CAP=cap)
+    got_name = job.launch()
+    knobs(ZFEC_HIP_GRID_CAP=0)
+    assert got_name == name, (k, m, sz, got_name)
+    check_rows(job.rows((k, m, sz, "capped")), want, (k, m, sz, cap))
+    capped = job.dst.clone()
+    assert job.launch() == name, "the hook changed the kernel chosen"
+    assert torch.equal(job.dst, capped), (k, m, sz, "capped and uncapped bytes differ")
+    return name, steps
+
+
+@pytest.mark.parametrize("geom", [0, 1], ids=["cps6-cap5", "cps3-cap7"])
+@pytest.mark.parametrize("k,m", WALK_SHAPES)
+def test_bsg_grid_stride_walk(bsg_only, knobs, k, m, geom):
+    """The walk runs one step ahead of itself (s2, c2, with the same carry) to
+    load the next unit's first inputs during the current unit's last phase."""
+    sz, cap = WALK_GEOM[geom]
+    assert (cap // units_of(sz), cap % units_of(sz)) == ((0, 5), (2, 1))[geom]
+    name, steps = run_walk(knobs, k, m, WALK_NS, sz, cap)
+    assert name == ("matapply_bsg<2,2>" if (k, m) == (6, 13) else "matapply_bsg<2,2,tbl>") and steps >= 3
+
+
+# ---- every instantiation by name -----------------------------------------------------------------
+# (k, r, sz, eighths): a batch of `eighths` x CUs / 2 units, i.e. eighths / 8 of the 4 x CUs below
+# which launch_bsg steps down.  8: the RT of ceil(r / 4) holds, in the arguments form (one row
+# group).  5: one group of the first RT is too few (5/8), two groups of the next smaller RT are
+# enough (10/8), so the launch stops there in the table form, its second group short (r = 19:
+# groups of 16 and 3 rows on RT 4).  0: three stripes; nothing shrinks below RT 2, and RT 1 is
+# chosen by r <= 4 alone.  RT 1 and RT 12 in the table form need k > 32: r <= 4 makes one group,
+# and past 48 rows a k <= 32 call is cut before it reaches the launcher.  Odd k: the last phase
+# holds one input; r not a multiple of 4: the last waves own fewer rows.
+INSTANCES = {
+    "matapply_bsg<1,2>": (9, 3, 8193, 0),
+    "matapply_bsg<2,2>": (5, 7, 4097, 0),
+    "matapply_bsg<3,2>": (5, 9, 4096, 8),
+    "matapply_bsg<4,2>": (6, 13, 8193, 8),
+    "matapply_bsg<5,2>": (7, 19, 4096, 8),
+    "matapply_bsg<6,2>": (5, 22, 8193, 8),
+    "matapply_bsg<8,2>": (6, 30, 4096, 8),
+    "matapply_bsg<10,2>": (7, 37, 8193, 8),
+    "matapply_bsg<12,2>": (5, 47, 4096, 8),
+    "matapply_bsg<1,2,tbl>": (33, 3, 8193, 0),
+    "matapply_bsg<2,2,tbl>": (5, 12, 4097, 0),
+    "matapply_bsg<3,2,tbl>": (7, 16, 8193, 5),
+    "matapply_bsg<4,2,tbl>": (5, 19, 4096, 5),
+    "matapply_bsg<5,2,tbl>": (7, 23, 8193, 5),
+    "matapply_bsg<6,2,tbl>": (5, 31, 4096, 5),
+    "matapply_bsg<8,2,tbl>": (6, 39, 8193, 5),
+    "matapply_bsg<10,2,tbl>": (5, 46, 4096, 5),
+    "matapply_bsg<12,2,tbl>": (33, 49, 4096, 5),
+}
+
+
+def instance_stripes(sz, eighths):
+    return -(-(eighths * cus() // 2) // units_of(sz)) if eighths else 3
+
+
+def test_bsg_instance_table_names_all_18():
+    names = {"matapply_bsg<%d,2%s>" % (rt, t) for rt in BSG_RT for t in ("", ",tbl")}
+    assert len(names) == 18 and set(INSTANCES) == names
+    for want, (k, r, sz, eighths) in INSTANCES.items():
+        assert bsg_name(k, r, units_of(sz, instance_stripes(sz, eighths)), cus()) == want, want
+
+
+def run_instance(k, r, sz, ns, want_name, knobs=None, cap=0):
+    """Encode r parity rows of the k/(k + r) code over ns stripes, every stripe
+    against the oracle."""
+    m = k + r
+    rng = np.random.default_rng(k * 1000 + r + sz)
+    blocks, want, index = encode_case(k, m, rng.integers(0, 256, size=(ns, k, sz), dtype=np.uint8))
+    job = Batch(k, m, "enc", index, blocks, r)
+    assert job.src.numel() + job.dst.numel() < 1 << 30
+    if cap:
+        knobs(ZFEC_HIP_GRID_CAP=cap)
+    got_name = job.launch()
+    if cap:
+        knobs(ZFEC_HIP_GRID_CAP=0)
+    assert got_name == want_name, (k, r, sz, ns, got_name)
+    check_rows(job.rows((want_name, cap)), want, (want_name, cap))
+
+
+@pytest.mark.parametrize("name", list(INSTANCES))
+def test_bsg_every_instantiation(bsg_only, name):
+    """Each RT is its own unrolled kernel, with its own bsg_phase_bytes padding,
+    coefficient byte packing and register pressure; each runs in both forms."""
+    k, r, sz, eighths = INSTANCES[name]
+    ns = instance_stripes(sz, eighths)
+    assert bsg_name(k, r, units_of(sz, ns), cus()) == name
+    run_instance(k, r, sz, ns, name)
+
+
+def test_bsg_large_rt_grid_stride_walk(bsg_only, knobs):
+    """matapply_bsg<10,2> over three-unit stripes on 61 workgroups (gs_s = 20,
+    gs_c = 1): a large-RT form with the carry and the prefetch across units."""
+    name = "matapply_bsg<10,2>"
+    k, r, sz, eighths = INSTANCES[name]
+    ns = instance_stripes(sz, eighths)
+    assert units_of(sz) == 3 and walk_steps(units_of(sz, ns), 3, 61) >= 3
+    run_instance(k, r, sz, ns, name, knobs, 61)
+
+
+# ---- every coefficient --------------------------------------------------------------------------
+
+def test_bsg_every_coefficient(bsg_only):
+    """Every row of the offset bank (g_bsg: 256 coefficients x 16 LDS offsets):
+    the 32/72 encode (253 of the 255 nonzero coefficients) and decodes chosen
+    until their matrices have used the remaining ones, each against the oracle.
+    Coefficient 0 is the padding rows and inputs of the walk order."""
+    k, m, sz = 32, 72, 4096
+    rng = np.random.default_rng(256)
+    data = rng.integers(0, 256, size=(k, sz), dtype=np.uint8)
+    ins = [torch.from_numpy(data[i]).cuda() for i in range(k)]
+    enc = zfec_amd.Encoder(k, m).encode(ins)
+    torch.cuda.synchronize()
+    assert capi.last_kernel_name() == bsg_name(k, m - k, 1, cus()), capi.last_kernel_name()
+    assert (torch.stack(enc[k:]).cpu().numpy() == oracle.encode(k, m, data)).all()
+    cov = set(np.asarray(oracle.enc_matrix(k, m)).reshape(m, k)[k:].flatten().tolist())
+    dec = zfec_amd.Decoder(k, m)
+    tries = 0
+    while not cov >= set(range(1, 256)) and tries < 400:
+        tries += 1
+        nums = sorted(int(x) for x in rng.choice(m, size=k, replace=False))
+        sl = place(nums, k)
+        miss = [i for i in range(k) if sl[i] >= k]
+        if len(miss) * k < 24:
+            continue
+        dm = np.asarray(oracle.decode_matrix(k, m, sl)).reshape(k, k)
+        new = set(dm[miss].flatten().tolist()) - cov
+        if not new:
+            continue
+        cov |= new
+        got = dec.decode([enc[n] for n in nums], nums)
+        torch.cuda.synchronize()
+        assert capi.last_kernel_name() == bsg_name(k, len(miss), 1, cus()), capi.last_kernel_name()
+        recv = np.stack([(data[n] if n < k else enc[n].cpu().numpy()) for n in sl])
+        assert (torch.stack(got).cpu().numpy()[miss] == oracle.decode(k, m, recv, sl)).all(), nums
+        assert (torch.stack(got).cpu().numpy() == data).all(), nums
+    assert cov >= set(range(1, 256)), sorted(set(range(1, 256)) - cov)

@@ -7,7 +7,11 @@ decodes every pattern with one code path).  Bit-exact against the CPU oracle
 for every rows-per-wave instantiation (RT = 1..10) and wave count (1..4 row
 tiles), block sizes around the 2 KiB unit and its overlapping last unit,
 batched strided stripes at misaligned bases with guard bytes, random erasure
-patterns, and against matapply_bsg (generic mode 1) on the same launch."""
+patterns, and against matapply_bsg (generic mode 1) on the same launch.  Every
+form -- one wave, LDS phases with the addresses in the arguments or the table,
+shared combinations in one and in two row groups, inputs split over the waves
+with equal and unequal row groups -- also walks grid-stride with a carry, under
+ZFEC_HIP_GRID_CAP (test_bsr_grid_stride_walk)."""
 
 import numpy as np
 import pytest
@@ -15,6 +19,7 @@ import pytest
 import zfec_amd
 from zfec_amd import capi
 from oracle import oracle
+from guarded_batch import Batch, check_rows, decode_case, encode_case, walk_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -46,11 +51,24 @@ def place(nums, k):
     return [s if s is not None else next(sec) for s in slots]
 
 
-def bsr_name(r, units=0):
+def bsr_waves(r, units=0):
     """kernels.hip bsr_tiles: one wave for r <= 10; two for 11-16 rows, and
     for 17-20 rows in launches of >= 2048 units; else four."""
-    nw = 1 if r <= 10 else 2 if r <= 16 or (r <= 20 and units * 2 >= 256 * 16) else 4
-    return "matapply_bsr<%d>" % (-(-r // nw))
+    return 1 if r <= 10 else 2 if r <= 16 or (r <= 20 and units * 2 >= 256 * 16) else 4
+
+
+def bsr_name(r, units=0):
+    return "matapply_bsr<%d>" % (-(-r // bsr_waves(r, units)))
+
+
+def bsr_exact(k, r, units=0):
+    """The exact name of a launch_bsr launch (k <= 32, r <= 40): the one-wave
+    form, the LDS-phase form with the routine addresses in the arguments, or
+    past kBsrArgAddrs = 432 of them (waves x inputs x rows per wave) in the
+    device-side table."""
+    nw = bsr_waves(r, units)
+    rt = -(-r // nw)
+    return "matapply_bsr<%d%s>" % (rt, "" if nw == 1 else ",lds,tbl" if nw * k * rt > 432 else ",lds")
 
 
 def is_bsr(name, r, units=0):
@@ -496,3 +514,71 @@ def test_bsr_graph_capture(bsr_only, k, m):
     eager = enc.encode(ins)
     torch.cuda.synchronize()
     assert (torch.stack(eager[k:]).cpu().numpy() == want).all()
+
+
+# ---- the grid-stride walk of every form, under ZFEC_HIP_GRID_CAP ---------------------------
+# (sz, cap): 10241 bytes are 6 units of 2 KiB (cps), the last overlapping its neighbour by 2047
+# bytes; 5 workgroups give gs_s = 0, gs_c = 5, a carry on five steps of six.  4097 bytes are 3
+# units, the last overlapping by 1; 7 workgroups give gs_s = 2, gs_c = 1.
+WALK_GEOM = [(10241, 5), (4097, 7)]
+
+# id -> (k, m, operation, stripes per geometry, the launch's kernel on a 256-CU device).
+# Stripes: 7, or what the LDS-phase form needs of a k >= 64 launch (units x row groups x 8 waves
+# >= 8 x CUs, kernels.hip bsr_wide_ok): 200/256 258 units, 128/256 (two row groups) 132 and 129.
+WALK_FORMS = {
+    "solo-10_16": (10, 16, "enc", (7, 7), "matapply_bsr<6>"),          # for (v = blockIdx.x; ...; v += gridDim.x)
+    "lds2-9_20": (9, 20, "enc", (7, 7), "matapply_bsr<6,lds>"),        # odd k: a short last DMA phase
+    "lds4-13_30": (13, 30, "enc", (7, 7), "matapply_bsr<5,lds>"),      # phases of 4, the last of 1
+    "tbl-20_60": (20, 60, "enc", (7, 7), "matapply_bsr<10,lds,tbl>"),
+    "dec-20_60": (20, 60, "dec", (7, 7), "matapply_bsr<5,lds>"),       # first-seen, from parity only: 20 rows
+    "tbl-40_60": (40, 60, "enc", (7, 7), "matapply_bsr<5,lds,tbl>"),   # k > 32
+    "cmb-200_256": (200, 256, "enc", (43, 86), "matapply_bsr<7,lds,tbl,cmb>"),  # one row group
+    "cmb-128_256": (128, 256, "enc", (22, 43), "matapply_bsr<8,lds,tbl,cmb>"),  # two: (group, stripe) walk
+    "ks-94_100": (94, 100, "enc", (7, 7), "matapply_bsr<6,ks,tbl>"),   # one group of 6 rows
+    "ks-64_109": (64, 109, "enc", (7, 7), "matapply_bsr<8,ks,tbl>"),   # groups of 7, 8, 7, 8, 7, 8 rows
+}
+
+
+def walk_name(k, r, units):
+    """(kernel, row groups of its walk) by this file's mirrors of the launchers."""
+    if k <= 32 and r <= 40:
+        return bsr_exact(k, r, units), 1
+    name = tbl_name(r, units, k)
+    if ",ks," in name:
+        return name, 1 if r <= 10 else -(-r // 8)
+    return name, -(-r // 64)
+
+
+@pytest.mark.parametrize("geom", [0, 1], ids=["cps6-cap5", "cps3-cap7"])
+@pytest.mark.parametrize("form", list(WALK_FORMS))
+def test_bsr_grid_stride_walk(bsr_only, knobs, form, geom):
+    """Every form walks (stripe, unit) pairs -- (row group, stripe, unit) triples
+    in the table forms -- grid-stride with a carry from unit into stripe: c +=
+    gs_c; s += gs_s; if (c >= cps) { c -= cps; ++s; }.  Each workgroup makes at
+    least three steps with gs_c != 0, on blocks whose last unit overlaps its
+    neighbour.  Every stripe against the oracle, guard bytes included; the same
+    call without the hook must take the same kernel and give the same bytes."""
+    k, m, op, nss, listed = WALK_FORMS[form]
+    sz, cap = WALK_GEOM[geom]
+    ns = nss[geom]
+    cps = -(-sz // 2048)
+    rng = np.random.default_rng(k * 1000 + m + sz)
+    data = rng.integers(0, 256, size=(ns, k, sz), dtype=np.uint8)
+    if op == "enc":
+        blocks, want, index = encode_case(k, m, data)
+    else:
+        blocks, want, index = decode_case(k, m, data, list(range(k, 2 * k)))
+    r = want.shape[1]
+    name, ng = walk_name(k, r, ns * cps)
+    assert name == listed, (name, listed)
+    assert (cap // cps, cap % cps) == ((0, 5), (2, 1))[geom]
+    assert walk_steps(ns * ng * cps, cps, cap) >= 3
+    job = Batch(k, m, op, index, blocks, r)
+    knobs(ZFEC_HIP_GRID_CAP=cap)
+    got_name = job.launch()
+    knobs(ZFEC_HIP_GRID_CAP=0)
+    assert got_name == name, (form, sz, got_name)
+    check_rows(job.rows((form, sz, "capped")), want, (form, sz, cap))
+    capped = job.dst.clone()
+    assert job.launch() == name, "the hook changed the kernel chosen"
+    assert torch.equal(job.dst, capped), (form, sz, "capped and uncapped bytes differ")

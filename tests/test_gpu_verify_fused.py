@@ -8,9 +8,10 @@ byte for byte after every call, and the kernel name checked.
 Most cases run under ZFEC_HIP_VERIFY_FUSED_MIN=1 so that launches of a few
 2-KiB units take the fused kernels; the gate itself is checked at the default.
 
-The bit-sliced kernels' grid is capped at CUs x 1024 workgroups, not by
-ZFEC_HIP_GRID_CAP, so their grid-stride walk (more than 2^18 units on 256 CUs,
-512 MiB per block) is not reached here; the walk's code is matapply_bsr's."""
+The bit-sliced kernels' grid is capped at CUs x 1024 workgroups (2^18 units on
+256 CUs, 512 MiB per block), or by ZFEC_HIP_GRID_CAP when that is lower: with
+it test_fused_grid_stride_walk walks every form grid-stride, with the carry
+from unit into stripe, over blocks whose last unit overlaps its neighbour."""
 import numpy as np
 import pytest
 
@@ -130,6 +131,55 @@ def test_fused_bits_equal_two_step_bits(shape, knobs):
         for p, cor in pats.items():
             assert (case.run(code, cor, ("two-step", shape, bname, p)) == fused[p]).all(), (shape, bname, p)
         assert any(w.any() for w in fused.values())
+
+
+# ---- the grid-stride walk ------------------------------------------------------------------
+# (sz, cap) as in test_gpu_bsr.py: 6 units per stripe on 5 workgroups (gs_s = 0, gs_c = 5, the
+# last unit overlapping by 2047 bytes), 3 units on 7 workgroups (gs_s = 2, gs_c = 1, by 1 byte)
+WALK_GEOM = [(10241, 5), (4097, 7)]
+WALK_NS = 7
+WALK_SHAPES = [(10, 16, 16), (6, 22, 22), (5, 25, 25), (20, 60, 60)]  # <6>, <8,lds>, <5,lds>, <10,lds,tbl>
+
+
+def every_unit_pattern(k, c, ns, sz):
+    """One flipped byte in every (stripe, unit) pair, each unit of a stripe in
+    another check block and at a byte no other unit covers (a unit's first
+    byte; the overlapping last unit's last byte): every walk iteration must
+    report, and a unit run twice or not at all changes the words."""
+    cps = -(-sz // 2048)
+    assert cps <= c
+    return [(s, k + (s * cps + u) % c, sz - 1 if u == cps - 1 else u * 2048, 1 + (s + u) % 255)
+            for s in range(ns) for u in range(cps)]
+
+
+@pytest.mark.parametrize("geom", [0, 1], ids=["cps6-cap5", "cps3-cap7"])
+@pytest.mark.parametrize("shape", WALK_SHAPES, ids=["%d-%d-%d" % s for s in WALK_SHAPES])
+def test_fused_grid_stride_walk(shape, geom, knobs):
+    """ZFEC_HIP_GRID_CAP below the units of the call: each workgroup makes at
+    least three steps of the walk (the one-wave form's u += gridDim.x; the
+    LDS-phase forms' c += gs_c; s += gs_s with the carry, gs_c != 0).  A clean
+    run leaves every word zero; then the usual corruptions and one in every
+    (stripe, unit) pair; words from the oracle's P, src unchanged, guard words
+    intact (Case.run).  Without the hook: the same kernel and words."""
+    k, m, nb = shape
+    sz, cap = WALK_GEOM[geom]
+    ns, cps = WALK_NS, -(-sz // 2048)
+    assert (cap // cps, cap % cps) == ((0, 5), (2, 1))[geom] and ns * cps >= 3 * cap
+    code = capi.Code(k, m)
+    for bname, nums in two_bases(k, m, nb, seed=k + nb):
+        case = make_case(shape, nums, ns, sz)
+        pats = all_patterns(k, case.c, ns, sz, k + sz + ns)
+        pats["every unit"] = every_unit_pattern(k, case.c, ns, sz)
+        assert pats.pop("clean") == []
+        knobs(ZFEC_HIP_VERIFY_FUSED_MIN=1, ZFEC_HIP_GRID_CAP=cap)
+        assert not case.run(code, [], (shape, bname, sz, "clean, capped")).any()
+        capped = {p: case.run(code, cor, (shape, bname, sz, p, "capped")) for p, cor in pats.items()}
+        knobs(ZFEC_HIP_GRID_CAP=0)
+        for p, cor in pats.items():
+            assert (case.run(code, cor, (shape, bname, sz, p, "uncapped")) == capped[p]).all(), (shape, bname, p)
+        unit_bits = expected_bits(case.P, k, ns, pats["every unit"])
+        assert (unit_bits.sum(axis=1) == cps).all()
+        assert (capped["every check"] == pack(np.ones((ns, case.c), dtype=bool))).all()
 
 
 # ---- the gate ------------------------------------------------------------------------------

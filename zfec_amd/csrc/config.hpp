@@ -32,7 +32,7 @@ struct Config {
     size_t launch_units;   // ZFEC_HIP_LAUNCH_UNITS: units per launch (long rows cut into byte ranges, batches into groups)
     uint64_t small_lanes;  // ZFEC_HIP_SMALL_LANES: launches below this many lanes take matapply_small (0: never)
     size_t stage_chunk;    // ZFEC_HIP_STAGE_CHUNK: bytes of each block per staged chunk (0: automatic)
-    size_t grid_cap;       // ZFEC_HIP_GRID_CAP: most workgroups per launch of the unit kernels (reg, rows, pair, lds) and of the generated bit-sliced kernels (0: automatic)
+    size_t grid_cap;       // ZFEC_HIP_GRID_CAP: most workgroups per launch of the unit kernels (reg, rows, pair, lds) and of the generated bit-sliced kernels; below their own caps, also of matapply_bsg, matapply_bsr / bsr_ks and matverify_bsr (0: automatic)
     size_t verify_scratch; // ZFEC_HIP_VERIFY_SCRATCH: cap of fec_verify_batch's expected-row scratch, bytes (64 MiB; only lowered)
     uint64_t verify_fused_min;  // ZFEC_HIP_VERIFY_FUSED_MIN: 2-KiB units from which a wide verify runs matverify_bsr (config.cpp)
 };

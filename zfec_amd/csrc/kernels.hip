@@ -3194,13 +3194,17 @@ int g_num_cu = 256;
 // walks grid-stride.
 constexpr uint64_t kGridPerCu = 8 * 1024;
 
-// Config::grid_cap (a test hook) lowers the cap so that a launch a test can
-// afford walks grid-stride; values outside [1, the cap] are ignored.
-uint64_t unit_grid_cap() {
-    const uint64_t cap = uint64_t(g_num_cu) * kGridPerCu;
+// Config::grid_cap (a test hook) lowers a launcher's own cap so that a launch a
+// test can afford walks grid-stride; values outside [1, cap) are ignored.  It
+// bounds the grid only: the kernel a launch takes is chosen from its units.
+uint64_t hooked_grid_cap(uint64_t cap) {
     const uint64_t hook = config().grid_cap;
     return hook >= 1 && hook < cap ? hook : cap;
 }
+uint64_t unit_grid_cap() { return hooked_grid_cap(uint64_t(g_num_cu) * kGridPerCu); }
+// Grid cap of the bit-sliced run-time-data kernels (matapply_bsr in all its
+// forms, matapply_bsr_ks, matverify_bsr): CUs x 1024 workgroups.
+uint64_t bsr_grid_cap() { return hooked_grid_cap(uint64_t(g_num_cu) * 1024); }
 
 void init_dispatch() {
     int dev = 0;
@@ -3613,7 +3617,7 @@ hipError_t launch_bsg(const ApplySpec& a, hipStream_t stream) {
     const size_t lds = size_t(P) * kBsgSlotBytes;
     const uint64_t vunits = units * ngroups;
     if (vunits >= (1ull << 32) - (1ull << 24)) return hipErrorInvalidValue;
-    const uint64_t cap = uint64_t(g_num_cu) * v.blocks_per_cu * 8;
+    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * v.blocks_per_cu * 8);
     const uint32_t grid = static_cast<uint32_t>(vunits < cap ? vunits : cap);
     const uint32_t gs_s = static_cast<uint32_t>(grid / cps), gs_c = static_cast<uint32_t>(grid % cps);
     if (ngroups == 1 && k <= static_cast<uint32_t>(kMaxIn) && r <= static_cast<uint32_t>(kMaxOut) &&
@@ -4048,7 +4052,7 @@ hipError_t launch_bsr_wide(const ApplySpec& a, hipStream_t stream) {
     job.r = r;
     job.ngroups = ng;
     job.pad_ = 0;
-    const uint64_t cap = uint64_t(g_num_cu) * 1024;
+    const uint64_t cap = bsr_grid_cap();
     const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
     job.cps = static_cast<uint32_t>(cps);
     job.gs_s = static_cast<uint32_t>(grid / cps);
@@ -4112,7 +4116,7 @@ hipError_t launch_bsr_lds_tbl(const ApplySpec& a, hipStream_t stream, uint64_t b
     job.r = r;
     job.ngroups = ng;
     job.pad_ = 0;
-    const uint64_t cap = uint64_t(g_num_cu) * 1024;
+    const uint64_t cap = bsr_grid_cap();
     const uint32_t grid = static_cast<uint32_t>(vunits < cap ? vunits : cap);
     job.cps = static_cast<uint32_t>(cps);
     job.gs_s = static_cast<uint32_t>(grid / cps);
@@ -4167,7 +4171,7 @@ hipError_t launch_bsr_a32(const ApplySpec& a, hipStream_t stream, uint64_t base,
     full.resize(size_t(nw) * k * rt);
     if (!fill_bsr_addrs(full.data(), a, base, 1, nw, rt, 1)) return hipErrorInvalidValue;
     for (size_t i = 0; i < full.size(); ++i) job.addr[i] = static_cast<uint32_t>(full[i]);
-    const uint64_t cap = uint64_t(g_num_cu) * 1024;
+    const uint64_t cap = bsr_grid_cap();
     const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
     job.cps = static_cast<uint32_t>(cps);
     job.gs_s = static_cast<uint32_t>(grid / cps);
@@ -4215,7 +4219,7 @@ hipError_t launch_bsr(const ApplySpec& a, hipStream_t stream) {
     for (uint32_t j = 0; j < k; ++j) job.in[j] = a.in[j];
     for (uint32_t i = 0; i < r; ++i) job.out[i] = a.out[i];
     if (!fill_bsr_addrs(job.addr, a, base, 1, nw, rt, 1)) return hipErrorInvalidValue;
-    const uint64_t cap = uint64_t(g_num_cu) * 1024;
+    const uint64_t cap = bsr_grid_cap();
     const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
     job.cps = static_cast<uint32_t>(cps);
     job.gs_s = static_cast<uint32_t>(grid / cps);
@@ -4268,7 +4272,7 @@ uint32_t bsr_vfy_header(J& job, const VerifySpec& v, uint64_t cps, uint64_t unit
     job.r = v.r;
     job.words = v.words;
     job.bit0 = v.bit0;
-    const uint64_t cap = uint64_t(g_num_cu) * 1024;
+    const uint64_t cap = bsr_grid_cap();
     const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
     job.cps = static_cast<uint32_t>(cps);
     job.gs_s = static_cast<uint32_t>(grid / cps);
