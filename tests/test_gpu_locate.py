@@ -197,7 +197,9 @@ def test_fused_layouts(k, m, c, kind):
 
 
 def test_grid_stride(knobs):
-    """Three workgroups (12 waves) walk 37 stripes of 3 waves each."""
+    """Three workgroups (12 waves) walk 37 stripes of 3 waves each.  A step of
+    12 waves is exactly 4 stripes here (gs_w = 0), so the carry of the walk
+    never runs: test_gpu_wave_walk.py has the geometries with gs_w != 0."""
     k, m, c = 3, 10, 7
     code = capi.Code(k, m)
     knobs(ZFEC_HIP_GRID_CAP=3)

@@ -165,7 +165,9 @@ def test_all_120_subsets():
 
 @pytest.mark.parametrize("sz", [1040, 4096])
 def test_grid_stride(knobs, sz):
-    """Two workgroups (8 waves) walk 37 stripes of 2 or 4 waves each."""
+    """Two workgroups (8 waves) walk 37 stripes of 2 or 4 waves each.  A step
+    of 8 waves is exactly 4 or 2 stripes here (gs_w = 0), so the carry of the
+    walk never runs: test_gpu_wave_walk.py has the geometries with gs_w != 0."""
     knobs(ZFEC_HIP_GRID_CAP=2)
     k, m, ns = 3, 10, 37
     pats = random_patterns(np.random.default_rng(sz), k, m, ns)

@@ -246,7 +246,9 @@ def test_register_path(k, m, kind):
 
 def test_grid_stride(knobs):
     """Three workgroups (12 waves) walk 37 stripes of 3 waves each: the masks
-    equal the uncapped run's."""
+    equal the uncapped run's.  A step of 12 waves is exactly 4 stripes here
+    (gs_w = 0), so the carry of the walk never runs: test_gpu_wave_walk.py
+    has the geometries with gs_w != 0."""
     k, m, ns, sz = 3, 10, 37, 2049
     code = capi.Code(k, m)
     case = Case(k, m, range(m), ns, sz)
