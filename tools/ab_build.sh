@@ -5,7 +5,7 @@
 # the other objects are the in-tree build's (run `make` first).  A variant is
 #
 #   name=FLAGS        kernels.hip of this tree with extra compiler flags, e.g.
-#                     "base=-DZFEC_TR64=0 -DZFEC_BSR_EARLY_ADDR=0 legacy"
+#                     "base=-DZFEC_REG_ONE=0 -DZFEC_BSR_NW_WIDE=8 legacy"
 #                     (the word `legacy` swaps in round 5's routine forms:
 #                     tools/gen_gf_routines.py --form legacy; `form=NAME` any
 #                     other form, e.g. form=trunc64, a timing-only experiment)
@@ -16,7 +16,7 @@
 # (zfec_amd/capi.py); tools/ab_bsr.py runs the variants interleaved on the
 # bit-sliced shapes, tools/ab_bench.py on the headline (plain bench.py runs).
 #
-#   tools/ab_build.sh "r05=git:a1850ed" "base=-DZFEC_TR64=0 legacy" "new="
+#   tools/ab_build.sh "r05=git:a1850ed" "base=-DZFEC_REG_TPIPE=0 legacy" "new="
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}

@@ -51,8 +51,6 @@ def bsr_traced(recorded):
     rt, form = a[0], ",".join(a[1:])
     return {"": ("matapply_bsr_solo", [rt]), "lds": ("matapply_bsr", [rt, "false", "false", "BsrJob"]),
             "lds,cmb": ("matapply_bsr", [rt, "false", "true", "BsrJob"]),
-            "lds,a32": ("matapply_bsr", [rt, "false", "false", "BsrJob32"]),
-            "lds,a32,cmb": ("matapply_bsr", [rt, "false", "true", "BsrJob32"]),
             "lds,tbl": ("matapply_bsr", [rt, "true", "false", "BsrTblJob"]),
             "lds,tbl,cmb": ("matapply_bsr", [rt, "true", "true", "BsrTblJob"]),
             "ks,tbl": ("matapply_bsr_ks", [rt])}.get(form)

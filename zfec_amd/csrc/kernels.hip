@@ -244,76 +244,6 @@ struct UnitIter {
     }
 };
 
-// ZFEC_TAIL_ORDER (A/B knob, tools/ab_build.sh; 0 = UnitIter, the default):
-// where the register kernels' walk puts each stripe's last chunk (the one
-// that ends every row, mid-line when sz is not a multiple of 128): 1 = the
-// ns row-tail units first in the walk, then the rest in order; 2 = last.
-#ifndef ZFEC_TAIL_ORDER
-#define ZFEC_TAIL_ORDER 0
-#endif
-template <int ORDER>
-struct TailIter {
-    uint32_t s, c, g, step, ns, cpb, bq, br;  // cpb: body chunks per stripe (cps - 1)
-    template <class J>
-    __device__ TailIter(const J& job, uint32_t block) {
-        ns = job.nstripes;
-        cpb = job.cps - 1;
-        step = job.gs_s * job.cps + job.gs_c;
-        g = block * kBlock + threadIdx.x;
-        bq = cpb ? step / cpb : 0u;
-        br = cpb ? step - bq * cpb : 0u;
-        map();
-    }
-    __device__ void map() {
-        if (cpb == 0) {  // one chunk per stripe: no tail of its own
-            s = g;
-            c = 0;
-            return;
-        }
-        if constexpr (ORDER == 1) {
-            if (g < ns) {
-                s = g;
-                c = cpb;
-            } else {
-                const uint32_t h = g - ns;
-                s = h / cpb;
-                c = h - s * cpb;
-            }
-        } else {
-            const uint32_t body = ns * cpb;
-            if (g < body) {
-                s = g / cpb;
-                c = g - s * cpb;
-            } else {
-                s = g - body;
-                c = cpb;
-            }
-        }
-    }
-    template <class J>
-    __device__ __forceinline__ void next(const J&) {
-        const bool tail = cpb && c == cpb;
-        g += step;
-        if (cpb == 0 || tail || (ORDER == 2 && s + bq + 1 >= ns)) {  // regime change possible: recompute
-            map();
-            return;
-        }
-        c += br;
-        s += bq;
-        if (c >= cpb) {
-            c -= cpb;
-            ++s;
-        }
-        if constexpr (ORDER == 1)
-            if (s >= ns) s = 0xFFFFFFFFu;  // past the body: done
-    }
-};
-#if ZFEC_TAIL_ORDER
-using RegIter = TailIter<ZFEC_TAIL_ORDER>;
-#else
-using RegIter = UnitIter;
-#endif
-
 // Byte span of chunk c of a block of sz bytes.  Chunks are CH bytes; the last
 // one, when sz is not a multiple of CH, is shifted back to end at sz and so
 // overlaps its neighbour: both lanes compute and store identical bytes there,
@@ -442,14 +372,14 @@ __device__ __forceinline__ void reg_body(const RegJob<K, R>& job, uint32_t block
 
     const uint64_t sz = job.sz;
     const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
-    RegIter u(job, block);
+    UnitIter u(job, block);
     if constexpr (PF) {
         u32x4 x[K];
         Span sp = chunk_span<kChunk, true>(u.c, sz, nfull);
         uint64_t ob = u.s * job.out_sstride + sp.off;
         if (u.s < job.nstripes) reg_load<K, R>(job, x, u.s * job.in_sstride + sp.off, sp.full, sp.nb);
         while (u.s < job.nstripes) {
-            RegIter v = u;
+            UnitIter v = u;
             v.next(job);
             const Span spn = chunk_span<kChunk, true>(v.c, sz, nfull);
             u32x4 xn[K];
@@ -1984,31 +1914,13 @@ __device__ __forceinline__ void bswap_blocks2(uint32_t& a0, uint32_t& b0, uint32
 }
 
 // 8 dwords (32 bytes) <-> 8 bit-planes; the transpose is its own inverse.
-// ZFEC_TR64 (default): the first two stages on 64-bit shift pairs, 40 VOP3
-// instructions instead of 48 (tools/ab_bsr.sh, profiles/r06_bsr_ab.json).
-#ifndef ZFEC_TR64
-#define ZFEC_TR64 1
-#endif
+// The first two stages run on 64-bit shift pairs, 40 VOP3 instructions instead
+// of 48 (tools/ab_bsr.sh, profiles/r06_bsr_ab.json).
 __device__ __forceinline__ void transpose8(uint32_t (&v)[8]) {
-#if ZFEC_TR64
     bswap_blocks2(v[0], v[4], v[1], v[5], 4, 0x0F0F0F0Fu);
     bswap_blocks2(v[2], v[6], v[3], v[7], 4, 0x0F0F0F0Fu);
     bswap_blocks2(v[0], v[2], v[1], v[3], 2, 0x33333333u);
     bswap_blocks2(v[4], v[6], v[5], v[7], 2, 0x33333333u);
-    bswap_blocks(v[0], v[1], 1, 0x55555555u);
-    bswap_blocks(v[2], v[3], 1, 0x55555555u);
-    bswap_blocks(v[4], v[5], 1, 0x55555555u);
-    bswap_blocks(v[6], v[7], 1, 0x55555555u);
-    return;
-#endif
-    bswap_blocks(v[0], v[4], 4, 0x0F0F0F0Fu);
-    bswap_blocks(v[1], v[5], 4, 0x0F0F0F0Fu);
-    bswap_blocks(v[2], v[6], 4, 0x0F0F0F0Fu);
-    bswap_blocks(v[3], v[7], 4, 0x0F0F0F0Fu);
-    bswap_blocks(v[0], v[2], 2, 0x33333333u);
-    bswap_blocks(v[1], v[3], 2, 0x33333333u);
-    bswap_blocks(v[4], v[6], 2, 0x33333333u);
-    bswap_blocks(v[5], v[7], 2, 0x33333333u);
     bswap_blocks(v[0], v[1], 1, 0x55555555u);
     bswap_blocks(v[2], v[3], 1, 0x55555555u);
     bswap_blocks(v[4], v[5], 1, 0x55555555u);
@@ -2252,29 +2164,6 @@ template <bool B>
 struct BoolC {  // a compile-time flag passed to generic lambdas
     static constexpr bool value = B;
 };
-// ZFEC_BSR_EARLY_ADDR (default): the LDS-phase form loads the next input's
-// routine addresses before the current input's calls, not after them
-// (matapply_bsr; tools/ab_bsr.sh, profiles/r06_bsr_ab.json).
-#ifndef ZFEC_BSR_EARLY_ADDR
-#define ZFEC_BSR_EARLY_ADDR 1
-#endif
-// ZFEC_BSR_TBL_WRITER (A/B knob, tools/ab_build.sh; 0): 1 writes a new
-// matrix's device-side address table with a kernel from the launch's
-// arguments instead of copying it from pinned host memory.  Even: K=20/M=60
-// first launches of new matrices 0.829-0.848 against 0.818-0.850 ms between
-// events (profiles/r06_bsr_tblwrite_ab.json); the host's enqueue, not the copy,
-// separates them from the compiled kernel's.
-#ifndef ZFEC_BSR_TBL_WRITER
-#define ZFEC_BSR_TBL_WRITER 0
-#endif
-// ZFEC_BSR_CMB_DB (A/B knob, tools/ab_build.sh; off): the combination-sharing
-// form double-buffers its phases (one barrier per phase, half the waves build
-// the next phase during the current one's calls).  It lost: 128/256 0.109 ->
-// 0.112 ms, 160/256 0.112 -> 0.119, 64/112 0.051 -> 0.054
-// (profiles/r06_bsr_cmb_db_ab.json).
-#ifndef ZFEC_BSR_CMB_DB
-#define ZFEC_BSR_CMB_DB 0
-#endif
 typedef __attribute__((address_space(1))) void GlobalVoid;
 typedef __attribute__((address_space(3))) void LdsVoid;
 // Inputs per phase of the combination-sharing form (7.5 KiB of combinations +
@@ -2318,65 +2207,6 @@ struct alignas(16) BsrTblJob {
     const uint8_t* ptr[kBsrTblPtrs];  // k input block pointers, then r output block pointers
 };
 static_assert(sizeof(BsrTblJob) <= 4096, "kernel arguments are limited to 4 KiB");
-
-// 32-bit argument form (LDS-phase kernel, one row group): block pointers and
-// the routine addresses' low halves in the kernel arguments, the high half
-// (the same for the whole routine table) once.  It holds twice the addresses
-// of BsrJob -- K=20/M=60's 40-row encode needs 800 -- so a first launch of a
-// new matrix copies no table to the device: the table form's upload (a
-// hipMemcpyAsync the kernel waits for) cost a first launch ~65 us between its
-// events (profiles/r06_bench_vs_trace.txt).
-constexpr int kBsr32Ptrs = 72;  // k + r block pointers
-struct alignas(16) BsrJob32 {
-    uint64_t sz, in_sstride, out_sstride;
-    uint32_t nstripes, k, r, cps, gs_c, gs_s;
-    uint32_t ngroups;  // 1
-    uint32_t addr_hi;  // high 32 bits of every routine address
-    const uint8_t* ptr[kBsr32Ptrs];
-    uint32_t addr[(4096 - 56 - 8 * kBsr32Ptrs) / 4];  // [wave][input][RT] low halves (56: the header)
-};
-[[maybe_unused]] constexpr int kBsr32Addrs = (4096 - 56 - 8 * kBsr32Ptrs) / 4;
-static_assert(sizeof(BsrJob32) <= 4096, "kernel arguments are limited to 4 KiB");
-typedef const __attribute__((address_space(4))) uint32_t* CU32;
-
-// Where a wave's routine addresses come from: 64-bit values (kernel arguments
-// or the device-side table) or the 32-bit argument form's low halves.
-struct Addr64 {
-    CU64 p;
-    template <int RT>
-    __device__ __forceinline__ void load(uint64_t (&ad)[RT], uint32_t j) const {
-        const CU64 q = p + static_cast<uint64_t>(j) * RT;
-#pragma unroll
-        for (int rr = 0; rr < RT; ++rr) ad[rr] = q[rr];
-    }
-};
-struct Addr32 {
-    CU32 p;
-    uint32_t hi;
-    template <int RT>
-    __device__ __forceinline__ void load(uint64_t (&ad)[RT], uint32_t j) const {
-        const CU32 q = p + static_cast<uint64_t>(j) * RT;
-#pragma unroll
-        for (int rr = 0; rr < RT; ++rr) ad[rr] = (static_cast<uint64_t>(hi) << 32) | q[rr];
-    }
-};
-
-// Writes a device-side routine-address table from its 32-bit low halves in the
-// kernel arguments (one workgroup; the high half is one value for the whole
-// table): a launch's upload of a new matrix's table without a host-to-device
-// copy (bsr_addr_table).
-constexpr int kBsrWriteMax = (4096 - 16) / 4;  // addresses per writer launch
-struct alignas(16) BsrWriteJob {
-    uint64_t* dst;
-    uint32_t n, hi;
-    uint32_t lo[kBsrWriteMax];
-};
-static_assert(sizeof(BsrWriteJob) <= 4096, "kernel arguments are limited to 4 KiB");
-__global__ __launch_bounds__(256) void bsr_table_write(const BsrWriteJob job) {
-    const KPtr<BsrWriteJob> kj = kernarg_job<BsrWriteJob>();
-    for (uint32_t i = threadIdx.x; i < job.n; i += 256)
-        job.dst[i] = (static_cast<uint64_t>(job.hi) << 32) | kj->lo[i];
-}
 
 // Reads input j's RT routine addresses (scalar loads).
 // (The row offset is added to a 64-bit pointer, so the loads share one
@@ -2580,17 +2410,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
     const uint32_t ns = job.nstripes;
     uint32_t ng = 1;
     KPtr<J> kj = kernarg_job<J>();
-    constexpr bool A32 = std::is_same<J, BsrJob32>::value;  // 32-bit argument form
-    constexpr bool PTR = TBL || A32;                         // block pointers in ptr[]
     if constexpr (TBL) ng = job.ngroups;
     auto in_ptr = [&](uint32_t j) -> const uint8_t* {
-        if constexpr (PTR)
+        if constexpr (TBL)
             return kj->ptr[j];
         else
             return kj->in[j];
     };
     auto out_ptr = [&](uint32_t i) -> uint8_t* {
-        if constexpr (PTR)
+        if constexpr (TBL)
             return const_cast<uint8_t*>(kj->ptr[k + i]);
         else
             return const_cast<uint8_t*>(kj->out[i]);  // (VFY: the stored check rows, only read)
@@ -2601,13 +2429,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
         const uint32_t g = TBL && ng > 1 ? s / ns : 0u, stripe = s - g * ns;
         const uint32_t gr0 = g * r / ng, grn = (g + 1) * r / ng - gr0;
         const uint32_t r0 = gr0 + wave * grn / nw, rows = gr0 + (wave + 1) * grn / nw - r0;
-        auto ca = [&] {
-            if constexpr (A32)
-                return Addr32{(CU32)kj->addr + wave * k * RT, job.addr_hi};
-            else if constexpr (TBL)
-                return Addr64{(CU64)job.addr + (g * nw + wave) * k * RT};
+        const CU64 ca = [&] {
+            if constexpr (TBL)
+                return (CU64)job.addr + (g * nw + wave) * k * RT;
             else
-                return Addr64{(CU64)kj->addr + wave * k * RT};
+                return (CU64)kj->addr + wave * k * RT;
         }();
         uint64_t off = static_cast<uint64_t>(c) * kBsrChunk;
         if (off > sz - kBsrChunk) off = sz - kBsrChunk;  // the last unit ends at sz (overlapping its neighbour)
@@ -2657,7 +2483,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
         // phase is its own instance (first = BoolC<true>): its input 0 runs the
         // set twins, peeled at compile time -- a run-time choice between the two
         // statements made the compiler copy and spill the pinned accumulators.
-#if ZFEC_BSR_EARLY_ADDR
+        //
         // Routine addresses, two sets by the parity of the input's global
         // index (phases hold an even number of inputs: bsr_db_phase,
         // bsr_cmb_phase).  Input g + 1's set is loaded (scalar loads) right
@@ -2666,7 +2492,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
         // drains scalar loads too (lgkmcnt), finds it landed.  Round 5 loaded
         // input g + 2's set after g's calls, and that wait stalled on it.
         uint64_t ad0[RT], ad1[RT];
-        ca.template load<RT>(ad0, 0);
+        bsr_addrs<RT>(ad0, ca, 0);
         auto step = [&](auto first, uint32_t gi, const u32x4* b, const uint64_t (&cur)[RT], uint64_t (&nxt)[RT]) {
             uint32_t q[kVals];
             load(b, q);
@@ -2677,7 +2503,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
             else
                 asm volatile("" ::"v"(q[3]), "v"(q[7]));
             __builtin_amdgcn_sched_barrier(0);
-            ca.template load<RT>(nxt, gi + 1 < k ? gi + 1 : k - 1);  // unconditional (clamped)
+            bsr_addrs<RT>(nxt, ca, gi + 1 < k ? gi + 1 : k - 1);  // unconditional (clamped)
             __builtin_amdgcn_sched_barrier(0);
             input(first, q, cur);
         };
@@ -2698,33 +2524,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
             }
             if (j < kn) step(first, ph + j, bsr_planes + o + j * kIn, ad0, ad1);  // the last phase
         };
-#else
-        // In pairs with fixed address registers (A: even, B: odd): after input
-        // j's calls its set is reloaded (scalar loads, unconditional: clamped to
-        // the phase's last input) with input j + 2's addresses (round 5's schedule)
-        auto calls = [&](auto first, uint32_t ph, uint32_t kn, uint32_t o) {
-            uint64_t ada[RT], adb[RT];
-            ca.template load<RT>(ada, ph);
-            ca.template load<RT>(adb, ph + (kn > 1 ? 1 : 0));
-            auto step = [&](auto fst, uint32_t j, uint64_t (&ad)[RT]) {
-                uint32_t q[kVals];
-                load(bsr_planes + o + j * kIn, q);
-                input(fst, q, ad);
-                ca.template load<RT>(ad, ph + (j + 2 < kn ? j + 2 : kn - 1));
-            };
-            uint32_t j = 0;
-            if constexpr (decltype(first)::value) {
-                step(BoolC<true>{}, 0, ada);
-                if (kn > 1) step(BoolC<false>{}, 1, adb);
-                j = 2;
-            }
-            for (; j + 1 < kn; j += 2) {
-                step(BoolC<false>{}, j, ada);
-                step(BoolC<false>{}, j + 1, adb);
-            }
-            if (j < kn) step(BoolC<false>{}, j, ada);
-        };
-#endif
         if constexpr (!CMB) {
             // Planes: double-buffered phases of kq inputs.  A phase's inputs go
             // straight into LDS (LDS-DMA, global_load_lds: no registers in
@@ -2770,60 +2569,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
             phase(BoolC<true>{}, 0);
             for (uint32_t ph = kq; ph < k; ph += kq) phase(BoolC<false>{}, ph);
         } else {
-#if ZFEC_BSR_CMB_DB
-            // Combinations, double-buffered: phases of kp = nw / 2 inputs, two
-            // phases' combinations resident.  The waves are two halves of kp
-            // (one wave of each per SIMD); wave i of half h owns input i of the
-            // phases of parity h.  In phase p, half (p + 1) & 1 builds phase p +
-            // 1 (its inputs arrived by LDS-DMA during phase p - 1: transpose, 30
-            // combinations, into the other buffer) and half p & 1 starts the
-            // LDS-DMA of phase p + 2 into the raw slots phase p has vacated;
-            // then every wave runs phase p's calls; one barrier ends the phase.
-            // (Single-buffered: phases of nw inputs, a barrier, every wave
-            // building one input, a second barrier: the build stalled the calls.)
-            const uint32_t kp = nw / 2, half = wave >= kp ? 1u : 0u, wi = wave - half * kp;
-            const uint32_t ocmb = 0, oraw = 2 * kp * kIn;  // [2][kp] combinations, then [2][kp] raw inputs
-            auto nin = [&](uint32_t ph) { return ph < k ? (k - ph < kp ? k - ph : kp) : 0u; };
-            auto dma = [&](uint32_t p) {  // my input of phase p into raw slot p & 1
-                if (wi < nin(p * kp)) {
-                    const uint8_t* ip = in_ptr(p * kp + wi) + ib;
-                    u32x4* b = bsr_planes + oraw + ((p & 1) * kp + wi) * 128u;
-                    __builtin_amdgcn_global_load_lds((const GlobalVoid*)(ip), (LdsVoid*)(b), 16, 0, 0);
-                    __builtin_amdgcn_global_load_lds((const GlobalVoid*)(ip + 1024), (LdsVoid*)(b + 64), 16, 0, 0);
-                }
-            };
-            auto build = [&](uint32_t p) {  // my input of phase p: raw slot -> combinations buffer p & 1
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (as in the planes form)
-                if (wi < nin(p * kp)) {
-                    const u32x4* r = bsr_planes + oraw + ((p & 1) * kp + wi) * 128u;
-                    const u32x4 x0 = r[lane], x1 = r[64u + lane];
-                    uint32_t v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-                    transpose8(v);
-                    uint32_t q30[30];
-                    bsr_combos(v, q30);
-                    u32x4* b = bsr_planes + ocmb + ((p & 1) * kp + wi) * kIn;
-#pragma unroll
-                    for (int g = 0; g < 7; ++g)
-                        b[g * 64 + lane] = u32x4{q30[4 * g], q30[4 * g + 1], q30[4 * g + 2], q30[4 * g + 3]};
-                    reinterpret_cast<u32x2*>(b + 448)[lane] = u32x2{q30[28], q30[29]};
-                }
-            };
-            const uint32_t np = (k + kp - 1) / kp;  // phases
-            dma(half);                              // phase 0 (half 0), phase 1 (half 1)
-            if (half == 0) build(0);
-            __syncthreads();
-            auto phase = [&](auto first, uint32_t p) {
-                if (half == ((p + 1) & 1)) {
-                    if (p + 1 < np) build(p + 1);
-                } else if (p + 2 < np) {
-                    dma(p + 2);
-                }
-                calls(first, p * kp, nin(p * kp), ocmb + (p & 1) * kp * kIn);
-                __syncthreads();  // phase p read, phase p + 1 written
-            };
-            phase(BoolC<true>{}, 0);
-            for (uint32_t p = 1; p < np; ++p) phase(BoolC<false>{}, p);
-#else
             // Combinations: phases of kp = nw inputs, one per wave.  A phase's
             // inputs go into a raw staging area (LDS-DMA) while the waves walk
             // the previous phase; after the barrier that ends it, each wave
@@ -2871,7 +2616,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
             };
             phase(BoolC<true>{}, 0);
             for (uint32_t ph = kp; ph < k; ph += kp) phase(BoolC<false>{}, ph);
-        #endif
         }
         if constexpr (VFY) {
             (void)ob;
@@ -3391,6 +3135,24 @@ const std::array<PairRow, kRegR + 1> g_pair_launch[kRegK + 1] = {
     {}, pair_plane<1>(std::make_integer_sequence<int, kRegR>()), pair_plane<2>(std::make_integer_sequence<int, kRegR>()),
     pair_plane<3>(std::make_integer_sequence<int, kRegR>()), pair_plane<4>(std::make_integer_sequence<int, kRegR>())};
 
+// ---- per-RT variant tables -------------------------------------------------------
+// f(integral_constant<int, I>) for I = 1 .. N: fills a table of kernels
+// instantiated per row-tile height.
+template <class F, int... I>
+void for_each_rt(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I + 1>{}), ...);
+}
+template <int N, class F>
+void for_each_rt(F&& f) {
+    for_each_rt(f, std::make_integer_sequence<int, N>());
+}
+
+// A variant's name as matapply_last_kernel() reports it: "kernel<RT tags>".
+typedef char KName[40];
+void kname(KName& dst, const char* kernel, int rt, const char* tags) {
+    snprintf(dst, sizeof dst, "%s<%d%s>", kernel, rt, tags);
+}
+
 // ---- table kernels (matapply_lds, k <= 32, r <= 48) ----------------------------
 struct LdsVariant {
     KernelFn fn;
@@ -3402,7 +3164,7 @@ struct LdsVariant {
 // Padded-tile variants by tile height: 1-8 rows in one tile (r <= 8), 9-20
 // rows for wider codes split into ceil(r/20) near-equal tiles.
 constexpr int kMaxTile = 20;
-char g_pad_names[kMaxTile + 1][40];
+KName g_pad_names[kMaxTile + 1];
 LdsVariant g_lds_pad[kMaxTile + 1];
 // measured (tools/mb_encode.exe MB_AB, interleaved medians): k <= 4
 // (memory-bound) takes 16 bytes per lane in ragged 8-row tiles; wider codes
@@ -3411,32 +3173,61 @@ LdsVariant g_lds_pad[kMaxTile + 1];
 const LdsVariant g_lds_fewin{matapply_lds<false, true, 8, 4, 4>, "matapply_lds<8,4,4>", 16, 0};
 const LdsVariant g_lds_acc{matapply_lds<true, false, 16, 2, 2>, "matapply_lds<16,2,2,acc>", 8, 0};
 
-template <int RT>
 void fill_pad() {
-    constexpr int G = (RT <= 4 || RT == 8) ? 4 : 2;  // input group size: measured per tile height
-    snprintf(g_pad_names[RT], sizeof g_pad_names[RT], "matapply_lds<%d,2,%d,pad>", RT, G);
-    g_lds_pad[RT] = LdsVariant{matapply_lds<false, true, RT, 2, G, kTilesPadded>, g_pad_names[RT], 8, RT};
-    if constexpr (RT < kMaxTile) fill_pad<RT + 1>();
+    for_each_rt<kMaxTile>([](auto rt) {
+        constexpr int RT = decltype(rt)::value;
+        constexpr int G = (RT <= 4 || RT == 8) ? 4 : 2;  // input group size: measured per tile height
+        kname(g_pad_names[RT], "matapply_lds", RT, G == 4 ? ",2,4,pad" : ",2,2,pad");
+        g_lds_pad[RT] = LdsVariant{matapply_lds<false, true, RT, 2, G, kTilesPadded>, g_pad_names[RT], 8, RT};
+    });
 }
 
 std::once_flag g_pad_once;
 
 const LdsVariant& pick_lds(uint32_t k, uint32_t r, bool acc) {
-    std::call_once(g_pad_once, [] { fill_pad<1>(); });
+    std::call_once(g_pad_once, fill_pad);
     if (acc) return g_lds_acc;
     if (k <= 4) return g_lds_fewin;
     const uint32_t tiles = (r + kMaxTile - 1) / kMaxTile;
     return g_lds_pad[(r + tiles - 1) / tiles];
 }
 
-void fill_matjob(const ApplySpec& a, MatJob& job) {
+// The header of a unit-walk job (any job type with these six fields).
+template <class J>
+void fill_header(J& job, const ApplySpec& a) {
     job.sz = a.sz;
     job.in_sstride = a.in_sstride;
     job.out_sstride = a.out_sstride;
     job.nstripes = static_cast<uint32_t>(a.nstripes);
     job.k = a.k;
     job.r = a.r;
-    job.cps = job.gs_c = job.gs_s = 0;
+}
+
+// The grid-stride unit walk of a launch over `units` units, cps per stripe,
+// into any job with the three walk fields: at most `cap` workgroups, each
+// taking `per_wg` units per step (kBlock lanes for matapply_lds, one unit for
+// the bit-sliced kernels); returns the grid.
+template <class J>
+uint32_t fill_stride(J& job, uint64_t cps, uint64_t units, uint64_t cap, uint32_t per_wg = 1) {
+    const uint64_t need = (units + per_wg - 1) / per_wg;
+    const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
+    const uint64_t gstride = uint64_t(grid) * per_wg;
+    job.cps = static_cast<uint32_t>(cps);
+    job.gs_s = static_cast<uint32_t>(gstride / cps);
+    job.gs_c = static_cast<uint32_t>(gstride % cps);
+    return grid;
+}
+
+// Both: the header and walk of a one-unit-per-workgroup launch.
+template <class J>
+uint32_t fill_units(J& job, const ApplySpec& a, uint64_t cps, uint64_t units, uint64_t cap) {
+    fill_header(job, a);
+    return fill_stride(job, cps, units, cap);
+}
+
+// (the walk fields are the launcher's: fill_stride, launch_small)
+void fill_matjob(const ApplySpec& a, MatJob& job) {
+    fill_header(job, a);
     job.accumulate = a.accumulate;
     job.pad_ = 0;
     for (uint32_t j = 0; j < a.k; ++j) job.in[j] = a.in[j];
@@ -3455,15 +3246,9 @@ hipError_t launch_lds(const ApplySpec& a, hipStream_t stream) {
     MatJob job;
     fill_matjob(a, job);
     fill_coef(a, job);
-    job.cps = static_cast<uint32_t>(cps);
     const size_t rows = v.pad_tile ? (a.r + v.pad_tile - 1) / v.pad_tile * v.pad_tile : a.r;
     const size_t lds = size_t(a.k) * rows * 32;
-    const uint64_t need = (total + kBlock - 1) / kBlock;
-    const uint64_t cap = unit_grid_cap();
-    const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
-    const uint64_t gstride = uint64_t(grid) * kBlock;
-    job.gs_s = static_cast<uint32_t>(gstride / cps);
-    job.gs_c = static_cast<uint32_t>(gstride % cps);
+    const uint32_t grid = fill_stride(job, cps, total, unit_grid_cap(), kBlock);
     t_last_kernel = v.name;
     return launch_job(reinterpret_cast<const void*>(v.fn), grid, kBlock, lds, stream, job);
 }
@@ -3477,29 +3262,30 @@ constexpr uint32_t kBsgMaxRows = 4u * 12u;
 struct BsgVariant {
     const void* fn_karg = nullptr;  // matapply_bsg<RT, false, MatJob>
     const void* fn_tbl = nullptr;   // matapply_bsg<RT, true, BsgTblJob>
-    char name[32] = "";
-    char name_tbl[32] = "";
+    KName name = "";
+    KName name_tbl = "";
     int blocks_per_cu = 1;          // resident workgroups per CU (occupancy API), set once
 };
 BsgVariant g_bsg_var[kBsgNumRT];
 std::once_flag g_bsg_once;
 std::atomic<int> g_generic{-1};
 
-template <int I>
 void fill_bsg() {
-    constexpr int RT = kBsgRT[I];
-    BsgVariant& v = g_bsg_var[I];
-    v.fn_karg = reinterpret_cast<const void*>(matapply_bsg<RT, false, MatJob>);
-    v.fn_tbl = reinterpret_cast<const void*>(matapply_bsg<RT, true, BsgTblJob>);
-    snprintf(v.name, sizeof v.name, "matapply_bsg<%d,2>", RT);
-    snprintf(v.name_tbl, sizeof v.name_tbl, "matapply_bsg<%d,2,tbl>", RT);
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, v.fn_karg, 256, kBsgPhase * kBsgSlotBytes) == hipSuccess &&
-        nb > 0)
-        v.blocks_per_cu = nb;
-    else
-        (void)hipGetLastError();
-    if constexpr (I + 1 < kBsgNumRT) fill_bsg<I + 1>();
+    for_each_rt<kBsgNumRT>([](auto i) {
+        constexpr int RT = kBsgRT[decltype(i)::value - 1];
+        BsgVariant& v = g_bsg_var[decltype(i)::value - 1];
+        v.fn_karg = reinterpret_cast<const void*>(matapply_bsg<RT, false, MatJob>);
+        v.fn_tbl = reinterpret_cast<const void*>(matapply_bsg<RT, true, BsgTblJob>);
+        kname(v.name, "matapply_bsg", RT, ",2");
+        kname(v.name_tbl, "matapply_bsg", RT, ",2,tbl");
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, v.fn_karg, 256, kBsgPhase * kBsgSlotBytes) ==
+                hipSuccess &&
+            nb > 0)
+            v.blocks_per_cu = nb;
+        else
+            (void)hipGetLastError();
+    });
 }
 
 bool bsg_shape_ok(uint32_t k, uint32_t r, uint64_t sz) {
@@ -3510,70 +3296,118 @@ bool bsg_shape_ok(uint32_t k, uint32_t r, uint64_t sz) {
            r <= rmax && k * r >= 24 && !(k <= 4 && r <= 8);
 }
 
-// Device-side argument tables of wide matapply_bsg launches, per thread and
-// device: a ring of slots in device memory filled by stream-ordered copies
-// from a pinned mirror; a slot is reused once the event recorded after its
-// last launch has completed.
 // Events that only tell the host when a table slot's readers have finished
 // (hipEventSynchronize before the slot is rewritten, hipStreamWaitEvent for
 // another stream of the same device): no system-scope release, which would
 // write the L2's dirty lines back at every launch that records one.
 constexpr unsigned kSlotEventFlags = hipEventDisableTiming | hipEventDisableSystemFence;
 
-struct TableRing {
-    static constexpr int kSlots = 8;
-    static constexpr size_t kSlotBytes = size_t(160) << 10;  // k, r <= 256 with 64 row groups of 4
+// A staging slot: pinned host memory, its device twin filled by stream-ordered
+// copies, and an event recorded after the slot's last reader and waited for
+// before the slot is rewritten.
+struct Slot {
     uint8_t* dev = nullptr;
     uint8_t* host = nullptr;
-    hipEvent_t ev[kSlots] = {};
-    bool busy[kSlots] = {};
-    unsigned next = 0;
+    hipEvent_t ev = nullptr;
+    bool busy = false;
+    hipError_t alloc(size_t bytes) {
+        hipError_t e = hipMalloc(&dev, bytes);
+        if (e != hipSuccess) return e;
+        if ((e = hipHostMalloc(&host, bytes, hipHostMallocDefault)) != hipSuccess) {
+            (void)hipFree(dev);
+            dev = nullptr;
+        }
+        return e;
+    }
+    void free_mem() {
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        dev = host = nullptr;
+    }
+    hipError_t event() { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, kSlotEventFlags); }
+    void drop_event() {
+        if (ev) (void)hipEventSynchronize(ev), (void)hipEventDestroy(ev);
+    }
+    hipError_t wait() {  // until the slot's last reader has finished
+        if (busy) {
+            const hipError_t e = hipEventSynchronize(ev);
+            if (e != hipSuccess) return e;
+        }
+        busy = false;
+        return hipSuccess;
+    }
+    hipError_t record(hipStream_t stream) {  // after the slot's last reader
+        const hipError_t e = hipEventRecord(ev, stream);
+        if (e == hipSuccess) busy = true;
+        return e;
+    }
 };
 
-struct Rings {
-    std::unordered_map<int, TableRing> dev;
-    ~Rings() {
+// N slots of BYTES each in one allocation, made with their events on first
+// use: slot 0 owns the memory, the others point into it.
+template <int N, size_t BYTES>
+struct FixedRing {
+    static constexpr int kSlots = N;
+    static constexpr size_t kSlotBytes = BYTES;
+    Slot slot[N];
+    unsigned next = 0;
+    hipError_t init() {
+        if (slot[0].dev) return hipSuccess;
+        hipError_t e = slot[0].alloc(N * BYTES);
+        if (e != hipSuccess) return e;
+        for (int i = 1; i < N; ++i) {
+            slot[i].dev = slot[0].dev + i * BYTES;
+            slot[i].host = slot[0].host + i * BYTES;
+        }
+        for (Slot& s : slot)
+            if ((e = s.event()) != hipSuccess) return e;
+        return hipSuccess;
+    }
+    void release() {
+        for (Slot& s : slot) s.drop_event();
+        slot[0].free_mem();
+    }
+};
+
+// The calling thread's ring of each device; a ring is released on its own
+// device when the thread exits.
+template <class R>
+struct PerDevice {
+    std::unordered_map<int, R> dev;
+    hipError_t here(R** ring) {
+        int id = 0;
+        const hipError_t e = hipGetDevice(&id);
+        if (e == hipSuccess) *ring = &dev[id];
+        return e;
+    }
+    ~PerDevice() {
         for (auto& kv : dev) {
             int cur = 0;
             if (hipGetDevice(&cur) != hipSuccess || hipSetDevice(kv.first) != hipSuccess) continue;
-            TableRing& t = kv.second;
-            for (int i = 0; i < TableRing::kSlots; ++i)
-                if (t.ev[i]) (void)hipEventSynchronize(t.ev[i]), (void)hipEventDestroy(t.ev[i]);
-            if (t.dev) (void)hipFree(t.dev);
-            if (t.host) (void)hipHostFree(t.host);
+            kv.second.release();
             (void)hipSetDevice(cur);
         }
     }
 };
-thread_local Rings t_rings;
 
-hipError_t ring_slot(TableRing** ring, unsigned* slot) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    TableRing& t = t_rings.dev[dev];
-    if (!t.dev) {
-        if ((e = hipMalloc(&t.dev, TableRing::kSlots * TableRing::kSlotBytes)) != hipSuccess) return e;
-        if ((e = hipHostMalloc(&t.host, TableRing::kSlots * TableRing::kSlotBytes, hipHostMallocDefault)) !=
-            hipSuccess) {
-            (void)hipFree(t.dev);
-            t.dev = nullptr;
-            return e;
-        }
-        for (int i = 0; i < TableRing::kSlots; ++i)
-            if ((e = hipEventCreateWithFlags(&t.ev[i], kSlotEventFlags)) != hipSuccess) return e;
-    }
-    const unsigned s = t.next++ % TableRing::kSlots;
-    if (t.busy[s] && (e = hipEventSynchronize(t.ev[s])) != hipSuccess) return e;  // its last launch has read it
-    t.busy[s] = false;
-    *ring = &t;
-    *slot = s;
+// Device-side argument tables of wide matapply_bsg launches: a slot is reused
+// once the event recorded after its last launch has completed.
+typedef FixedRing<8, (size_t(160) << 10)> TableRing;  // k, r <= 256 with 64 row groups of 4
+thread_local PerDevice<TableRing> t_rings;
+
+hipError_t ring_slot(Slot** slot) {
+    TableRing* t = nullptr;
+    hipError_t e = t_rings.here(&t);
+    if (e != hipSuccess || (e = t->init()) != hipSuccess) return e;
+    Slot& s = t->slot[t->next++ % TableRing::kSlots];
+    if ((e = s.wait()) != hipSuccess) return e;  // its last launch has read it
+    *slot = &s;
     return hipSuccess;
 }
 
 // matapply_bsg launch (the table form declines under graph capture: stream_capturing).
 hipError_t launch_bsg(const ApplySpec& a, hipStream_t stream) {
-    std::call_once(g_bsg_once, [] { fill_bsg<0>(); });
+    std::call_once(g_bsg_once, fill_bsg);
     const uint32_t k = a.k, r = a.r;
     const uint64_t cps = (a.sz + kBsgChunk - 1) / kBsgChunk;
     const uint64_t units = cps * a.nstripes;
@@ -3618,49 +3452,34 @@ hipError_t launch_bsg(const ApplySpec& a, hipStream_t stream) {
     const uint64_t vunits = units * ngroups;
     if (vunits >= (1ull << 32) - (1ull << 24)) return hipErrorInvalidValue;
     const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * v.blocks_per_cu * 8);
-    const uint32_t grid = static_cast<uint32_t>(vunits < cap ? vunits : cap);
-    const uint32_t gs_s = static_cast<uint32_t>(grid / cps), gs_c = static_cast<uint32_t>(grid % cps);
     if (ngroups == 1 && k <= static_cast<uint32_t>(kMaxIn) && r <= static_cast<uint32_t>(kMaxOut) &&
         walk <= static_cast<uint32_t>(kMaxCoef)) {
         MatJob job;
         fill_matjob(a, job);
         fill_walk(job.coef);
-        job.cps = static_cast<uint32_t>(cps);
-        job.gs_s = gs_s;
-        job.gs_c = gs_c;
         t_last_kernel = v.name;
-        return launch_job(v.fn_karg, grid, 256, lds, stream, job);
+        return launch_job(v.fn_karg, fill_stride(job, cps, vunits, cap), 256, lds, stream, job);
     }
     // pointers and coefficients in a device-side table
     if (stream_capturing(stream)) return hipErrorNotSupported;
     const size_t bytes = 8 * size_t(k + r) + walk;
     if (bytes > TableRing::kSlotBytes) return hipErrorNotSupported;
-    TableRing* ring = nullptr;
-    unsigned slot = 0;
-    hipError_t e = ring_slot(&ring, &slot);
+    Slot* slot = nullptr;
+    hipError_t e = ring_slot(&slot);
     if (e != hipSuccess) return e;
-    uint8_t* h = ring->host + slot * TableRing::kSlotBytes;
-    uint8_t* d = ring->dev + slot * TableRing::kSlotBytes;
+    uint8_t* h = slot->host;
+    uint8_t* d = slot->dev;
     std::memcpy(h, a.in, 8 * size_t(k));
     std::memcpy(h + 8 * size_t(k), a.out, 8 * size_t(r));
     fill_walk(h + 8 * size_t(k + r));
     if ((e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     BsgTblJob job;
-    job.sz = a.sz;
-    job.in_sstride = a.in_sstride;
-    job.out_sstride = a.out_sstride;
-    job.nstripes = static_cast<uint32_t>(a.nstripes);
-    job.k = k;
-    job.r = r;
-    job.cps = static_cast<uint32_t>(cps);
-    job.gs_s = gs_s;
-    job.gs_c = gs_c;
+    const uint32_t grid = fill_units(job, a, cps, vunits, cap);
     job.ngroups = ngroups;
     job.pad_ = 0;
     job.table = d;
     if ((e = launch_job(v.fn_tbl, grid, 256, lds, stream, job)) != hipSuccess) return e;
-    if ((e = hipEventRecord(ring->ev[slot], stream)) != hipSuccess) return e;
-    ring->busy[slot] = true;
+    if ((e = slot->record(stream)) != hipSuccess) return e;
     t_last_kernel = v.name_tbl;
     return hipSuccess;
 }
@@ -3678,18 +3497,12 @@ hipError_t launch_bsg(const ApplySpec& a, hipStream_t stream) {
 #ifndef ZFEC_BSR_CMB_MIN_NW
 #define ZFEC_BSR_CMB_MIN_NW 8
 #endif
-// (the double-buffered form needs an even phase, nw / 2 >= 2: the kernel's
-// routine-address sets alternate by input parity across phases)
-bool bsr_cmb(uint32_t nw) { return nw >= ZFEC_BSR_CMB_MIN_NW && (!ZFEC_BSR_CMB_DB || nw >= 4); }
+bool bsr_cmb(uint32_t nw) { return nw >= ZFEC_BSR_CMB_MIN_NW; }
 
 // LDS of an nw-wave LDS-phase launch over k inputs: one phase of combinations
 // and its raw staging, or two phases of planes (one when a single phase holds
 // all k).
 size_t bsr_lds_bytes(uint32_t k, uint32_t nw, bool cmb) {
-#if ZFEC_BSR_CMB_DB
-    // two phases of nw / 2 inputs: combinations and raw staging each
-    if (cmb) return size_t(2) * (nw / 2) * (bsr_in_bytes<true>() + bsr_in_bytes<false>());
-#endif
     const uint32_t ph = cmb ? bsr_cmb_phase(nw) : bsr_db_phase(nw);
     if (cmb) return size_t(k < ph ? k : ph) * (bsr_in_bytes<true>() + bsr_in_bytes<false>());  // + raw staging
     return size_t(k <= ph ? k : 2 * ph) * bsr_in_bytes<false>();
@@ -3700,32 +3513,24 @@ struct BsrVariant {
     const void* fn = nullptr;
     const void* fn_cmb = nullptr;  // combination-sharing form (bsr_cmb)
     const void* fn_solo = nullptr;
-    const void* fn_a32 = nullptr;  // 32-bit argument form (BsrJob32)
-    const void* fn_a32_cmb = nullptr;
-    char name[24] = "";
-    char name_cmb[28] = "";
-    char name_solo[32] = "";
-    char name_a32[28] = "";
-    char name_a32_cmb[32] = "";
+    KName name = "";
+    KName name_cmb = "";
+    KName name_solo = "";
 };
 BsrVariant g_bsr_var[kBsrMaxRows + 1];
 std::once_flag g_bsr_once;
 
-template <int RT>
 void fill_bsr() {
-    g_bsr_var[RT].fn = reinterpret_cast<const void*>(matapply_bsr<RT, false, false, BsrJob>);
-    g_bsr_var[RT].fn_cmb = reinterpret_cast<const void*>(matapply_bsr<RT, false, true, BsrJob>);
-    snprintf(g_bsr_var[RT].name, sizeof g_bsr_var[RT].name, "matapply_bsr<%d,lds>", RT);
-    snprintf(g_bsr_var[RT].name_cmb, sizeof g_bsr_var[RT].name_cmb, "matapply_bsr<%d,lds,cmb>", RT);
-    g_bsr_var[RT].fn_solo = reinterpret_cast<const void*>(matapply_bsr_solo<RT>);
-    snprintf(g_bsr_var[RT].name_solo, sizeof g_bsr_var[RT].name_solo, "matapply_bsr<%d>", RT);
-#if !ZFEC_BSR_NO_A32  // (instantiated only for the A/B)
-    g_bsr_var[RT].fn_a32 = reinterpret_cast<const void*>(matapply_bsr<RT, false, false, BsrJob32>);
-    g_bsr_var[RT].fn_a32_cmb = reinterpret_cast<const void*>(matapply_bsr<RT, false, true, BsrJob32>);
-#endif
-    snprintf(g_bsr_var[RT].name_a32, sizeof g_bsr_var[RT].name_a32, "matapply_bsr<%d,lds,a32>", RT);
-    snprintf(g_bsr_var[RT].name_a32_cmb, sizeof g_bsr_var[RT].name_a32_cmb, "matapply_bsr<%d,lds,a32,cmb>", RT);
-    if constexpr (RT < kBsrMaxRows) fill_bsr<RT + 1>();
+    for_each_rt<kBsrMaxRows>([](auto rt) {
+        constexpr int RT = decltype(rt)::value;
+        BsrVariant& v = g_bsr_var[RT];
+        v.fn = reinterpret_cast<const void*>(matapply_bsr<RT, false, false, BsrJob>);
+        v.fn_cmb = reinterpret_cast<const void*>(matapply_bsr<RT, false, true, BsrJob>);
+        v.fn_solo = reinterpret_cast<const void*>(matapply_bsr_solo<RT>);
+        kname(v.name, "matapply_bsr", RT, ",lds");
+        kname(v.name_cmb, "matapply_bsr", RT, ",lds,cmb");
+        kname(v.name_solo, "matapply_bsr", RT, "");
+    });
 }
 
 // The address of the routine table on each device, read by bsr_table_probe
@@ -3830,35 +3635,13 @@ bool fill_bsr_addrs(uint64_t* dst, const ApplySpec& a, uint64_t base, uint32_t n
 // are reused round-robin once the launches that read them have finished (an
 // event per slot); a launch on another stream than the slot's last one is
 // ordered after it (hipStreamWaitEvent), so one event covers every reader.
-struct BsrTblCache {
-    static constexpr int kSlots = 8;
-    static constexpr size_t kSlotBytes = size_t(160) << 10;
-    uint8_t* dev = nullptr;
-    uint8_t* host = nullptr;
-    hipEvent_t used[kSlots] = {};  // recorded after the last launch that read the slot (and its upload)
-    bool busy[kSlots] = {};
+struct BsrTblCache : FixedRing<8, (size_t(160) << 10)> {
+    // (a slot's event: recorded after the last launch that read the slot, and its upload)
     hipStream_t last[kSlots] = {};
     uint32_t dims[kSlots][6] = {};  // k, r, ng, nw, rt, split of the table held (k == 0: empty)
     std::vector<uint8_t> coef[kSlots];
-    unsigned next = 0;
 };
-
-struct BsrTblCaches {
-    std::unordered_map<int, BsrTblCache> dev;
-    ~BsrTblCaches() {
-        for (auto& kv : dev) {
-            int cur = 0;
-            if (hipGetDevice(&cur) != hipSuccess || hipSetDevice(kv.first) != hipSuccess) continue;
-            BsrTblCache& c = kv.second;
-            for (int i = 0; i < BsrTblCache::kSlots; ++i)
-                if (c.used[i]) (void)hipEventSynchronize(c.used[i]), (void)hipEventDestroy(c.used[i]);
-            if (c.dev) (void)hipFree(c.dev);
-            if (c.host) (void)hipHostFree(c.host);
-            (void)hipSetDevice(cur);
-        }
-    }
-};
-thread_local BsrTblCaches t_bsr_tbl;
+thread_local PerDevice<BsrTblCache> t_bsr_tbl;
 
 struct BsrTblRef {
     BsrTblCache* c = nullptr;
@@ -3867,11 +3650,8 @@ struct BsrTblRef {
 };
 
 hipError_t bsr_table_done(const BsrTblRef& t, hipStream_t stream) {
-    const hipError_t e = hipEventRecord(t.c->used[t.slot], stream);
-    if (e == hipSuccess) {
-        t.c->busy[t.slot] = true;
-        t.c->last[t.slot] = stream;
-    }
+    const hipError_t e = t.c->slot[t.slot].record(stream);
+    if (e == hipSuccess) t.c->last[t.slot] = stream;
     return e;
 }
 
@@ -3884,56 +3664,28 @@ hipError_t bsr_addr_table(const ApplySpec& a, hipStream_t stream, uint64_t base,
     const uint32_t k = a.k, r = a.r;
     const size_t n = size_t(ng) * nw * k * rt;
     if (n * 8 > BsrTblCache::kSlotBytes || stream_capturing(stream)) return hipErrorNotSupported;
-    int devid = 0;
-    hipError_t e = hipGetDevice(&devid);
-    if (e != hipSuccess) return e;
-    BsrTblCache& c = t_bsr_tbl.dev[devid];
-    if (!c.dev) {
-        if ((e = hipMalloc(&c.dev, BsrTblCache::kSlots * BsrTblCache::kSlotBytes)) != hipSuccess) return e;
-        if ((e = hipHostMalloc(&c.host, BsrTblCache::kSlots * BsrTblCache::kSlotBytes, hipHostMallocDefault)) !=
-            hipSuccess) {
-            (void)hipFree(c.dev);
-            c.dev = nullptr;
-            return e;
-        }
-        for (int i = 0; i < BsrTblCache::kSlots; ++i)
-            if ((e = hipEventCreateWithFlags(&c.used[i], kSlotEventFlags)) != hipSuccess) return e;
-    }
+    BsrTblCache* cp = nullptr;
+    hipError_t e = t_bsr_tbl.here(&cp);
+    if (e != hipSuccess || (e = cp->init()) != hipSuccess) return e;
+    BsrTblCache& c = *cp;
     thread_local std::vector<uint8_t> m;  // the matrix, row-major: the key with the layout
     m.resize(size_t(r) * k);
     for (uint32_t i = 0; i < r; ++i) std::memcpy(&m[size_t(i) * k], a.coef + size_t(i) * a.coef_stride, k);
     const uint32_t dims[6] = {k, r, ng, nw, rt, split};
     for (unsigned i = 0; i < BsrTblCache::kSlots; ++i) {
         if (std::memcmp(c.dims[i], dims, sizeof dims) != 0 || c.coef[i] != m) continue;
-        if (c.busy[i] && c.last[i] != stream && (e = hipStreamWaitEvent(stream, c.used[i], 0)) != hipSuccess)
+        if (c.slot[i].busy && c.last[i] != stream && (e = hipStreamWaitEvent(stream, c.slot[i].ev, 0)) != hipSuccess)
             return e;
-        *ref = BsrTblRef{&c, i, reinterpret_cast<const uint64_t*>(c.dev + i * BsrTblCache::kSlotBytes)};
+        *ref = BsrTblRef{&c, i, reinterpret_cast<const uint64_t*>(c.slot[i].dev)};
         return hipSuccess;
     }
     const unsigned i = c.next++ % BsrTblCache::kSlots;
-    if (c.busy[i] && (e = hipEventSynchronize(c.used[i])) != hipSuccess) return e;  // its readers have finished
-    c.busy[i] = false;
+    if ((e = c.slot[i].wait()) != hipSuccess) return e;  // its readers have finished
     c.dims[i][0] = 0;  // empty until the upload is enqueued
-    uint64_t* h = reinterpret_cast<uint64_t*>(c.host + i * BsrTblCache::kSlotBytes);
-    uint8_t* d = c.dev + i * BsrTblCache::kSlotBytes;
+    uint64_t* h = reinterpret_cast<uint64_t*>(c.slot[i].host);
+    uint8_t* d = c.slot[i].dev;
     if (!fill_bsr_addrs(h, a, base, ng, nw, rt, split)) return hipErrorInvalidValue;
-    const uint32_t hi = static_cast<uint32_t>(h[0] >> 32);
-    bool one_hi = ZFEC_BSR_TBL_WRITER && n <= size_t(4) * kBsrWriteMax;
-    for (size_t x = 0; one_hi && x < n; ++x) one_hi = static_cast<uint32_t>(h[x] >> 32) == hi;
-    if (one_hi) {
-        // up to 4 writer launches (~4 KB of arguments each) instead of the copy
-        for (size_t x0 = 0; x0 < n; x0 += kBsrWriteMax) {
-            BsrWriteJob w;
-            w.dst = reinterpret_cast<uint64_t*>(d) + x0;
-            w.n = static_cast<uint32_t>(n - x0 < size_t(kBsrWriteMax) ? n - x0 : kBsrWriteMax);
-            w.hi = hi;
-            for (uint32_t x = 0; x < w.n; ++x) w.lo[x] = static_cast<uint32_t>(h[x0 + x]);
-            if ((e = launch_job(reinterpret_cast<const void*>(bsr_table_write), 1, 256, 0, stream, w)) != hipSuccess)
-                return e;
-        }
-    } else if ((e = hipMemcpyAsync(d, h, n * 8, hipMemcpyHostToDevice, stream)) != hipSuccess) {
-        return e;
-    }
+    if ((e = hipMemcpyAsync(d, h, n * 8, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     // (no event for the upload itself: the launch that follows on this stream records
     // the slot's event whether or not it is accepted, bsr_table_done, and that event
     // completes after the upload -- one hipEventRecord less in a first launch)
@@ -4012,20 +3764,21 @@ bool bsr_wide_ok(uint32_t k, uint32_t r, uint64_t sz, uint64_t nstripes) {
 
 struct BsrKsVariant {
     const void* fn = nullptr;
-    char name[28] = "";
+    KName name = "";
 };
 BsrKsVariant g_bsr_ks[kBsrMaxRows + 1];
 std::once_flag g_bsr_ks_once;
 
-template <int RT>
 void fill_bsr_ks() {
-    g_bsr_ks[RT].fn = reinterpret_cast<const void*>(matapply_bsr_ks<RT>);
-    snprintf(g_bsr_ks[RT].name, sizeof g_bsr_ks[RT].name, "matapply_bsr<%d,ks,tbl>", RT);
-    if constexpr (RT < kBsrMaxRows) fill_bsr_ks<RT + 1>();
+    for_each_rt<kBsrMaxRows>([](auto rt) {
+        constexpr int RT = decltype(rt)::value;
+        g_bsr_ks[RT].fn = reinterpret_cast<const void*>(matapply_bsr_ks<RT>);
+        kname(g_bsr_ks[RT].name, "matapply_bsr", RT, ",ks,tbl");
+    });
 }
 
 hipError_t launch_bsr_wide(const ApplySpec& a, hipStream_t stream) {
-    std::call_once(g_bsr_ks_once, [] { fill_bsr_ks<1>(); });
+    std::call_once(g_bsr_ks_once, fill_bsr_ks);
     uint64_t base = 0;
     if (bsr_routine_base(&base, stream) != hipSuccess) return hipErrorNotSupported;
     const uint32_t k = a.k, r = a.r;
@@ -4044,19 +3797,9 @@ hipError_t launch_bsr_wide(const ApplySpec& a, hipStream_t stream) {
     BsrTblRef t;
     hipError_t e = bsr_addr_table(a, stream, base, ng, 1, rt, nw, &t);
     if (e != hipSuccess) return e;
-    job.sz = a.sz;
-    job.in_sstride = a.in_sstride;
-    job.out_sstride = a.out_sstride;
-    job.nstripes = static_cast<uint32_t>(a.nstripes);
-    job.k = k;
-    job.r = r;
+    const uint32_t grid = fill_units(job, a, cps, units, bsr_grid_cap());
     job.ngroups = ng;
     job.pad_ = 0;
-    const uint64_t cap = bsr_grid_cap();
-    const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
-    job.cps = static_cast<uint32_t>(cps);
-    job.gs_s = static_cast<uint32_t>(grid / cps);
-    job.gs_c = static_cast<uint32_t>(grid % cps);
     job.addr = t.dev;
     e = launch_job(g_bsr_ks[rt].fn, grid, 64 * nw, 0, stream, job);
     const hipError_t te = bsr_table_done(t, stream);  // also when the launch failed: the upload is a reader
@@ -4078,27 +3821,29 @@ bool bsr_tbl_ok(uint32_t k, uint32_t r, uint64_t sz) {
 struct BsrTblVariant {
     const void* fn = nullptr;
     const void* fn_cmb = nullptr;
-    char name[28] = "";
-    char name_cmb[32] = "";
+    KName name = "";
+    KName name_cmb = "";
 };
 BsrTblVariant g_bsr_tbl[kBsrMaxRows + 1];
 std::once_flag g_bsr_tbl_once;
 
-template <int RT>
 void fill_bsr_tbl() {
-    g_bsr_tbl[RT].fn = reinterpret_cast<const void*>(matapply_bsr<RT, true, false, BsrTblJob>);
-    g_bsr_tbl[RT].fn_cmb = reinterpret_cast<const void*>(matapply_bsr<RT, true, true, BsrTblJob>);
-    snprintf(g_bsr_tbl[RT].name, sizeof g_bsr_tbl[RT].name, "matapply_bsr<%d,lds,tbl>", RT);
-    snprintf(g_bsr_tbl[RT].name_cmb, sizeof g_bsr_tbl[RT].name_cmb, "matapply_bsr<%d,lds,tbl,cmb>", RT);
-    if constexpr (RT < kBsrMaxRows) fill_bsr_tbl<RT + 1>();
+    for_each_rt<kBsrMaxRows>([](auto rt) {
+        constexpr int RT = decltype(rt)::value;
+        BsrTblVariant& v = g_bsr_tbl[RT];
+        v.fn = reinterpret_cast<const void*>(matapply_bsr<RT, true, false, BsrTblJob>);
+        v.fn_cmb = reinterpret_cast<const void*>(matapply_bsr<RT, true, true, BsrTblJob>);
+        kname(v.name, "matapply_bsr", RT, ",lds,tbl");
+        kname(v.name_cmb, "matapply_bsr", RT, ",lds,tbl,cmb");
+    });
 }
 
 // One table-form launch of the LDS-phase kernel: ng row groups of nw waves of
 // <= rt rows each.
 hipError_t launch_bsr_lds_tbl(const ApplySpec& a, hipStream_t stream, uint64_t base, uint32_t ng, uint32_t nw,
                               uint32_t rt) {
-    std::call_once(g_bsr_tbl_once, [] { fill_bsr_tbl<1>(); });
-    const uint32_t k = a.k, r = a.r;
+    std::call_once(g_bsr_tbl_once, fill_bsr_tbl);
+    const uint32_t k = a.k;
     const uint64_t cps = (a.sz + kBsrChunk - 1) / kBsrChunk;
     const uint64_t vunits = cps * a.nstripes * ng;
     if (vunits >= (1ull << 32) - (1ull << 24) || rt < 1 || rt > static_cast<uint32_t>(kBsrMaxRows))
@@ -4108,19 +3853,9 @@ hipError_t launch_bsr_lds_tbl(const ApplySpec& a, hipStream_t stream, uint64_t b
     BsrTblRef t;
     hipError_t e = bsr_addr_table(a, stream, base, ng, nw, rt, 1, &t);
     if (e != hipSuccess) return e;
-    job.sz = a.sz;
-    job.in_sstride = a.in_sstride;
-    job.out_sstride = a.out_sstride;
-    job.nstripes = static_cast<uint32_t>(a.nstripes);
-    job.k = k;
-    job.r = r;
+    const uint32_t grid = fill_units(job, a, cps, vunits, bsr_grid_cap());
     job.ngroups = ng;
     job.pad_ = 0;
-    const uint64_t cap = bsr_grid_cap();
-    const uint32_t grid = static_cast<uint32_t>(vunits < cap ? vunits : cap);
-    job.cps = static_cast<uint32_t>(cps);
-    job.gs_s = static_cast<uint32_t>(grid / cps);
-    job.gs_c = static_cast<uint32_t>(grid % cps);
     job.addr = t.dev;
     const bool cmb = bsr_cmb(nw);
     e = launch_job(cmb ? g_bsr_tbl[rt].fn_cmb : g_bsr_tbl[rt].fn, grid, 64 * nw, bsr_lds_bytes(k, nw, cmb), stream, job);
@@ -4141,49 +3876,8 @@ hipError_t launch_bsr_tbl(const ApplySpec& a, hipStream_t stream) {
     return launch_bsr_lds_tbl(a, stream, base, ng, nw, (rpg + nw - 1) / nw);
 }
 
-// ZFEC_BSR_NO_A32 (A/B knob, tools/ab_build.sh; 1 = off): 0 puts launches of
-// 433-866 addresses on the 32-bit argument form.  It lost: K=20/M=60's 40-row
-// encode 0.69 -> 0.74 ms back to back (each address needs its 64-bit SGPR pair
-// assembled: ~20 more scalar instructions per input and wave), and its first
-// launches of new matrices too (profiles/r06_bsr_a32_ab.json); the table form
-// stays, its upload written by a kernel (bsr_table_write).
-#ifndef ZFEC_BSR_NO_A32
-#define ZFEC_BSR_NO_A32 1
-#endif
-
-// The LDS-phase kernel in its 32-bit argument form (BsrJob32): one row group of
-// nw waves of rt rows.
-hipError_t launch_bsr_a32(const ApplySpec& a, hipStream_t stream, uint64_t base, uint32_t nw, uint32_t rt,
-                          uint64_t units, uint64_t cps) {
-    const uint32_t k = a.k, r = a.r;
-    BsrJob32 job;
-    job.sz = a.sz;
-    job.in_sstride = a.in_sstride;
-    job.out_sstride = a.out_sstride;
-    job.nstripes = static_cast<uint32_t>(a.nstripes);
-    job.k = k;
-    job.r = r;
-    job.ngroups = 1;
-    job.addr_hi = static_cast<uint32_t>(base >> 32);
-    for (uint32_t j = 0; j < k; ++j) job.ptr[j] = a.in[j];
-    for (uint32_t i = 0; i < r; ++i) job.ptr[k + i] = a.out[i];
-    thread_local std::vector<uint64_t> full;
-    full.resize(size_t(nw) * k * rt);
-    if (!fill_bsr_addrs(full.data(), a, base, 1, nw, rt, 1)) return hipErrorInvalidValue;
-    for (size_t i = 0; i < full.size(); ++i) job.addr[i] = static_cast<uint32_t>(full[i]);
-    const uint64_t cap = bsr_grid_cap();
-    const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
-    job.cps = static_cast<uint32_t>(cps);
-    job.gs_s = static_cast<uint32_t>(grid / cps);
-    job.gs_c = static_cast<uint32_t>(grid % cps);
-    const bool cmb = bsr_cmb(nw);
-    t_last_kernel = cmb ? g_bsr_var[rt].name_a32_cmb : g_bsr_var[rt].name_a32;
-    return launch_job(cmb ? g_bsr_var[rt].fn_a32_cmb : g_bsr_var[rt].fn_a32, grid, 64 * nw,
-                      bsr_lds_bytes(k, nw, cmb), stream, job);
-}
-
 hipError_t launch_bsr(const ApplySpec& a, hipStream_t stream) {
-    std::call_once(g_bsr_once, [] { fill_bsr<1>(); });
+    std::call_once(g_bsr_once, fill_bsr);
     uint64_t base = 0;
     if (bsr_routine_base(&base, stream) != hipSuccess) return hipErrorNotSupported;
     const uint32_t k = a.k, r = a.r;
@@ -4192,38 +3886,17 @@ hipError_t launch_bsr(const ApplySpec& a, hipStream_t stream) {
     uint32_t nw, rt;
     bsr_tiles(r, units, &nw, &rt);
     if (units >= (1ull << 32) - (1ull << 24)) return hipErrorInvalidValue;
-    // more addresses than the arguments hold as 64-bit values (e.g. K=20/M=60's
-    // 40-row encode, 800): their low halves in the arguments (BsrJob32) when
-    // they fit and the routine table's high half is one value; else the same
-    // kernel reading them from a device-side table
-    if (size_t(nw) * k * rt > static_cast<size_t>(kBsrArgAddrs)) {
-        const uint64_t top = base + uint64_t(kBsrSlotStride ? kBsrSlotStride * kBsrMaxRows : kBsrSetBase * 2);
-#if !ZFEC_BSR_NO_A32
-        if (nw > 1 && size_t(nw) * k * rt <= static_cast<size_t>(kBsr32Addrs) && k + r <= uint32_t(kBsr32Ptrs) &&
-            (base >> 32) == (top >> 32))
-            return launch_bsr_a32(a, stream, base, nw, rt, units, cps);
-#else
-        (void)top;
-#endif
+    // more addresses than the arguments hold (e.g. K=20/M=60's 40-row encode,
+    // 800): the same kernel reading them from a device-side table
+    if (size_t(nw) * k * rt > static_cast<size_t>(kBsrArgAddrs))
         return launch_bsr_lds_tbl(a, stream, base, 1, nw, rt);
-    }
     BsrJob job;
-    job.sz = a.sz;
-    job.in_sstride = a.in_sstride;
-    job.out_sstride = a.out_sstride;
-    job.nstripes = static_cast<uint32_t>(a.nstripes);
-    job.k = k;
-    job.r = r;
+    const uint32_t grid = fill_units(job, a, cps, units, bsr_grid_cap());
     job.nt = nw;
     job.pad_ = 0;
     for (uint32_t j = 0; j < k; ++j) job.in[j] = a.in[j];
     for (uint32_t i = 0; i < r; ++i) job.out[i] = a.out[i];
     if (!fill_bsr_addrs(job.addr, a, base, 1, nw, rt, 1)) return hipErrorInvalidValue;
-    const uint64_t cap = bsr_grid_cap();
-    const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
-    job.cps = static_cast<uint32_t>(cps);
-    job.gs_s = static_cast<uint32_t>(grid / cps);
-    job.gs_c = static_cast<uint32_t>(grid % cps);
     if (nw == 1) {  // one row tile: one wave per unit, no LDS
         t_last_kernel = g_bsr_var[rt].name_solo;
         return launch_job(g_bsr_var[rt].fn_solo, grid, 64, 0, stream, job);
@@ -4243,22 +3916,24 @@ struct BsrVfyVariant {
     const void* fn_solo = nullptr;
     const void* fn = nullptr;
     const void* fn_tbl = nullptr;
-    char name_solo[24] = "";
-    char name[28] = "";
-    char name_tbl[32] = "";
+    KName name_solo = "";
+    KName name = "";
+    KName name_tbl = "";
 };
 BsrVfyVariant g_bsr_vfy[kBsrMaxRows + 1];
 std::once_flag g_bsr_vfy_once;
 
-template <int RT>
 void fill_bsr_vfy() {
-    g_bsr_vfy[RT].fn_solo = reinterpret_cast<const void*>(matverify_bsr_solo<RT>);
-    g_bsr_vfy[RT].fn = reinterpret_cast<const void*>(matapply_bsr<RT, false, false, BsrVfyJob>);
-    g_bsr_vfy[RT].fn_tbl = reinterpret_cast<const void*>(matapply_bsr<RT, true, false, BsrVfyTblJob>);
-    snprintf(g_bsr_vfy[RT].name_solo, sizeof g_bsr_vfy[RT].name_solo, "matverify_bsr<%d>", RT);
-    snprintf(g_bsr_vfy[RT].name, sizeof g_bsr_vfy[RT].name, "matverify_bsr<%d,lds>", RT);
-    snprintf(g_bsr_vfy[RT].name_tbl, sizeof g_bsr_vfy[RT].name_tbl, "matverify_bsr<%d,lds,tbl>", RT);
-    if constexpr (RT < kBsrMaxRows) fill_bsr_vfy<RT + 1>();
+    for_each_rt<kBsrMaxRows>([](auto rt) {
+        constexpr int RT = decltype(rt)::value;
+        BsrVfyVariant& v = g_bsr_vfy[RT];
+        v.fn_solo = reinterpret_cast<const void*>(matverify_bsr_solo<RT>);
+        v.fn = reinterpret_cast<const void*>(matapply_bsr<RT, false, false, BsrVfyJob>);
+        v.fn_tbl = reinterpret_cast<const void*>(matapply_bsr<RT, true, false, BsrVfyTblJob>);
+        kname(v.name_solo, "matverify_bsr", RT, "");
+        kname(v.name, "matverify_bsr", RT, ",lds");
+        kname(v.name_tbl, "matverify_bsr", RT, ",lds,tbl");
+    });
 }
 
 // The header every verify job shares, and the grid (launch_bsr's).
@@ -4272,16 +3947,11 @@ uint32_t bsr_vfy_header(J& job, const VerifySpec& v, uint64_t cps, uint64_t unit
     job.r = v.r;
     job.words = v.words;
     job.bit0 = v.bit0;
-    const uint64_t cap = bsr_grid_cap();
-    const uint32_t grid = static_cast<uint32_t>(units < cap ? units : cap);
-    job.cps = static_cast<uint32_t>(cps);
-    job.gs_s = static_cast<uint32_t>(grid / cps);
-    job.gs_c = static_cast<uint32_t>(grid % cps);
-    return grid;
+    return fill_stride(job, cps, units, bsr_grid_cap());
 }
 
 hipError_t launch_verify_bsr_one(const VerifySpec& v, hipStream_t stream) {
-    std::call_once(g_bsr_vfy_once, [] { fill_bsr_vfy<1>(); });
+    std::call_once(g_bsr_vfy_once, fill_bsr_vfy);
     uint64_t base = 0;
     if (bsr_routine_base(&base, stream) != hipSuccess) return hipErrorNotSupported;
     const uint32_t k = v.k, r = v.r;
@@ -4333,56 +4003,28 @@ hipError_t launch_verify_bsr_one(const VerifySpec& v, hipStream_t stream) {
 // needs: 4096 K=4 patterns are 1.3 MB of tables, 10^6 host-side ids 4 MB.
 struct MixedRing {
     static constexpr int kSlots = 4;
-    struct Slot {
-        uint8_t* dev = nullptr;
-        uint8_t* host = nullptr;
-        size_t cap = 0;
-        hipEvent_t ev = nullptr;
-        bool busy = false;
-    };
     Slot slot[kSlots];
+    size_t cap[kSlots] = {};
     unsigned next = 0;
-};
-
-struct MixedRings {
-    std::unordered_map<int, MixedRing> dev;
-    ~MixedRings() {
-        for (auto& kv : dev) {
-            int cur = 0;
-            if (hipGetDevice(&cur) != hipSuccess || hipSetDevice(kv.first) != hipSuccess) continue;
-            for (MixedRing::Slot& s : kv.second.slot) {
-                if (s.ev) (void)hipEventSynchronize(s.ev), (void)hipEventDestroy(s.ev);
-                if (s.dev) (void)hipFree(s.dev);
-                if (s.host) (void)hipHostFree(s.host);
-            }
-            (void)hipSetDevice(cur);
-        }
+    void release() {
+        for (Slot& s : slot) s.drop_event(), s.free_mem();
     }
 };
-thread_local MixedRings t_mixed_rings;
+thread_local PerDevice<MixedRing> t_mixed_rings;
 
-hipError_t mixed_slot(size_t bytes, MixedRing::Slot** out) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+hipError_t mixed_slot(size_t bytes, Slot** out) {
+    MixedRing* t = nullptr;
+    hipError_t e = t_mixed_rings.here(&t);
     if (e != hipSuccess) return e;
-    MixedRing& t = t_mixed_rings.dev[dev];
-    MixedRing::Slot& s = t.slot[t.next++ % MixedRing::kSlots];
-    if (!s.ev && (e = hipEventCreateWithFlags(&s.ev, kSlotEventFlags)) != hipSuccess) return e;
-    if (s.busy && (e = hipEventSynchronize(s.ev)) != hipSuccess) return e;  // its last launch has read it
-    s.busy = false;
-    if (s.cap < bytes) {
-        if (s.dev) (void)hipFree(s.dev);
-        if (s.host) (void)hipHostFree(s.host);
-        s.dev = s.host = nullptr;
-        s.cap = 0;
+    const unsigned i = t->next++ % MixedRing::kSlots;
+    Slot& s = t->slot[i];
+    if ((e = s.event()) != hipSuccess || (e = s.wait()) != hipSuccess) return e;  // its last launch has read it
+    if (t->cap[i] < bytes) {
+        s.free_mem();
+        t->cap[i] = 0;
         const size_t cap = (std::max<size_t>(bytes, size_t(64) << 10) + 4095) / 4096 * 4096;
-        if ((e = hipMalloc(&s.dev, cap)) != hipSuccess) return e;
-        if ((e = hipHostMalloc(&s.host, cap, hipHostMallocDefault)) != hipSuccess) {
-            (void)hipFree(s.dev);
-            s.dev = nullptr;
-            return e;
-        }
-        s.cap = cap;
+        if ((e = s.alloc(cap)) != hipSuccess) return e;
+        t->cap[i] = cap;
     }
     *out = &s;
     return hipSuccess;
@@ -4392,7 +4034,7 @@ hipError_t mixed_slot(size_t bytes, MixedRing::Slot** out) {
 // copy(), launch what reads dev(), then done() -- also after a failed launch,
 // since the copy reads the slot whatever happened.
 struct StagedUpload {
-    MixedRing::Slot* slot = nullptr;
+    Slot* slot = nullptr;
     hipError_t acquire(size_t bytes) { return mixed_slot(bytes, &slot); }
     uint8_t* host() const { return slot->host; }
     const uint8_t* dev() const { return slot->dev; }
@@ -4400,10 +4042,7 @@ struct StagedUpload {
         return hipMemcpyAsync(slot->dev, slot->host, bytes, hipMemcpyHostToDevice, stream);
     }
     void done(hipStream_t stream) const {
-        if (hipEventRecord(slot->ev, stream) == hipSuccess)
-            slot->busy = true;
-        else
-            (void)hipStreamSynchronize(stream);
+        if (slot->record(stream) != hipSuccess) (void)hipStreamSynchronize(stream);
     }
 };
 
@@ -4742,7 +4381,7 @@ hipError_t locate_tables_upload(const uint8_t* q, uint32_t k, uint32_t c, hipStr
 }
 
 void locate_tables_release(const LocateTables& t, hipStream_t stream) {
-    if (t.slot) StagedUpload{static_cast<MixedRing::Slot*>(t.slot)}.done(stream);
+    if (t.slot) StagedUpload{static_cast<Slot*>(t.slot)}.done(stream);
 }
 
 hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint8_t* b0, uint32_t k, uint32_t xbit,
