@@ -178,10 +178,18 @@ int fec_decode_batch(const fec_t* code,
  * k <= 4 runs in one launch of matapply_mixed<k>; the per-pattern tables (and
  * host-side ids) are uploaded by a stream-ordered copy from pinned staging the
  * library owns, so pattern_of and patterns may be reused as soon as the call
- * returns.  k > 4 is cut into runs of consecutive stripes with one id, each run
- * one fec_decode_batch-style launch; a device-side pattern_of is first copied
- * to the host, which SYNCHRONISES the stream.  While the stream is being
- * captured into a graph the call returns FEC_EINVAL. */
+ * returns.  4 < k <= 32 with sz >= 2048 and the blocks in device memory is one
+ * launch too, of matapply_bsr<RT,mix> / <RT,lds,mix>: one record of routine
+ * addresses per pattern goes through the same staging, a device-side
+ * pattern_of is read where it is, and nothing synchronises the stream (each
+ * pattern costs the host one k x k inversion per call: fec_repair_plan_new
+ * builds the records once).  The remaining shapes -- k > 32, sz < 2048,
+ * page-locked host blocks, more than 32 MiB of records, no routine table on the
+ * device, ZFEC_HIP_MIXED_FUSED=0 -- are cut into runs of consecutive stripes with
+ * one id, each run one fec_decode_batch-style launch; on that path a
+ * device-side pattern_of is first copied to the host, which SYNCHRONISES the
+ * stream.  While the stream is being captured into a graph the call returns
+ * FEC_EINVAL. */
 int fec_decode_batch_mixed(const fec_t* code,
                            const gf* src, size_t src_block_stride, size_t src_stripe_stride,
                            gf* dst, size_t dst_block_stride, size_t dst_stripe_stride,
@@ -443,10 +451,17 @@ int fec_correct_rows(const fec_t* code, const unsigned* block_nums, size_t num_b
  *
  * k <= 4 runs on matrepair_mixed<k, r>, at most 8 rows per launch (11 targets
  * are launches of 8 and 3 rows over one upload of the tables; a group of rows
- * that no pattern uses is skipped).  k > 4 is cut into runs of consecutive
- * stripes with one id, each run one shared-matrix launch of that pattern's
- * used rows; a device-side pattern_of is first copied to the host, which
- * SYNCHRONISES the stream. */
+ * that no pattern uses is skipped).  4 < k <= 32 with sz >= 2048 and the blocks
+ * in device memory runs as ONE launch of matapply_bsr<RT,mix> (ntargets <= 10)
+ * or matapply_bsr<RT,lds,mix>, over one record per pattern (its rows' routine
+ * addresses and a live-row mask) uploaded through the same staging; a
+ * device-side pattern_of is read where it is and nothing synchronises the
+ * stream; a call whose targets are all FEC_REPAIR_NONE launches nothing.  The
+ * remaining shapes -- k > 32, sz < 2048, page-locked host blocks, more than 32
+ * MiB of records, no routine table on the device, ZFEC_HIP_MIXED_FUSED=0 -- are
+ * cut into runs of consecutive stripes with one id, each run one shared-matrix
+ * launch of that pattern's used rows; on that path a device-side pattern_of is
+ * first copied to the host, which SYNCHRONISES the stream. */
 #define FEC_REPAIR_NONE 0xFFFFFFFFu /* a target slot this pattern does not use */
 int fec_repair_batch(const fec_t* code,
                      const gf* src, size_t src_block_stride, size_t src_stripe_stride,
@@ -462,6 +477,46 @@ int fec_repair_batch(const fec_t* code,
  * one pattern.  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
 int fec_repair_rows(const fec_t* code, const unsigned* present, const unsigned* targets, size_t ntargets,
                     gf* rows);
+
+/* Pattern plans: a store has a small, stable set of erasure patterns, so the
+ * per-pattern work of fec_repair_batch -- one k x k inversion on the host, the
+ * tables or routine-address records, their upload -- is done once and reused.
+ *
+ * fec_repair_plan_new takes the pattern arguments of fec_repair_batch (present,
+ * targets, ntargets, npatterns; a decode plan is targets = 0..k-1 for every
+ * pattern, so it needs k <= 32) and checks them in the same order with the same
+ * messages: invalid fec_t; NULL present, targets or plan; ntargets == 0 or > 32;
+ * npatterns == 0 or more than 65536 patterns; a present number >= n; a
+ * duplicate among a pattern's present numbers; a target that is neither < n nor
+ * FEC_REPAIR_NONE.  Then FEC_ENODEV when no GPU is visible, FEC_EINVAL for a
+ * device that does not exist (-1: the current device).  The plan owns the
+ * host-side rows and masks and, in device memory of its own on that device, the
+ * records: matrepair_mixed's for k <= 4, matapply_bsr<..,mix>'s for 4 < k <= 32
+ * (none for k > 32, or where the device has no routine table: such a plan's
+ * calls take the run path).  It returns with the upload complete.  Plans are
+ * immutable: any thread may use one, concurrently, on any streams.
+ * fec_repair_plan_free(NULL) is harmless; a plan must outlive the calls (and
+ * graphs) that use it.
+ *
+ * fec_repair_batch_planned is fec_repair_batch with the plan in place of the
+ * pattern arguments: the same buffer rules, flags, strides and output, byte for
+ * byte.  pattern_of must not be NULL; blocks or device-side ids on another
+ * device than the plan's return FEC_EINVAL.  k <= 4 launches matrepair_mixed
+ * over the plan's records (row groups of 8), 4 < k <= 32 with sz >= 2048 and
+ * device blocks the mix form of matapply_bsr; everything else takes the run
+ * path from the plan's host rows.  With pattern_of in DEVICE memory those two
+ * launches touch nothing the library owns and reuses, so the call MAY BE
+ * CAPTURED INTO A GRAPH; with host-side ids (staged per call) it returns
+ * FEC_EINVAL under capture as fec_repair_batch does. */
+typedef struct fec_repair_plan fec_repair_plan_t;
+int fec_repair_plan_new(const fec_t* code, const unsigned* present, const unsigned* targets,
+                        size_t ntargets, size_t npatterns, int device, fec_repair_plan_t** plan);
+void fec_repair_plan_free(fec_repair_plan_t* plan);
+int fec_repair_batch_planned(const fec_repair_plan_t* plan,
+                             const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                             gf* dst, size_t dst_block_stride, size_t dst_stripe_stride,
+                             const unsigned* pattern_of, size_t sz, size_t nstripes,
+                             void* stream, unsigned flags);
 
 /* Batched calls over several GPUs of this process.  The nstripes stripes are
  * split into contiguous, balanced ranges, one per entry of devices[] (entry d

@@ -22,7 +22,7 @@ from ._fec import Error, device_count, test_from_agl, version
 
 __version__ = "0.1.0"
 
-__all__ = ["Encoder", "Decoder", "Error", "easyfec", "filefec", "cmdline_zfec", "cmdline_zunfec", "test_from_agl",
+__all__ = ["Encoder", "Decoder", "RepairPlan", "Error", "easyfec", "filefec", "cmdline_zfec", "cmdline_zunfec", "test_from_agl",
            "device_count", "version", "reuse_host_memory", "LOCATE_CLEAN", "LOCATE_MANY", "LOCATE_UNKNOWN"]
 
 # Decoder.locate_batch verdicts that are not a slot: FEC_LOCATE_CLEAN / _MANY /
@@ -184,6 +184,121 @@ def _capi_code(coder):
         with _as_error():
             code = coder._batch_code = capi.Code(coder.k, coder.m)
     return code
+
+
+class RepairPlan(object):
+    """The erasure patterns of a store resolved once (fec_repair_plan_new): the
+    per-pattern matrices are inverted and their kernel tables uploaded at
+    creation, and every later call only names each stripe's pattern.  Made by
+    Decoder.repair_plan / Decoder.decode_plan; immutable; close() frees it
+    (calls in flight, and graphs captured from them, must have finished).
+
+    patterns [P, k] and targets [P, t] are numpy arrays (-1: none); npatterns
+    is P."""
+
+    def __init__(self, coder, patterns, targets, decode):
+        import numpy as np
+
+        k, m = coder.k, coder.m
+        self.k, self.m = k, m
+        self.patterns, self.targets = patterns, targets
+        self.npatterns, self.ntargets = patterns.shape[0], targets.shape[1]
+        self._decode = decode
+        with _as_error():
+            self._plan = _capi_code(coder).repair_plan(np.ascontiguousarray(patterns, dtype=np.int64),
+                                                       np.ascontiguousarray(targets, dtype=np.int64))
+        self._coder = coder  # keeps the code alive
+
+    def close(self):
+        """Free the plan; harmless when repeated."""
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan is not None:
+            plan.close()
+
+    def _ids(self, pattern_of, ns, device):
+        """(pointer, keep-alive) of nstripes uint32 ids from a 1-D integer list,
+        numpy array or torch tensor; a device tensor stays on the device."""
+        import numpy as np
+
+        if hasattr(pattern_of, "data_ptr"):
+            import torch
+
+            if pattern_of.dim() != 1 or pattern_of.dtype.is_floating_point:
+                raise Error("Precondition violation: pattern_of is required to be a 1-D integer array")
+            if pattern_of.shape[0] != ns:
+                raise Error("Precondition violation: pattern_of is required to hold nstripes = %d ids, not %d"
+                            % (ns, pattern_of.shape[0]))
+            if pattern_of.is_cuda:
+                if pattern_of.device != device:
+                    raise Error("Precondition violation: device pattern_of ids are required to be on the blocks' "
+                                "device")
+                ids = pattern_of.to(torch.int32).contiguous()  # non-negative ids: the bits of uint32
+                return ids.data_ptr(), ids
+            host = pattern_of.numpy()
+        else:
+            host = np.asarray(pattern_of)
+            if host.ndim != 1 or (host.size and host.dtype.kind not in "iu"):
+                raise Error("Precondition violation: pattern_of is required to be a 1-D integer array")
+            if host.shape[0] != ns:
+                raise Error("Precondition violation: pattern_of is required to hold nstripes = %d ids, not %d"
+                            % (ns, host.shape[0]))
+        if host.size and (host.min() < 0 or host.max() >= self.npatterns):
+            raise Error("Precondition violation: pattern_of ids are required to be in [0, %d]" % (self.npatterns - 1))
+        ids = np.ascontiguousarray(host, dtype=np.uint32)
+        return ids.ctypes.data, ids
+
+    def repair_batch(self, blocks, pattern_of, out=None):
+        """Decoder.repair_batch with the plan's patterns: blocks is a uint8
+        device tensor [nstripes, k, sz], pattern_of a 1-D integer list, numpy
+        array or torch tensor (host or device) naming each stripe's pattern.
+        Returns [nstripes, t, sz] under Decoder.repair_batch's rules: a new
+        tensor (block-major when the input was; rows of -1 targets
+        unspecified), or `out` with those rows untouched."""
+        k, t = self.k, self.ntargets
+        if self._plan is None:
+            raise Error("Precondition violation: the repair plan is closed")
+        if _is_host_array(blocks):
+            raise Error("Precondition violation: repair_batch takes a device tensor; host (numpy) blocks are not "
+                        "staged by this call")
+        is_tensor = type(blocks).__module__.startswith("torch") and hasattr(blocks, "data_ptr")
+        if not is_tensor or str(blocks.dtype) != "torch.uint8" or blocks.dim() != 3:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz]" % k)
+        if blocks.shape[1] != k:
+            raise Error("Precondition violation: blocks is required to hold %d blocks per stripe, not %d"
+                        % (k, blocks.shape[1]))
+        ns, sz = blocks.shape[0], blocks.shape[2]
+        ids_ptr, ids = self._ids(pattern_of, ns, blocks.device)
+        if out is not None:
+            out_ok = type(out).__module__.startswith("torch") and hasattr(out, "data_ptr")
+            if not out_ok or str(out.dtype) != "torch.uint8" or tuple(out.shape) != (ns, t, sz):
+                raise Error("Precondition violation: out is required to be a uint8 tensor [nstripes, t, sz] = "
+                            "[%d, %d, %d]" % (ns, t, sz))
+            if out.device != blocks.device:
+                raise Error("Precondition violation: out is required to be on the blocks' device")
+            if (sz > 1 and out.stride(2) != 1) or min(out.stride(0), out.stride(1)) < 0:
+                raise Error("Precondition violation: out rows are required to be contiguous along sz")
+        if not blocks.is_cuda:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
+                        "not a host tensor" % k)
+        ns, sz, sbs, sss, ptr = _batch_view(blocks, k, "blocks")
+        if out is None:
+            out = _batch_out(blocks, sss < sbs, ns, t, sz)
+        if ns and sz:
+            optr, obs, oss = _batch_strides(out)
+            stream, flags = _batch_call_args(blocks)
+            # `ids` need only outlive the call: host ids are copied into the
+            # library's staging, device ids are read by work of this stream
+            with _as_error():
+                self._plan.repair_batch(ptr, sbs, sss, optr, obs, oss, ids_ptr, sz, ns, stream=stream, flags=flags)
+        return out
+
+    def decode_batch(self, blocks, pattern_of):
+        """Decoder.decode_batch_mixed with the plan's patterns (a plan made by
+        Decoder.decode_plan): a new [nstripes, k, sz] tensor of every stripe's
+        k primaries in order, block-major when the input was."""
+        if not self._decode:
+            raise Error("Precondition violation: decode_batch takes a plan made by Decoder.decode_plan")
+        return self.repair_batch(blocks, pattern_of)
 
 
 class Encoder(_fec.Encoder):
@@ -585,6 +700,64 @@ class Decoder(_fec.Decoder):
                                               np.ascontiguousarray(tgts, dtype=np.int64), ids_ptr, sz, ns,
                                               stream=stream, flags=flags)
         return out
+
+    def repair_plan(self, patterns, targets):
+        """A RepairPlan of P erasure patterns for repair_batch's work: patterns
+        is an integer array [P, k] (list of lists, numpy array or torch tensor)
+        of the block numbers a stripe's slots hold, distinct, in [0, m-1], in
+        any slot order; targets an integer array [P, t], 1 <= t <= 32, of the
+        block numbers to rebuild, in [0, m-1] or -1 for none.  The plan lives
+        on the current device."""
+        return self._plan(patterns, targets, False)
+
+    def decode_plan(self, patterns):
+        """A RepairPlan whose every pattern rebuilds primaries 0..k-1 in order:
+        decode_batch_mixed's work (k <= 32)."""
+        import numpy as np
+
+        if self.k > 32:
+            raise Error("Precondition violation: decode_plan takes codes of k <= 32, not k = %d (a plan holds at most "
+                        "32 rows per pattern)" % self.k)
+        pats = patterns.cpu().numpy() if hasattr(patterns, "data_ptr") else np.asarray(patterns)
+        n = pats.shape[0] if pats.ndim == 2 else 0
+        return self._plan(pats, np.tile(np.arange(self.k, dtype=np.int64), (n, 1)), True)
+
+    def _plan(self, patterns, targets, decode):
+        import numpy as np
+
+        k, m = self.k, self.m
+
+        def host_table(x, what):
+            a = x.cpu().numpy() if hasattr(x, "data_ptr") else np.asarray(x)
+            if a.ndim != 2 or (a.size and a.dtype.kind not in "iu"):
+                raise Error("Precondition violation: %s is required to be a 2-D integer array" % what)
+            return a
+
+        pats, tgts = host_table(patterns, "patterns"), host_table(targets, "targets")
+        if pats.shape[1] != k:
+            raise Error("Precondition violation: patterns is required to be an integer array [P, k = %d]" % k)
+        if pats.shape[0] < 1:
+            raise Error("Precondition violation: patterns is required to hold at least one pattern")
+        if tgts.shape[0] != pats.shape[0]:
+            raise Error("Precondition violation: targets is required to hold one row per pattern: %d rows, %d "
+                        "patterns" % (tgts.shape[0], pats.shape[0]))
+        t = tgts.shape[1]
+        if t < 1 or t > 32:
+            raise Error("Precondition violation: targets is required to hold between 1 and 32 block nums per pattern, "
+                        "not %d" % t)
+        if pats.min() < 0 or pats.max() >= m:
+            bad = pats[(pats < 0) | (pats >= m)][0]
+            raise Error("Precondition violation: block nums are required to be in [0, m-1] = [0, %d], but one was %d"
+                        % (m - 1, bad))
+        for row in pats:
+            if len(set(row.tolist())) != k:
+                raise Error("Precondition violation: the block nums of a stripe are required to be distinct, but one "
+                            "stripe has %r" % (row.tolist(),))
+        if tgts.min() < -1 or tgts.max() >= m:
+            bad = tgts[(tgts < -1) | (tgts >= m)][0]
+            raise Error("Precondition violation: targets are required to be in [0, m-1] = [0, %d] or -1 (none), but "
+                        "one was %d" % (m - 1, bad))
+        return RepairPlan(self, pats.astype(np.int64), tgts.astype(np.int64), decode)
 
     def verify_batch(self, blocks, blocknums):
         """Check many independent stripes for consistency without writing any

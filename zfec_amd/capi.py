@@ -67,6 +67,9 @@ SYMBOLS = [
     ("fec_locate_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
     ("fec_correct_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
     ("fec_correct_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
+    ("fec_repair_plan_new", ctypes.c_int, [_P, _UP, _UP, _SZ, _SZ, ctypes.c_int, _PP]),
+    ("fec_repair_plan_free", None, [_P]),
+    ("fec_repair_batch_planned", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _U]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_REPAIR_NONE = 0xFFFFFFFF  # a target slot its pattern does not use
@@ -295,6 +298,20 @@ class Code(object):
         if st:
             check(st)
 
+    def repair_plan(self, present, targets, device=None):
+        """fec_repair_plan_new: the patterns of repair_batch (`present` [P, k],
+        `targets` [P, t], -1 for FEC_REPAIR_NONE) resolved once into a
+        RepairPlan on `device` (None: the current device).  A decode plan is
+        targets = 0..k-1 for every pattern."""
+        pres, npat, _ = _uint_table(present, self.k, "present is required to be [npatterns, k = %d]" % self.k)
+        tgts, ntp, nt = _uint_table(targets, None, "targets is required to be [npatterns, ntargets]")
+        if ntp != npat:
+            raise FecError("targets is required to hold one row per pattern: %d rows, %d patterns" % (ntp, npat))
+        out = ctypes.c_void_p()
+        check(lib().fec_repair_plan_new(self.ptr, pres[0], tgts[0], nt, npat, -1 if device is None else int(device),
+                                        ctypes.byref(out)))
+        return RepairPlan(out.value, self.k, nt, npat)
+
     def verify_batch(self, src, sbs, sss, block_nums, sz, nstripes, mismatch_ptr, stream=0, flags=FEC_FLAG_ASYNC):
         """fec_verify_batch: slot j of every stripe holds block block_nums[j],
         the first k slots the basis, the rest the checks; `mismatch_ptr` is the
@@ -343,6 +360,33 @@ class Code(object):
     def decode_ptrs(self, in_addrs, out_addrs, index, sz, stream=0, flags=FEC_FLAG_ASYNC):
         check(lib().fec_decode_ex(self.ptr, ptr_array(in_addrs), ptr_array(out_addrs), uint_array(index),
                                   sz, stream or None, flags))
+
+
+class RepairPlan(object):
+    """A fec_repair_plan_t*: immutable, usable from any thread on any stream
+    until close() (fec_repair_plan_free).  The caller keeps it alive as long
+    as calls, and graphs captured from them, are in flight."""
+
+    def __init__(self, ptr, k, ntargets, npatterns):
+        self.ptr, self.k, self.ntargets, self.npatterns = ptr, k, ntargets, npatterns
+
+    def repair_batch(self, src, sbs, sss, dst, dbs, dss, pattern_of_ptr, sz, nstripes, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_repair_batch_planned: Code.repair_batch's arguments without the
+        patterns; `pattern_of_ptr` is the address of nstripes uint32 pattern
+        ids in host or device memory."""
+        if not self.ptr:
+            raise FecError("the repair plan is closed")
+        st = lib().fec_repair_batch_planned(self.ptr, src, sbs, sss, dst, dbs, dss, pattern_of_ptr or None, sz, nstripes,
+                                            stream or None, flags)
+        if st:
+            check(st)
+
+    def close(self):
+        if getattr(self, "ptr", None) and _lib is not None:
+            _lib.fec_repair_plan_free(self.ptr)
+        self.ptr = None
+
+    __del__ = close
 
 
 def mixed_decode_rows(code, pattern):

@@ -52,6 +52,8 @@ Config* read_env() {
     // shapes take the fused kernel; 0 is read as 1, 4294967295 turns it off.
     const size_t vf = env_size("ZFEC_HIP_VERIFY_FUSED_MIN", kVerifyFusedMin);
     c->verify_fused_min = vf ? vf : 1;
+    const char* mf = env("ZFEC_HIP_MIXED_FUSED");
+    c->mixed_fused = !(mf && mf[0] == '0');
     return c;
 }
 

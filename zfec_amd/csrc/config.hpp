@@ -35,6 +35,7 @@ struct Config {
     size_t grid_cap;       // ZFEC_HIP_GRID_CAP: most workgroups per launch of the unit kernels (reg, rows, pair, lds) and of the generated bit-sliced kernels; below their own caps, also of matapply_bsg, matapply_bsr / bsr_ks and matverify_bsr (0: automatic)
     size_t verify_scratch; // ZFEC_HIP_VERIFY_SCRATCH: cap of fec_verify_batch's expected-row scratch, bytes (64 MiB; only lowered)
     uint64_t verify_fused_min;  // ZFEC_HIP_VERIFY_FUSED_MIN: 2-KiB units from which a wide verify runs matverify_bsr (config.cpp)
+    bool mixed_fused;      // ZFEC_HIP_MIXED_FUSED=0: pattern-per-stripe calls of 4 < k <= 32 take the run path, not matapply_bsr<..,mix> (the A/B and a second reference)
 };
 
 const Config& config();

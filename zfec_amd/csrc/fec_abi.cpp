@@ -1475,6 +1475,16 @@ int for_each_id_run(const unsigned* pattern_of, int idev, size_t nstripes, size_
     return FEC_OK;
 }
 
+// Whether a pattern-per-stripe call of a wider code (4 < k <= 32) is ONE launch
+// of the mix form of the bit-sliced kernels (kernels.hpp launch_bsr_mixed): r
+// rows per pattern, blocks in device memory (page-locked host blocks keep the
+// run path), the records within kBsrMixMaxBytes, ZFEC_HIP_MIXED_FUSED not 0.
+bool fused_mixed_shape(unsigned k, size_t r, size_t sz, size_t npatterns, const BatchMem& mem) {
+    return config().mixed_fused && mem.bdev[0] >= 0 && mem.bdev[1] >= 0 && r <= kRepairMaxRows &&
+           bsr_mix_ok(k, static_cast<uint32_t>(r), sz) &&
+           npatterns * bsr_mix_record_bytes(k, static_cast<uint32_t>(r)) <= kBsrMixMaxBytes;
+}
+
 int run_mixed(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst, size_t dbs, size_t dss,
               const unsigned* patterns, size_t npatterns, const unsigned* pattern_of, int idev, size_t sz,
               size_t nstripes, void* stream, unsigned flags) {
@@ -1489,13 +1499,16 @@ int run_mixed(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst,
     gf* const zdst = const_cast<gf*>(mem.z[1]);
     hipStream_t st = mem.st;
     hipError_t e;
-    if (k <= kMixedMaxK) {
+    // one launch: the register kernels for k <= 4, the mix form of the bit-sliced
+    // kernels for wider codes on device memory (fused_mixed_shape)
+    bool one = k <= kMixedMaxK || fused_mixed_shape(k, k, sz, npatterns, mem);
+    if (one) {
         thread_local std::vector<uint8_t> rows;
         rows.resize(npatterns * k * k);
         for (size_t p = 0; p < npatterns; ++p)
             if (mixed_rows(code, patterns + p * k, &rows[p * k * k])) return t_status;
-        const uint8_t* in[kMixedMaxK];
-        uint8_t* out[kMixedMaxK];
+        const uint8_t* in[kMaxIn];
+        uint8_t* out[kMaxIn];
         for (unsigned j = 0; j < k; ++j) {
             in[j] = zsrc + j * sbs;
             out[j] = zdst + j * dbs;
@@ -1513,9 +1526,14 @@ int run_mixed(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst,
         m.in_sstride = sss;
         m.out_sstride = dss;
         ++t_launches;
-        if ((e = launch_mixed(m, st)) != hipSuccess) return hip_fail(e, "launch_mixed");
-    } else {
-        // codes past the register shapes: each run through the shared-pattern batched path
+        e = launch_mixed(m, st);
+        if (e == hipErrorNotSupported && k > kMixedMaxK)
+            one = false;  // the launch declined with nothing enqueued: the run path
+        else if (e != hipSuccess)
+            return hip_fail(e, "launch_mixed");
+    }
+    if (!one) {
+        // what the one launch does not take: each run through the shared-pattern batched path
         const unsigned jf = (flags & FEC_FLAG_LIBRARY_STREAM) | FEC_FLAG_ASYNC;
         if (for_each_id_run<std::vector<uint8_t>>(
                 pattern_of, idev, nstripes, npatterns, st,
@@ -2125,19 +2143,20 @@ int run_repair(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst
     hipError_t e;
     thread_local std::vector<uint8_t> rows;
     thread_local std::vector<uint32_t> masks;
+    bool runs = false;
     if (!pattern_of) {
         // one pattern for every stripe: a shared-matrix application, no new kernel
         rows.resize(nt * k);
         uint32_t mask = 0;
         if (repair_rows(code, present, targets, nt, rows.data(), &mask)) return t_status;
         if (repair_shared(rows.data(), mask, k, nt, zsrc, sbs, sss, zdst, dbs, dss, sz, nstripes, st)) return t_status;
-    } else if (k <= kMixedMaxK) {
+    } else if (k <= kMixedMaxK || fused_mixed_shape(k, nt, sz, npatterns, mem)) {
         rows.resize(npatterns * nt * k);
         masks.resize(npatterns);
         for (size_t p = 0; p < npatterns; ++p)
             if (repair_rows(code, present + p * k, targets + p * nt, nt, &rows[p * nt * k], &masks[p]))
                 return t_status;
-        const uint8_t* in[kMixedMaxK];
+        const uint8_t* in[kMaxIn];
         uint8_t* out[kRepairMaxRows];
         for (unsigned j = 0; j < k; ++j) in[j] = zsrc + j * sbs;
         for (size_t i = 0; i < nt; ++i) out[i] = zdst + i * dbs;
@@ -2156,9 +2175,16 @@ int run_repair(const fec_t* code, const gf* src, size_t sbs, size_t sss, gf* dst
         r.in_sstride = sss;
         r.out_sstride = dss;
         ++t_launches;
-        if ((e = launch_repair(r, st)) != hipSuccess) return hip_fail(e, "launch_repair");
+        e = launch_repair(r, st);
+        if (e == hipErrorNotSupported && k > kMixedMaxK)
+            runs = true;  // the launch declined with nothing enqueued: the run path
+        else if (e != hipSuccess)
+            return hip_fail(e, "launch_repair");
     } else {
-        // codes past the register shapes: each run one shared-matrix application of its pattern's live rows
+        runs = true;
+    }
+    if (runs) {
+        // what the one launch does not take: each run one shared-matrix application of its pattern's live rows
         typedef std::pair<std::vector<uint8_t>, uint32_t> RowsAndMask;
         if (for_each_id_run<RowsAndMask>(
                 pattern_of, idev, nstripes, npatterns, st,
@@ -2219,6 +2245,187 @@ FEC_API int fec_repair_batch(const fec_t* code, const gf* src, size_t src_block_
     return guarded([&] {
         return run_repair(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,
                           present, targets, ntargets, npatterns, pattern_of, idev, sz, nstripes, stream, flags);
+    });
+}
+
+// ---- pattern plans: the per-pattern work of fec_repair_batch done once --------------------
+// Immutable after fec_repair_plan_new: the host-side rows and masks (the run
+// path) and, in device memory of its own, the records the kernels read.
+struct fec_repair_plan {
+    unsigned long magic = 0;
+    unsigned k = 0;
+    size_t nt = 0, npatterns = 0;
+    int device = -1;
+    std::vector<uint8_t> rows;    // npatterns x nt x k
+    std::vector<uint32_t> masks;  // npatterns live-row masks
+    void* records = nullptr;      // device memory; null: every call takes the run path
+};
+
+namespace {
+constexpr unsigned long kPlanMagic = 0x7265706c616eul;  // "replan"
+
+bool valid_plan(const fec_repair_plan_t* p) { return p && p->magic == kPlanMagic; }
+
+int run_repair_planned(const fec_repair_plan_t* plan, const gf* src, size_t sbs, size_t sss, gf* dst, size_t dbs,
+                       size_t dss, const unsigned* pattern_of, int idev, size_t sz, size_t nstripes, void* stream,
+                       unsigned flags) {
+    static const char fn[] = "fec_repair_batch_planned";
+    const unsigned k = plan->k;
+    const size_t nt = plan->nt, npatterns = plan->npatterns;
+    if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
+    const BatchBuf bufs[2] = {{src, (nstripes - 1) * sss + (k - 1) * sbs + sz, "src"},
+                              {dst, (nstripes - 1) * dss + (nt - 1) * dbs + sz, "dst"}};
+    BatchMem mem;
+    if (resolve_batch(mem, fn, bufs, 2, "pattern_of", idev, stream, flags, nullptr)) return t_status;
+    if ((mem.bdev[0] >= 0 || mem.bdev[1] >= 0 || idev >= 0) && mem.dev != plan->device)
+        return set_status(FEC_EINVAL, "%s: the plan lives on device %d, the %s on device %d", fn, plan->device,
+                          mem.bdev[0] >= 0 || mem.bdev[1] >= 0 ? "blocks" : "ids", mem.dev);
+    const gf* const zsrc = mem.z[0];
+    gf* const zdst = const_cast<gf*>(mem.z[1]);
+    hipStream_t st = mem.st;
+    hipError_t e;
+    // one launch over the plan's records: the register kernels (any memory the
+    // device sees) or, on device blocks, the mix form of the bit-sliced kernels
+    bool one = plan->records && mem.dev == plan->device &&
+               (k <= kMixedMaxK || (config().mixed_fused && mem.bdev[0] >= 0 && mem.bdev[1] >= 0 &&
+                                    bsr_mix_ok(k, static_cast<uint32_t>(nt), sz)));
+    // only that launch with the ids where they are touches nothing the library owns and reuses
+    const bool capturing = stream_capturing(st);
+    if (capturing && !(one && idev >= 0))
+        return set_status(FEC_EINVAL, "%s: the stream is being captured into a graph (%s)", fn,
+                          one ? "host-side ids are staged when the call is made" : kCaptureMemory);
+    if (one) {
+        const uint8_t* in[kMaxIn];
+        uint8_t* out[kRepairMaxRows];
+        for (unsigned j = 0; j < k; ++j) in[j] = zsrc + j * sbs;
+        for (size_t i = 0; i < nt; ++i) out[i] = zdst + i * dbs;
+        RepairSpec r;
+        r.k = k;
+        r.t = static_cast<uint32_t>(nt);
+        r.rows = nullptr;
+        r.masks = plan->masks.data();
+        r.npatterns = static_cast<uint32_t>(npatterns);
+        r.ids_host = idev < 0 ? pattern_of : nullptr;
+        r.ids_dev = idev < 0 ? nullptr : pattern_of;
+        r.in = in;
+        r.out = out;
+        r.sz = sz;
+        r.nstripes = nstripes;
+        r.in_sstride = sss;
+        r.out_sstride = dss;
+        ++t_launches;
+        e = launch_repair_records(r, plan->records, st);
+        if (e == hipErrorNotSupported && k > kMixedMaxK && !capturing)
+            one = false;  // the launch declined with nothing enqueued: the run path
+        else if (e != hipSuccess)
+            return hip_fail(e, "launch_repair_records");
+    }
+    if (!one) {
+        // the run path of fec_repair_batch, from the plan's host rows
+        struct Ref {
+            const uint8_t* rows;
+            uint32_t mask;
+        };
+        if (for_each_id_run<Ref>(
+                pattern_of, idev, nstripes, npatterns, st,
+                [&](unsigned id, Ref& r) {
+                    r.rows = &plan->rows[size_t(id) * nt * k];
+                    r.mask = plan->masks[id];
+                    return int(FEC_OK);
+                },
+                [&](const Ref& r, size_t s0, size_t s1) {
+                    return repair_shared(r.rows, r.mask, k, nt, zsrc + s0 * sss, sbs, sss, zdst + s0 * dss, dbs, dss,
+                                         sz, s1 - s0, st);
+                }))
+            return t_status;
+    }
+    if (!(flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_repair_plan_new(const fec_t* code, const unsigned* present, const unsigned* targets, size_t ntargets,
+                                size_t npatterns, int device, fec_repair_plan_t** plan) {
+    // every check that needs no GPU comes first, in fec_repair_batch's order
+    if (plan) *plan = nullptr;
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (!present) return set_status(FEC_EINVAL, "present is NULL");
+    if (!targets) return set_status(FEC_EINVAL, "targets is NULL");
+    if (!plan) return set_status(FEC_EINVAL, "plan is NULL");
+    if (ntargets == 0 || ntargets > kRepairMaxRows)
+        return set_status(FEC_EINVAL, "ntargets is %zu: a plan takes between 1 and %u targets per pattern", ntargets,
+                          unsigned(kRepairMaxRows));
+    if (npatterns == 0) return set_status(FEC_EINVAL, "npatterns is 0: a plan holds at least one pattern");
+    if (npatterns > kMixedMaxPatterns)
+        return set_status(FEC_EINVAL, "%zu patterns: a plan takes at most %u", npatterns, unsigned(kMixedMaxPatterns));
+    if (check_repair_patterns(code, present, targets, ntargets, npatterns)) return t_status;
+    const int ngpu = gpu_available();
+    if (!ngpu) return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return set_status(FEC_ENODEV, "no current HIP device");
+    if (device >= ngpu) return set_status(FEC_EINVAL, "device %d: HIP sees %d", device, ngpu);
+    return guarded([&] {
+        const unsigned k = code->k;
+        std::unique_ptr<fec_repair_plan> p(new fec_repair_plan);
+        p->k = k;
+        p->nt = ntargets;
+        p->npatterns = npatterns;
+        p->device = device;
+        p->rows.resize(npatterns * ntargets * k);
+        p->masks.resize(npatterns);
+        for (size_t q = 0; q < npatterns; ++q)
+            if (repair_rows(code, present + q * k, targets + q * ntargets, ntargets, &p->rows[q * ntargets * k],
+                            &p->masks[q]))
+                return t_status;
+        // the records, where a kernel reads them (k <= 32) and they stay within the cap
+        const size_t bytes = repair_records_bytes(k, static_cast<uint32_t>(ntargets), npatterns);
+        if (bytes && (k <= kMixedMaxK || bytes <= kBsrMixMaxBytes)) {
+            DeviceGuard guard(device);
+            std::vector<uint8_t> host(bytes);
+            hipError_t e = repair_records_fill(host.data(), p->rows.data(), p->masks.data(), npatterns, k,
+                                               static_cast<uint32_t>(ntargets));
+            if (e == hipSuccess) {
+                if ((e = hipMalloc(&p->records, bytes)) != hipSuccess)
+                    return set_status(FEC_ENOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+                if ((e = hipMemcpy(p->records, host.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+                    (void)hipFree(p->records);
+                    return hip_fail(e, "hipMemcpy H2D (plan records)");
+                }
+            } else if (e != hipErrorNotSupported) {
+                return hip_fail(e, "repair_records_fill");
+            }  // no routine table on the device: no records, the run path
+        }
+        p->magic = kPlanMagic;
+        *plan = p.release();
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API void fec_repair_plan_free(fec_repair_plan_t* plan) {
+    if (!valid_plan(plan)) return;
+    plan->magic = 0;
+    if (plan->records) {
+        DeviceGuard guard(plan->device);
+        (void)hipFree(plan->records);
+    }
+    delete plan;
+}
+
+FEC_API int fec_repair_batch_planned(const fec_repair_plan_t* plan, const gf* src, size_t src_block_stride,
+                                     size_t src_stripe_stride, gf* dst, size_t dst_block_stride,
+                                     size_t dst_stripe_stride, const unsigned* pattern_of, size_t sz, size_t nstripes,
+                                     void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    if (!valid_plan(plan)) return set_status(FEC_EINVAL, "invalid fec_repair_plan_t");
+    if (!src || !dst) return set_status(FEC_EINVAL, "NULL buffer");
+    if (!pattern_of) return set_status(FEC_EINVAL, "pattern_of is NULL");
+    int idev = -1;
+    if (check_patterns_and_ids(plan->npatterns, nstripes, pattern_of, &idev, [] { return int(FEC_OK); }))
+        return t_status;
+    if (sz == 0 || nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_repair_planned(plan, src, src_block_stride, src_stripe_stride, dst, dst_block_stride,
+                                  dst_stripe_stride, pattern_of, idev, sz, nstripes, stream, flags);
     });
 }
 

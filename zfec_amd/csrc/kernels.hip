@@ -43,6 +43,10 @@
 //                       precompiled multiply-by-constant routines
 //                       (gf_routines.inc); past 32 inputs or 40 rows its
 //                       pointers and coefficients come from a device-side table.
+//   matapply_bsr<RT,mix> matapply_bsr for 4 < k <= 32 with a pattern id per stripe:
+//                       the id picks the record (routine addresses, live-row
+//                       mask) its unit walks with (fec_decode_batch_mixed,
+//                       fec_repair_batch, fec_repair_batch_planned).
 //   matverify_bsr<RT>   matapply_bsr's walk for 4 < k <= 32 with the rows kept as
 //                       bit-planes and compared with the stored check blocks
 //                       instead of stored: fec_verify_batch on wide codes reads
@@ -2208,6 +2212,26 @@ struct alignas(16) BsrTblJob {
 };
 static_assert(sizeof(BsrTblJob) <= 4096, "kernel arguments are limited to 4 KiB");
 
+// Mix form (a pattern per stripe; 4 < k <= 32, r <= kRepairMaxRows): every
+// pattern's r x k matrix is a record in device memory -- its routine addresses
+// in the walk order [wave][input][RT] (fill_bsr_addrs with one group, no input
+// split), then one dword live-row mask (bit i: row i is stored), padded to 16
+// bytes -- and ids[s] names the record of stripe s.  The tiles depend on r
+// alone (bsr_mix_tiles), so a record built once serves every call.  Ids,
+// records and masks are only read, by scalar loads: an earlier copy or kernel
+// of the stream wrote them (the scalar cache starts every kernel empty).
+constexpr int kBsrMixPtrs = kMaxIn + static_cast<int>(kRepairMaxRows);
+struct alignas(16) BsrMixJob {
+    uint64_t sz, in_sstride, out_sstride;
+    uint32_t nstripes, k, r, cps, gs_c, gs_s;
+    uint32_t npatterns;
+    uint32_t stride;                  // uint64 words per record
+    const uint32_t* ids;              // device: nstripes pattern ids
+    const uint64_t* records;          // device: npatterns records
+    const uint8_t* ptr[kBsrMixPtrs];  // k input block pointers, then r output block pointers
+};
+static_assert(sizeof(BsrMixJob) <= 4096, "kernel arguments are limited to 4 KiB");
+
 // Reads input j's RT routine addresses (scalar loads).
 // (The row offset is added to a 64-bit pointer, so the loads share one
 // address and merge into s_load_dwordx16 / x4 with immediate offsets.)
@@ -2397,6 +2421,10 @@ template <int RT, bool TBL, bool CMB, class J>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void matapply_bsr(const J job) {
     constexpr bool VFY = std::is_same<J, BsrVfyJob>::value || std::is_same<J, BsrVfyTblJob>::value;
     static_assert(!VFY || !CMB, "the verify forms share planes, not combinations");
+    // J = BsrMixJob (matapply_bsr<RT,lds,mix>): a pattern id per stripe picks the
+    // record the routine addresses and the live-row mask are read from
+    constexpr bool MIX = std::is_same<J, BsrMixJob>::value;
+    static_assert(!MIX || (TBL && !CMB), "the mix form: block pointers as the table form's, planes shared");
     // [input][half][lane] planes, or (CMB) [input][7 x (4 dwords)][lane] + [2 dwords][lane] combinations
     extern __shared__ u32x4 bsr_planes[];
     constexpr uint32_t kIn = bsr_in_bytes<CMB>() / 16;  // u32x4 per input
@@ -2410,7 +2438,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
     const uint32_t ns = job.nstripes;
     uint32_t ng = 1;
     KPtr<J> kj = kernarg_job<J>();
-    if constexpr (TBL) ng = job.ngroups;
+    if constexpr (TBL && !MIX) ng = job.ngroups;
     auto in_ptr = [&](uint32_t j) -> const uint8_t* {
         if constexpr (TBL)
             return kj->ptr[j];
@@ -2425,12 +2453,36 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
     };
     const uint64_t sz = job.sz;
     uint32_t s = blockIdx.x / job.cps, c = blockIdx.x - s * job.cps;
+    auto advance = [&] {  // the grid-stride step, with its carry
+        c += job.gs_c;
+        s += job.gs_s;
+        if (c >= job.cps) {
+            c -= job.cps;
+            ++s;
+        }
+    };
     while (s < ns * ng) {
         const uint32_t g = TBL && ng > 1 ? s / ns : 0u, stripe = s - g * ns;
         const uint32_t gr0 = g * r / ng, grn = (g + 1) * r / ng - gr0;
         const uint32_t r0 = gr0 + wave * grn / nw, rows = gr0 + (wave + 1) * grn / nw - r0;
+        uint32_t id = 0;
+        if constexpr (MIX) {
+            // the stripe's id: one scalar load, the same in every wave of the
+            // workgroup; an id that names no record skips the unit before any
+            // record read and any barrier, and nothing of the stripe is written
+            // (the id's fields by a fresh look at the arguments, not held across the walk)
+            const KPtr<J> km = kernarg_job<J>();
+            id = __builtin_amdgcn_readfirstlane(((CU32)km->ids)[stripe]);
+            if (id >= km->npatterns) {
+                advance();
+                continue;
+            }
+        }
         const CU64 ca = [&] {
-            if constexpr (TBL)
+            if constexpr (MIX) {
+                const KPtr<J> km = kernarg_job<J>();
+                return (CU64)km->records + static_cast<uint64_t>(id) * km->stride + wave * k * RT;
+            } else if constexpr (TBL)
                 return (CU64)job.addr + (g * nw + wave) * k * RT;
             else
                 return (CU64)kj->addr + wave * k * RT;
@@ -2627,9 +2679,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
             bsr_verify_rows<RT>(acc, rows, so + lane * 16u, [&](uint32_t rr) { return out_ptr(r0 + rr); },
                                 kv->mismatch + static_cast<uint64_t>(stripe) * kv->words, kv->bit0 + r0);
         } else {
+            // MIX: the record's live-row mask (the dword after its nw tiles of
+            // addresses), read here, after the walk; a row whose bit is clear
+            // is not stored
+            uint32_t live = ~0u;
+            if constexpr (MIX)
+                live = __builtin_amdgcn_readfirstlane(((CU32)(ca + (nw - wave) * k * RT))[0]) >> r0;
 #pragma unroll
             for (int rr = 0; rr < RT; ++rr) {
-                if (static_cast<uint32_t>(rr) < rows) {  // wave-uniform
+                if (static_cast<uint32_t>(rr) < rows && ((live >> rr) & 1u)) {  // wave-uniform
                     transpose8(acc[rr]);
                     uint8_t* op = out_ptr(r0 + rr) + ob;
                     store16_out<true>(op, u32x4{acc[rr][0], acc[rr][1], acc[rr][2], acc[rr][3]});
@@ -2637,12 +2695,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void m
                 }
             }
         }
-        c += job.gs_c;
-        s += job.gs_s;
-        if (c >= job.cps) {
-            c -= job.cps;
-            ++s;
-        }
+        advance();
     }
 }
 
@@ -2729,6 +2782,56 @@ __global__ __launch_bounds__(64) void matapply_bsr_solo(const BsrJob job) {
                 store16_out<true>(op + 1024, u32x4{acc[rr][4], acc[rr][5], acc[rr][6], acc[rr][7]});
             }
         }
+    }
+}
+
+// The mix form of the one-wave kernel (matapply_bsr<RT,mix>; BsrMixJob, r <=
+// 10): the unit's stripe, hence its pattern id and record, is the same in every
+// lane -- read through readfirstlane and constant-address-space pointers, so id,
+// addresses and mask are scalar loads.  An id that names no record skips the
+// unit: nothing of the stripe is read or written.  The walk over units is the
+// LDS-phase kernel's (c += gs_c, s += gs_s with the carry).
+template <int RT>
+__global__ __launch_bounds__(64) void matapply_bsr_mix_solo(const BsrMixJob job) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t k = job.k, r = job.r;
+    const KPtr<BsrMixJob> kj = kernarg_job<BsrMixJob>();
+    const uint64_t sz = job.sz;
+    uint32_t s = blockIdx.x / job.cps, c = blockIdx.x - s * job.cps;
+    auto advance = [&] {
+        c += job.gs_c;
+        s += job.gs_s;
+        if (c >= job.cps) {
+            c -= job.cps;
+            ++s;
+        }
+    };
+    while (s < job.nstripes) {
+        // (the id's fields by a fresh look at the arguments, not held across the walk)
+        const KPtr<BsrMixJob> km = kernarg_job<BsrMixJob>();
+        const uint32_t id = __builtin_amdgcn_readfirstlane(((CU32)km->ids)[s]);
+        if (id >= km->npatterns) {
+            advance();
+            continue;
+        }
+        const CU64 ca = (CU64)km->records + static_cast<uint64_t>(id) * km->stride;
+        uint64_t off = static_cast<uint64_t>(c) * kBsrChunk;
+        if (off > sz - kBsrChunk) off = sz - kBsrChunk;
+        const uint64_t ib = s * job.in_sstride + off + lane * 16u;
+        const uint64_t ob = s * job.out_sstride + off + lane * 16u;
+        uint32_t acc[RT][8];  // no zeroing: the wave's first input calls "set" routines (kBsrSetBase)
+        bsr_walk<RT>(acc, k, ib, ca, [&](uint32_t j) { return kj->ptr[j]; });
+        const uint32_t live = __builtin_amdgcn_readfirstlane(((CU32)(ca + k * RT))[0]);  // the mask, after the walk
+#pragma unroll
+        for (int rr = 0; rr < RT; ++rr) {
+            if (static_cast<uint32_t>(rr) < r && ((live >> rr) & 1u)) {  // wave-uniform
+                transpose8(acc[rr]);
+                uint8_t* op = const_cast<uint8_t*>(kj->ptr[k + rr]) + ob;
+                store16_out<true>(op, u32x4{acc[rr][0], acc[rr][1], acc[rr][2], acc[rr][3]});
+                store16_out<true>(op + 1024, u32x4{acc[rr][4], acc[rr][5], acc[rr][6], acc[rr][7]});
+            }
+        }
+        advance();
     }
 }
 
@@ -4253,50 +4356,279 @@ struct RepairKr {
 };
 constexpr KrTable<RepairKr> g_repair_launch;
 
-hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
-    const uint32_t k = p.k, t = p.t;
+// The live rows of all patterns together.
+uint32_t repair_any(const uint32_t* masks, size_t npatterns, uint32_t t) {
     uint32_t any = 0;
-    for (size_t q = 0; q < p.npatterns; ++q) any |= p.masks[q];
-    if (t < 32) any &= (1u << t) - 1u;
-    if (!any) return hipSuccess;  // nothing to store: no upload, no launch
+    for (size_t q = 0; q < npatterns; ++q) any |= masks[q];
+    return t < 32 ? any & ((1u << t) - 1u) : any;
+}
+
+// Build records: npatterns matrepair_mixed records into host memory.
+void repair_fill_records(uint32_t* ht, const uint8_t* rows, const uint32_t* masks, size_t npatterns, uint32_t k,
+                         uint32_t t) {
+    const uint32_t rec_dwords = repair_rec_dwords(k, t), mask_off = t * k * 5;
+    for (size_t q = 0; q < npatterns; ++q) {
+        uint32_t* rec = ht + q * rec_dwords;
+        for (uint32_t i = 0; i < t * k; ++i) host_tab(rec + i * 5, rows[q * t * k + i]);
+        rec[mask_off] = masks[q];
+        for (uint32_t i = mask_off + 1; i < rec_dwords; ++i) rec[i] = 0;
+    }
+}
+
+// Launch over records: the row groups of 8 that some pattern stores (`any`),
+// records and ids in device memory.
+hipError_t launch_repair_groups(const RepairSpec& p, const uint32_t* records, const uint32_t* ids, uint32_t any,
+                                hipStream_t stream) {
+    const uint32_t k = p.k, t = p.t;
     RepairUpload u;
     u.rec_dwords = repair_rec_dwords(k, t);
     u.mask_off = t * k * 5;
-    const size_t tab_bytes = (size_t(p.npatterns) * u.rec_dwords * 4 + 255) / 256 * 256;
-    const size_t ids_bytes = p.ids_host ? size_t(p.nstripes) * 4 : 0;
-    StagedUpload up;
-    hipError_t e = up.acquire(tab_bytes + ids_bytes);
-    if (e != hipSuccess) return e;
-    uint32_t* ht = reinterpret_cast<uint32_t*>(up.host());
-    for (size_t q = 0; q < p.npatterns; ++q) {
-        uint32_t* rec = ht + q * u.rec_dwords;
-        for (uint32_t i = 0; i < t * k; ++i) host_tab(rec + i * 5, p.rows[q * t * k + i]);
-        rec[u.mask_off] = p.masks[q];
-        for (uint32_t i = u.mask_off + 1; i < u.rec_dwords; ++i) rec[i] = 0;
-    }
-    if (ids_bytes) std::memcpy(up.host() + tab_bytes, p.ids_host, ids_bytes);
-    if ((e = up.copy(tab_bytes + ids_bytes, stream)) != hipSuccess) return e;
-    u.records = reinterpret_cast<const uint32_t*>(up.dev());
-    u.ids = p.ids_host ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : p.ids_dev;
+    u.records = records;
+    u.ids = ids;
+    hipError_t e = hipSuccess;
     for (uint32_t g0 = 0; g0 < t && e == hipSuccess; g0 += kRegR) {
         const uint32_t rg = std::min<uint32_t>(kRegR, t - g0);
         if (!((any >> g0) & ((1u << rg) - 1u))) continue;  // rows no pattern stores
         e = g_repair_launch(k, rg)(p, u, g0, stream);
     }
+    return e;
+}
+
+hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
+    const uint32_t k = p.k, t = p.t;
+    const uint32_t any = repair_any(p.masks, p.npatterns, t);
+    if (!any) return hipSuccess;  // nothing to store: no upload, no launch
+    const size_t tab_bytes = (size_t(p.npatterns) * repair_rec_dwords(k, t) * 4 + 255) / 256 * 256;
+    const size_t ids_bytes = p.ids_host ? size_t(p.nstripes) * 4 : 0;
+    StagedUpload up;
+    hipError_t e = up.acquire(tab_bytes + ids_bytes);
+    if (e != hipSuccess) return e;
+    repair_fill_records(reinterpret_cast<uint32_t*>(up.host()), p.rows, p.masks, p.npatterns, k, t);
+    if (ids_bytes) std::memcpy(up.host() + tab_bytes, p.ids_host, ids_bytes);
+    if ((e = up.copy(tab_bytes + ids_bytes, stream)) != hipSuccess) return e;
+    e = launch_repair_groups(p, reinterpret_cast<const uint32_t*>(up.dev()),
+                             p.ids_host ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : p.ids_dev, any,
+                             stream);
+    up.done(stream);
+    return e;
+}
+
+// ---- mix form of the run-time-data bit-sliced kernels (4 < k <= 32) ------------------
+// Waves (row tiles) per unit from r alone -- not from the size of the call as
+// bsr_tiles -- so that a record serves every call: one wave for r <= 10, 2 for
+// r <= 20, 4 for r <= 32, tiles of rt = ceil(r / nw) rows.
+void bsr_mix_tiles(uint32_t r, uint32_t* nw, uint32_t* rt) {
+    *nw = r <= static_cast<uint32_t>(kBsrMaxRows) ? 1u : r <= 2u * kBsrMaxRows ? 2u : 4u;
+    *rt = (r + *nw - 1) / *nw;
+}
+
+// uint64 words per record: the addresses, the mask dword, padded to 16 bytes.
+uint32_t bsr_mix_stride(uint32_t k, uint32_t r) {
+    uint32_t nw, rt;
+    bsr_mix_tiles(r, &nw, &rt);
+    return (nw * k * rt + 1 + 1) / 2 * 2;
+}
+
+struct BsrMixVariant {
+    const void* fn_solo = nullptr;
+    const void* fn = nullptr;  // LDS-phase form: RT 6-10 (r = 11..32 on 2 or 4 waves)
+    KName name_solo = "";
+    KName name = "";
+};
+BsrMixVariant g_bsr_mix[kBsrMaxRows + 1];
+std::once_flag g_bsr_mix_once;
+
+void fill_bsr_mix() {
+    for_each_rt<kBsrMaxRows>([](auto rt) {
+        constexpr int RT = decltype(rt)::value;
+        BsrMixVariant& v = g_bsr_mix[RT];
+        v.fn_solo = reinterpret_cast<const void*>(matapply_bsr_mix_solo<RT>);
+        kname(v.name_solo, "matapply_bsr", RT, ",mix");
+        if constexpr (RT >= 6) {
+            v.fn = reinterpret_cast<const void*>(matapply_bsr<RT, true, false, BsrMixJob>);
+            kname(v.name, "matapply_bsr", RT, ",lds,mix");
+        }
+    });
+}
+
+// launch_mixed / launch_repair for 4 < k <= 32: the records of every pattern
+// and any host-side ids through one staging slot, then one launch.  Every way
+// to decline comes before anything is enqueued.
+hipError_t launch_repair_wide(const RepairSpec& p, hipStream_t stream) {
+    if (!repair_any(p.masks, p.npatterns, p.t)) return hipSuccess;  // nothing to store: no upload, no launch
+    const size_t rec = bsr_mix_record_bytes(p.k, p.t);
+    if (!bsr_mix_ok(p.k, p.t, p.sz) || rec * p.npatterns > kBsrMixMaxBytes) return hipErrorNotSupported;
+    const uint64_t cps = (p.sz + kBsrChunk - 1) / kBsrChunk;
+    if (cps >= (1ull << 32) || p.nstripes >= (1ull << 32) || cps * p.nstripes >= (1ull << 32) - (1ull << 24))
+        return hipErrorNotSupported;
+    uint64_t base = 0;
+    if (bsr_routine_base(&base, stream) != hipSuccess) return hipErrorNotSupported;
+    const size_t tab_bytes = (rec * p.npatterns + 255) / 256 * 256;
+    const size_t ids_bytes = p.ids_host ? size_t(p.nstripes) * 4 : 0;
+    StagedUpload up;
+    hipError_t e = up.acquire(tab_bytes + ids_bytes);
+    if (e != hipSuccess) return e;
+    if (!bsr_mix_fill_records(up.host(), p.rows, p.masks, p.npatterns, p.k, p.t, base)) return hipErrorInvalidValue;
+    if (ids_bytes) std::memcpy(up.host() + tab_bytes, p.ids_host, ids_bytes);
+    if ((e = up.copy(tab_bytes + ids_bytes, stream)) != hipSuccess) return e;
+    BsrMixSpec m;
+    m.k = p.k;
+    m.r = p.t;
+    m.npatterns = p.npatterns;
+    m.records = up.dev();
+    m.ids = p.ids_host ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : p.ids_dev;
+    m.in = p.in;
+    m.out = p.out;
+    m.sz = p.sz;
+    m.nstripes = p.nstripes;
+    m.in_sstride = p.in_sstride;
+    m.out_sstride = p.out_sstride;
+    e = launch_bsr_mixed(m, stream);
     up.done(stream);
     return e;
 }
 
 }  // namespace
 
+bool bsr_mix_ok(uint32_t k, uint32_t r, uint64_t sz) {
+    return generic_mode() == 2 && k > kMixedMaxK && k <= static_cast<uint32_t>(kMaxIn) && r >= 1 &&
+           r <= kRepairMaxRows && sz >= kBsrChunk;
+}
+
+size_t bsr_mix_record_bytes(uint32_t k, uint32_t r) { return size_t(bsr_mix_stride(k, r)) * 8; }
+
+bool bsr_mix_fill_records(void* dst, const uint8_t* rows, const uint32_t* masks, size_t npatterns, uint32_t k,
+                          uint32_t r, uint64_t base) {
+    uint32_t nw, rt;
+    bsr_mix_tiles(r, &nw, &rt);
+    const uint32_t stride = bsr_mix_stride(k, r), naddr = nw * k * rt;
+    const uint32_t all = r < 32 ? (1u << r) - 1u : ~0u;
+    ApplySpec a{};
+    a.k = k;
+    a.r = r;
+    a.coef_stride = k;
+    for (size_t q = 0; q < npatterns; ++q) {
+        uint64_t* rec = static_cast<uint64_t*>(dst) + q * stride;
+        a.coef = rows + q * r * k;
+        if (!fill_bsr_addrs(rec, a, base, 1, nw, rt, 1)) return false;
+        for (uint32_t i = naddr; i < stride; ++i) rec[i] = 0;
+        rec[naddr] = (masks ? masks[q] : all) & all;  // the mask is the low dword
+    }
+    return true;
+}
+
+hipError_t launch_bsr_mixed(const BsrMixSpec& m, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    std::call_once(g_bsr_mix_once, fill_bsr_mix);
+    if (!m.records || !m.ids || m.npatterns < 1 || m.nstripes == 0 || m.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (!bsr_mix_ok(m.k, m.r, m.sz)) return hipErrorNotSupported;
+    uint64_t base = 0;
+    if (bsr_routine_base(&base, stream) != hipSuccess) return hipErrorNotSupported;
+    const uint64_t cps = (m.sz + kBsrChunk - 1) / kBsrChunk;
+    const uint64_t units = cps * m.nstripes;
+    if (units >= (1ull << 32) - (1ull << 24)) return hipErrorNotSupported;
+    uint32_t nw, rt;
+    bsr_mix_tiles(m.r, &nw, &rt);
+    const BsrMixVariant& v = g_bsr_mix[rt];
+    if (nw > 1 && !v.fn) return hipErrorNotSupported;
+    reset_signal();
+    BsrMixJob job;
+    job.sz = m.sz;
+    job.in_sstride = m.in_sstride;
+    job.out_sstride = m.out_sstride;
+    job.nstripes = static_cast<uint32_t>(m.nstripes);
+    job.k = m.k;
+    job.r = m.r;
+    const uint32_t grid = fill_stride(job, cps, units, bsr_grid_cap());
+    job.npatterns = m.npatterns;
+    job.stride = bsr_mix_stride(m.k, m.r);
+    job.ids = m.ids;
+    job.records = static_cast<const uint64_t*>(m.records);
+    for (uint32_t j = 0; j < m.k; ++j) job.ptr[j] = m.in[j];
+    for (uint32_t i = 0; i < m.r; ++i) job.ptr[m.k + i] = m.out[i];
+    const hipError_t e = nw == 1 ? launch_job(v.fn_solo, grid, 64, 0, stream, job)
+                                 : launch_job(v.fn, grid, 64 * nw, bsr_lds_bytes(m.k, nw, false), stream, job);
+    if (e == hipSuccess) t_last_kernel = nw == 1 ? v.name_solo : v.name;
+    return e;
+}
+
+size_t repair_records_bytes(uint32_t k, uint32_t t, size_t npatterns) {
+    if (k < 1 || k > static_cast<uint32_t>(kMaxIn) || t < 1 || t > kRepairMaxRows) return 0;
+    return npatterns * (k <= kMixedMaxK ? size_t(repair_rec_dwords(k, t)) * 4 : bsr_mix_record_bytes(k, t));
+}
+
+hipError_t repair_records_fill(void* dst, const uint8_t* rows, const uint32_t* masks, size_t npatterns, uint32_t k,
+                               uint32_t t) {
+    if (!repair_records_bytes(k, t, npatterns)) return hipErrorNotSupported;
+    if (k <= kMixedMaxK) {
+        repair_fill_records(static_cast<uint32_t*>(dst), rows, masks, npatterns, k, t);
+        return hipSuccess;
+    }
+    uint64_t base = 0;
+    if (bsr_routine_base(&base, nullptr) != hipSuccess) return hipErrorNotSupported;
+    return bsr_mix_fill_records(dst, rows, masks, npatterns, k, t, base) ? hipSuccess : hipErrorInvalidValue;
+}
+
+hipError_t launch_repair_records(const RepairSpec& p, const void* records, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (p.k < 1 || p.k > static_cast<uint32_t>(kMaxIn) || p.t < 1 || p.t > kRepairMaxRows || p.npatterns < 1 ||
+        !p.masks || !records || (!p.ids_host && !p.ids_dev) || p.sz == 0 || p.nstripes == 0 ||
+        p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    const uint32_t any = repair_any(p.masks, p.npatterns, p.t);
+    if (!any) return hipSuccess;  // nothing to store: no launch
+    const bool wide = p.k > kMixedMaxK;
+    if (wide) {  // every way to decline, before anything is enqueued
+        const uint64_t cps = (p.sz + kBsrChunk - 1) / kBsrChunk;
+        uint64_t base = 0;
+        if (!bsr_mix_ok(p.k, p.t, p.sz) || cps >= (1ull << 32) ||
+            cps * p.nstripes >= (1ull << 32) - (1ull << 24) || bsr_routine_base(&base, stream) != hipSuccess)
+            return hipErrorNotSupported;
+    }
+    const uint32_t* ids = p.ids_dev;
+    StagedUpload up;
+    if (p.ids_host) {  // the ids alone through a staging slot
+        if (stream_capturing(stream)) return hipErrorNotSupported;
+        const size_t ids_bytes = size_t(p.nstripes) * 4;
+        hipError_t e = up.acquire(ids_bytes);
+        if (e != hipSuccess) return e;
+        std::memcpy(up.host(), p.ids_host, ids_bytes);
+        if ((e = up.copy(ids_bytes, stream)) != hipSuccess) return e;
+        ids = reinterpret_cast<const uint32_t*>(up.dev());
+    }
+    reset_signal();
+    hipError_t e;
+    if (wide) {
+        BsrMixSpec m;
+        m.k = p.k;
+        m.r = p.t;
+        m.npatterns = p.npatterns;
+        m.records = records;
+        m.ids = ids;
+        m.in = p.in;
+        m.out = p.out;
+        m.sz = p.sz;
+        m.nstripes = p.nstripes;
+        m.in_sstride = p.in_sstride;
+        m.out_sstride = p.out_sstride;
+        e = launch_bsr_mixed(m, stream);
+    } else {
+        e = launch_repair_groups(p, static_cast<const uint32_t*>(records), ids, any, stream);
+    }
+    if (p.ids_host) up.done(stream);
+    return e;
+}
+
 hipError_t launch_repair(const RepairSpec& p, hipStream_t stream) {
     std::call_once(g_dispatch_once, init_dispatch);
-    if (p.k < 1 || p.k > kMixedMaxK || p.t < 1 || p.t > kRepairMaxRows || p.npatterns < 1 ||
+    if (p.k < 1 || p.k > static_cast<uint32_t>(kMaxIn) || p.t < 1 || p.t > kRepairMaxRows || p.npatterns < 1 ||
         p.npatterns > kMixedMaxPatterns || !p.rows || !p.masks || (!p.ids_host && !p.ids_dev) || p.sz == 0 ||
         p.nstripes == 0 || p.nstripes >= (1ull << 32))
         return hipErrorInvalidValue;
     if (stream_capturing(stream)) return hipErrorNotSupported;
     reset_signal();
+    if (p.k > kMixedMaxK) return launch_repair_wide(p, stream);
     return launch_repair_all(p, stream);
 }
 
@@ -4472,11 +4804,28 @@ hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream) {
 
 hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream) {
     std::call_once(g_dispatch_once, init_dispatch);
-    if (m.k < 1 || m.k > kMixedMaxK || m.npatterns < 1 || m.npatterns > kMixedMaxPatterns || !m.rows ||
-        (!m.ids_host && !m.ids_dev) || m.sz == 0 || m.nstripes == 0)
+    if (m.k < 1 || m.k > static_cast<uint32_t>(kMaxIn) || m.npatterns < 1 || m.npatterns > kMixedMaxPatterns ||
+        !m.rows || (!m.ids_host && !m.ids_dev) || m.sz == 0 || m.nstripes == 0)
         return hipErrorInvalidValue;
     if (stream_capturing(stream)) return hipErrorNotSupported;
     reset_signal();
+    if (m.k > kMixedMaxK) {  // a decode is a repair of the k primaries, every row live
+        const std::vector<uint32_t> masks(m.npatterns, ~0u);
+        RepairSpec p;
+        p.k = p.t = m.k;
+        p.rows = m.rows;
+        p.masks = masks.data();
+        p.npatterns = m.npatterns;
+        p.ids_host = m.ids_host;
+        p.ids_dev = m.ids_dev;
+        p.in = m.in;
+        p.out = m.out;
+        p.sz = m.sz;
+        p.nstripes = m.nstripes;
+        p.in_sstride = m.in_sstride;
+        p.out_sstride = m.out_sstride;
+        return launch_repair_wide(p, stream);
+    }
     switch (m.k) {
     case 1: return launch_mixed_k<1>(m, stream);
     case 2: return launch_mixed_k<2>(m, stream);

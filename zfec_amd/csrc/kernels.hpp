@@ -112,6 +112,61 @@ struct RepairSpec {
 };
 hipError_t launch_repair(const RepairSpec& p, hipStream_t stream);
 
+// The same two calls for wider codes (4 < k <= kMaxIn, sz >= 2048,
+// generic_mode() == 2): launch_mixed and launch_repair build one record per
+// pattern (below) into the same staging slot and make ONE launch of the mix
+// form of the run-time-data bit-sliced kernels -- matapply_bsr<RT,mix> (r <= 10,
+// one wave per 2 KiB unit) or matapply_bsr<RT,lds,mix> (2 waves for r <= 20, 4
+// for r <= 32, a tile of RT = ceil(r / waves) rows each).  They return
+// hipErrorNotSupported, with nothing enqueued, where that launch declines
+// (bsr_mix_ok false, no routine table on the device, records past
+// kBsrMixMaxBytes, 2^32 - 2^24 units): the caller takes its run path.
+//
+// A pattern's record: the routine addresses of its r x k matrix in the
+// kernels' walk order [wave][input][RT] (the first input's are the "set"
+// twins, rows past a wave's tile routine 0), then one dword live-row mask,
+// padded to 16 bytes.  The layout depends on (k, r) alone, so records built
+// once serve any later call.  launch_bsr_mixed launches over records and ids
+// already in device memory; it touches nothing the library owns, so it may be
+// captured into a graph once the routine-table probe has run on the device
+// (it synchronises a stream of its own, so it does not run under capture;
+// repair_records_fill below runs it).
+constexpr size_t kBsrMixMaxBytes = size_t(32) << 20;  // records of one call or plan (10^4 K=20 decode patterns)
+bool bsr_mix_ok(uint32_t k, uint32_t r, uint64_t sz);
+size_t bsr_mix_record_bytes(uint32_t k, uint32_t r);
+// npatterns records into dst (host memory) from rows (npatterns x r x k
+// coefficients) and masks (npatterns; null: every row live); base: the routine
+// table's address on the device
+bool bsr_mix_fill_records(void* dst, const uint8_t* rows, const uint32_t* masks, size_t npatterns, uint32_t k,
+                          uint32_t r, uint64_t base);
+struct BsrMixSpec {
+    uint32_t k, r;
+    uint32_t npatterns;
+    const void* records;       // device: npatterns x bsr_mix_record_bytes(k, r)
+    const uint32_t* ids;       // device: nstripes pattern ids
+    const uint8_t* const* in;  // k input block bases (stripe 0), device memory
+    uint8_t* const* out;       // r output row bases (stripe 0)
+    uint64_t sz, nstripes;
+    uint64_t in_sstride, out_sstride;
+};
+hipError_t launch_bsr_mixed(const BsrMixSpec& m, hipStream_t stream);
+
+// Records built once and launched over many times (fec_repair_plan_new,
+// fec_repair_batch_planned).  repair_records_bytes: the bytes of npatterns
+// records of a (k, t) repair -- matrepair_mixed's layout for k <= 4, the mix
+// form's for 4 < k <= kMaxIn; 0 for other shapes.  repair_records_fill writes
+// them into host memory (hipErrorNotSupported where the current device has no
+// routine table; not under capture).  launch_repair_records launches over such
+// records in device memory: `p` as for launch_repair with rows ignored and
+// masks the patterns' live-row masks (host memory).  With ids in device memory
+// it stages nothing, so it may be captured into a graph; host-side ids go
+// through a staging slot (hipErrorNotSupported under capture).  It also returns
+// hipErrorNotSupported, with nothing enqueued, where launch_bsr_mixed declines.
+size_t repair_records_bytes(uint32_t k, uint32_t t, size_t npatterns);
+hipError_t repair_records_fill(void* dst, const uint8_t* rows, const uint32_t* masks, size_t npatterns, uint32_t k,
+                               uint32_t t);
+hipError_t launch_repair_records(const RepairSpec& p, const void* records, hipStream_t stream);
+
 // Parity verification (fec_verify_batch): nothing is written but mismatch bits.
 // Bit (bit0 + i) % 32 of mismatch[s * words + (bit0 + i) / 32] is OR-ed in
 // (relaxed, device scope) when row i of stripe s differs in at least one byte;
