@@ -399,6 +399,107 @@ int fec_correct_batch(const fec_t* code,
  * rows[nb*k].  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
 int fec_correct_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
 
+/* Two corrupt blocks per stripe: fec_locate2_batch names them, and
+ * fec_correct2_batch heals them in place.  The arguments are those of
+ * fec_locate_batch / fec_correct_batch, except that culprit holds TWO words
+ * per stripe in planar layout: culprit[s] is the first word of stripe s and
+ * culprit[nstripes + s] the second, 2 * nstripes words in all.
+ *
+ * Let p_h be column h of the c x nb matrix [P | I]: P's column for a basis
+ * slot, a unit column for a check slot, so that the syndrome vector at a byte
+ * is s = sum_h e_h . p_h over the slots' error bytes e_h.
+ *   Rules 1-4 of fec_locate_batch are unchanged: they give CLEAN, UNKNOWN or a
+ *     single slot h as the first word; the second word is FEC_LOCATE_NONE.
+ *   Rule 5 applies where fec_locate_batch says MANY, when c >= 4 and nb <= 32.
+ *     The pair hypothesis (a, b), a < b < nb, "only slots a and b are corrupt"
+ *     is refuted iff at some byte s is not in span(p_a, p_b).  If exactly one
+ *     pair is not refuted the verdict is (a, b); otherwise it is
+ *     (FEC_LOCATE_MANY, FEC_LOCATE_NONE).
+ *   With c < 4 or nb > 32 the pair pass does not run: the first word is
+ *     exactly fec_locate_batch's verdict, the second is FEC_LOCATE_NONE, and no
+ *     error is returned.
+ * Where a pair needs an index it is p = a*nb - a(a+1)/2 + (b - a - 1)
+ * (lexicographic order).
+ *
+ * What this guarantees.  Any c columns of [P | I] are independent (the held
+ * blocks form an MDS code); four columns need c >= 4.
+ *   - A stripe with exactly two corrupt blocks a, b gets (a, b), whether they
+ *     differ at the same bytes or at different ones: every s lies in
+ *     span(p_a, p_b), so (a, b) is never refuted.  Another pair (a', b')
+ *     survives only if every s lies in span(p_a', p_b') too; the two spans
+ *     meet in 0 when the pairs are disjoint and in one column's line when
+ *     they share a slot (else three or four columns were dependent), so all
+ *     the errors would sit in at most one block -- which rules 3 and 4 catch.
+ *   - At most one pair survives under rule 5, by the same argument: two
+ *     surviving pairs put every s on one column's line, a single-block
+ *     stripe, and those never reach rule 5.
+ *   - A stripe with one corrupt block gets that slot by rules 3-4.
+ *   - Three to c - 2 blocks corrupt at one byte give MANY (this needs c >= 5):
+ *     s is a combination of t <= c - 2 columns with nonzero weights, and were
+ *     it in some span(p_a, p_b), at most t + 2 <= c columns were dependent.
+ *   - From c - 1 blocks corrupt at one byte on, a wrong pair is possible, as
+ *     with any decoder past its distance.  With c = 4 that is already three
+ *     blocks: pass c >= 5 to have triple errors refused.
+ *
+ * fec_correct2_batch: verdicts are exactly fec_locate2_batch's for the blocks
+ * as they were on entry.  A single-slot verdict is healed exactly as
+ * fec_correct_batch heals it.  For a pair verdict (a, b) the sz bytes of slots
+ * a and b are rewritten: the sources S_ab are the k lowest-numbered slots not
+ * in {a, b}, ascending, and the rows are fec_repair_rows(present =
+ * block_nums[S_ab], targets = {block_nums[a], block_nums[b]})
+ * (fec_correct2_rows).  Nothing else in caller memory is written (the list of
+ * fec_correct_batch's rule 3).  Every stripe that gets a slot or pair verdict
+ * passes fec_verify_batch afterwards, whatever the corruption was: a surviving
+ * pair means some codeword differs from the stored blocks only in a and b, and
+ * rebuilding a and b from any k other blocks yields it.
+ *
+ * Memory, streams, flags, capture (FEC_EINVAL under capture) and the order of
+ * validation are fec_locate_batch's, the messages naming the new calls.
+ * culprit is device memory used in place (FEC_FLAG_ASYNC honoured) or host
+ * memory gathered in device words the library owns and copied back.  sz == 0
+ * gives (CLEAN, NONE) everywhere.  Page-locked host blocks are read, and by
+ * fec_correct2_batch written, in place with plain vector stores; every atomic
+ * aims at device memory the library owns.
+ *
+ * The location path of fec_locate_batch runs unchanged, so clean data pays
+ * what it pays there plus the second plane's stores and the launches below
+ * over an empty list.  locate2_finish writes both planes and appends every
+ * MANY stripe to a dirty list in device memory; (fec_correct2_batch: the
+ * single-slot correction of fec_correct_batch runs here;) pairs_locate walks
+ * the list, forms the c syndromes of each unit and ORs refuted pair bits into
+ * the entry's words; pairs_finish names the one surviving pair; pairs_correct
+ * rewrites it.  fec_last_kernel_name() is pairs_locate after
+ * fec_locate2_batch and pairs_correct after fec_correct2_batch where the pair
+ * pass runs (sz != 0, c >= 4, nb <= 32), else what the single-block call
+ * reports. */
+#define FEC_LOCATE_NONE    0xFFFFFFFCu
+int fec_locate2_batch(const fec_t* code,
+                      const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                      const unsigned* block_nums, size_t num_block_nums,
+                      size_t sz, size_t nstripes,
+                      unsigned* culprit, void* stream, unsigned flags);
+int fec_correct2_batch(const fec_t* code,
+                       gf* blocks, size_t block_stride, size_t stripe_stride,
+                       const unsigned* block_nums, size_t num_block_nums,
+                       size_t sz, size_t nstripes,
+                       unsigned* culprit, void* stream, unsigned flags);
+
+/* Host only, no GPU: a (c-2) x c matrix N of rank c - 2 with N . p_a =
+ * N . p_b = 0, row-major into rows[(c-2)*c]: s lies in span(p_a, p_b) iff
+ * N . s = 0.  The pivot form is written: two rows r0, r1 on which [p_a p_b]
+ * has a nonzero minor, and for every other row i the row e_i + alpha . e_r0 +
+ * beta . e_r1.  FEC_EINVAL for a >= b, b >= nb or c < 4, after
+ * fec_locate_rows' checks.  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
+int fec_locate2_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, unsigned a, unsigned b,
+                     gf* rows);
+
+/* Host only, no GPU: sources[k], the k lowest-numbered slots not in {a, b},
+ * ascending, and rows[2*k], row-major, the coefficients that yield slot a
+ * (row 0) and slot b (row 1) from them.  FEC_EINVAL for a >= b, b >= nb or
+ * c < 2.  FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
+int fec_correct2_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, unsigned a, unsigned b,
+                      unsigned* sources, gf* rows);
+
 /* Batched repair: rebuild any lost blocks of every stripe, primaries and parity
  * alike, from the k blocks the stripe still holds, in one call (the step after
  * fec_verify_batch in a store's scrub-and-repair cycle).

@@ -23,11 +23,14 @@ from ._fec import Error, device_count, test_from_agl, version
 __version__ = "0.1.0"
 
 __all__ = ["Encoder", "Decoder", "RepairPlan", "Error", "easyfec", "filefec", "cmdline_zfec", "cmdline_zunfec", "test_from_agl",
-           "device_count", "version", "reuse_host_memory", "LOCATE_CLEAN", "LOCATE_MANY", "LOCATE_UNKNOWN"]
+           "device_count", "version", "reuse_host_memory", "LOCATE_CLEAN", "LOCATE_MANY", "LOCATE_UNKNOWN",
+           "LOCATE_NONE"]
 
 # Decoder.locate_batch verdicts that are not a slot: FEC_LOCATE_CLEAN / _MANY /
 # _UNKNOWN (include/zfec_hip.h) read as int32
 LOCATE_CLEAN, LOCATE_MANY, LOCATE_UNKNOWN = -1, -2, -3
+# Decoder.locate2_batch: the second word of a verdict that is no pair (FEC_LOCATE_NONE as int32)
+LOCATE_NONE = -4
 
 
 def _is_device_tensor(x):
@@ -841,8 +844,49 @@ class Decoder(_fec.Decoder):
             _capi_code(self).correct_batch(ptr, sbs, sss, nums, sz, ns, out.data_ptr(), stream=stream, flags=flags)
         return out
 
+    def locate2_batch(self, blocks, blocknums):
+        """Name up to two corrupt blocks of every stripe (fec_locate2_batch).
+
+        blocks and blocknums as in locate_batch, with the same preconditions.
+        Returns a torch.int32 tensor [2, nstripes] on the blocks' device.
+        Column s is (a, b), a < b, the SLOTS of the stripe's two corrupt
+        blocks, or (v, LOCATE_NONE) with v what locate_batch returns: a single
+        slot, LOCATE_CLEAN, LOCATE_UNKNOWN or LOCATE_MANY.  Pairs are looked
+        for with nb - k >= 4 checks and nb <= 32 blocks per stripe; other
+        shapes get locate_batch's verdicts.  With four or more checks a stripe
+        with exactly two corrupt blocks always gets that pair; pass nb >= k + 5
+        to have triple errors refused (LOCATE_MANY).  The work is enqueued on
+        the current stream, without a host sync."""
+        return self._scrub2(blocks, blocknums, "locate2_batch")
+
+    def correct2_batch(self, blocks, blocknums):
+        """Scrub, locate and heal up to two blocks per stripe in place, in one
+        call (fec_correct2_batch).
+
+        Returns the torch.int32 verdicts [2, nstripes] locate2_batch would
+        return for the blocks as they were on entry, and CORRECTS `blocks` IN
+        PLACE: a single slot exactly as correct_batch does, and for a pair
+        (a, b) the sz bytes of slots a and b, from the k lowest other slots of
+        the stripe.  Nothing else is written.  Every corrected stripe is
+        consistent afterwards (verify_batch returns no bit for it)."""
+        return self._scrub2(blocks, blocknums, "correct2_batch")
+
+    def _scrub2(self, blocks, blocknums, what):
+        import torch
+
+        nums, nb, ns, sz, sbs, sss, ptr = self._scrub_args(blocks, blocknums, what)
+        out = torch.empty((2, ns), dtype=torch.int32, device=blocks.device)
+        if not (ns and sz):
+            out[0] = LOCATE_CLEAN
+            out[1] = LOCATE_NONE
+            return out
+        stream, flags = _batch_call_args(blocks)
+        with _as_error():
+            getattr(_capi_code(self), what)(ptr, sbs, sss, nums, sz, ns, out.data_ptr(), stream=stream, flags=flags)
+        return out
+
     def _scrub_args(self, blocks, blocknums, what):
-        """The preconditions verify_batch, locate_batch and correct_batch share; returns
+        """The preconditions the scrub calls (verify_batch to correct2_batch) share; returns
         (nums, nb, nstripes, sz, block stride, stripe stride, address)."""
         import torch
 

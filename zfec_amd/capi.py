@@ -67,11 +67,16 @@ SYMBOLS = [
     ("fec_locate_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
     ("fec_correct_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
     ("fec_correct_rows", ctypes.c_int, [_P, _UP, _SZ, _P]),
+    ("fec_locate2_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
+    ("fec_locate2_rows", ctypes.c_int, [_P, _UP, _SZ, _U, _U, _P]),
+    ("fec_correct2_batch", ctypes.c_int, [_P, _P, _SZ, _SZ, _UP, _SZ, _SZ, _SZ, _P, _P, _U]),
+    ("fec_correct2_rows", ctypes.c_int, [_P, _UP, _SZ, _U, _U, _UP, _P]),
     ("fec_repair_plan_new", ctypes.c_int, [_P, _UP, _UP, _SZ, _SZ, ctypes.c_int, _PP]),
     ("fec_repair_plan_free", None, [_P]),
     ("fec_repair_batch_planned", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _U]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
+FEC_LOCATE_NONE = 0xFFFFFFFC  # fec_locate2_batch: the second word of a verdict that is no pair
 FEC_REPAIR_NONE = 0xFFFFFFFF  # a target slot its pattern does not use
 
 JIT_OFF, JIT_AUTO, JIT_FORCE = 0, 1, 2
@@ -341,6 +346,25 @@ class Code(object):
         if st:
             check(st)
 
+    def locate2_batch(self, src, sbs, sss, block_nums, sz, nstripes, culprit_ptr, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_locate2_batch: the arguments of locate_batch; `culprit_ptr` is
+        the address of 2 * nstripes uint32 words in device or host memory, two
+        planes: word s and word nstripes + s are stripe s's verdict, a pair of
+        slots (a, b) or locate_batch's verdict and FEC_LOCATE_NONE."""
+        st = lib().fec_locate2_batch(self.ptr, src, sbs, sss, _nums(block_nums), len(block_nums), sz, nstripes,
+                                     culprit_ptr or None, stream or None, flags)
+        if st:
+            check(st)
+
+    def correct2_batch(self, blocks, bs, ss, block_nums, sz, nstripes, culprit_ptr, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_correct2_batch: the arguments of locate2_batch, `blocks`
+        writable.  The slot or the two slots a verdict names are rewritten in
+        place from k other slots of their stripe."""
+        st = lib().fec_correct2_batch(self.ptr, blocks, bs, ss, _nums(block_nums), len(block_nums), sz, nstripes,
+                                      culprit_ptr or None, stream or None, flags)
+        if st:
+            check(st)
+
     def encode_batch_multi(self, src, sbs, sss, dst, dbs, dss, block_nums, sz, nstripes, devices, flags=0):
         """fec_encode_batch_multi: the stripes split over `devices` (host memory)."""
         devs = (ctypes.c_int * max(1, len(devices)))(*devices)
@@ -431,6 +455,29 @@ def correct_rows(code, block_nums):
     rows = (ctypes.c_ubyte * max(1, n))()
     check(lib().fec_correct_rows(code.ptr, uint_array(nums), len(nums), ctypes.cast(rows, _P)))
     return bytes(rows)[:n]
+
+
+def locate2_rows(code, block_nums, a, b):
+    """fec_locate2_rows: the (c-2)*c bytes (row-major, c = len(block_nums) - k)
+    of a matrix N of rank c - 2 that annihilates columns a and b of [P | I]: a
+    syndrome vector lies in their span iff N maps it to zero.  Host only."""
+    nums = list(block_nums)
+    c = len(nums) - code.k
+    n = max(0, (c - 2) * c)
+    rows = (ctypes.c_ubyte * max(1, n))()
+    check(lib().fec_locate2_rows(code.ptr, uint_array(nums), len(nums), a, b, ctypes.cast(rows, _P)))
+    return bytes(rows)[:n]
+
+
+def correct2_rows(code, block_nums, a, b):
+    """fec_correct2_rows: (sources, rows): the k lowest slots outside {a, b}
+    and the 2*k bytes (row-major) that yield slot a (row 0) and slot b (row 1)
+    from them.  Host only."""
+    nums = list(block_nums)
+    sources = (ctypes.c_uint * code.k)()
+    rows = (ctypes.c_ubyte * (2 * code.k))()
+    check(lib().fec_correct2_rows(code.ptr, uint_array(nums), len(nums), a, b, sources, ctypes.cast(rows, _P)))
+    return list(sources), bytes(rows)
 
 
 def repair_rows(code, present, targets):

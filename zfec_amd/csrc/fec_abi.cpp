@@ -1917,6 +1917,102 @@ void correct_rows(const uint8_t* P, unsigned k, unsigned c, uint8_t* R) {
     std::memcpy(R + size_t(k) * k, P, size_t(c) * k);
 }
 
+// Column h of the c x nb matrix [P | I] at row i.
+inline uint8_t column_at(const uint8_t* P, unsigned k, unsigned h, unsigned i) {
+    return h < k ? P[size_t(i) * k + h] : uint8_t(h - k == i);
+}
+
+// The pivot form of a (c-2) x c matrix N of rank c - 2 with N . p_a = N . p_b = 0
+// (fec_locate2_rows), c >= 3: out[0..1] = two rows r0, r1 on which [p_a p_b] has
+// a nonzero minor -- r0 the first row where p_a is nonzero, r1 the first other
+// row that completes one; p_a and p_b are independent, so it exists -- then
+// for every other row i, ascending, (i, alpha, beta) with
+//     p_h[i] = alpha . p_h[r0] + beta . p_h[r1]   for h = a and h = b
+// (a 2 x 2 solve), i.e. row e_i + alpha . e_r0 + beta . e_r1 of N.  O(c) per pair.
+// False (nothing usable written) if no such rows exist, which an MDS code rules out.
+bool pair_pivots(const uint8_t* P, unsigned k, unsigned c, unsigned a, unsigned b, uint8_t* out) {
+    const Field& f = field();
+    unsigned r0 = 0, r1 = 0;
+    while (r0 < c && !column_at(P, k, a, r0)) ++r0;
+    if (r0 == c) return false;
+    const uint8_t a0 = column_at(P, k, a, r0), b0 = column_at(P, k, b, r0);
+    uint8_t a1 = 0, b1 = 0, det = 0;
+    for (; r1 < c; ++r1) {
+        if (r1 == r0) continue;
+        a1 = column_at(P, k, a, r1);
+        b1 = column_at(P, k, b, r1);
+        det = f.mul[a0][b1] ^ f.mul[a1][b0];
+        if (det) break;
+    }
+    if (r1 == c) return false;
+    const uint8_t id = f.inv[det];
+    out[0] = uint8_t(r0);
+    out[1] = uint8_t(r1);
+    out += 2;
+    for (unsigned i = 0; i < c; ++i) {
+        if (i == r0 || i == r1) continue;
+        const uint8_t ai = column_at(P, k, a, i), bi = column_at(P, k, b, i);
+        out[0] = uint8_t(i);
+        out[1] = f.mul[f.mul[b1][ai] ^ f.mul[a1][bi]][id];
+        out[2] = f.mul[f.mul[b0][ai] ^ f.mul[a0][bi]][id];
+        out += 3;
+    }
+    return true;
+}
+
+// fec_correct2_rows, c >= 2: the k lowest slots outside {a, b}, ascending, into
+// sources, and the 2 x k rows that yield slots a and b from them, by solving
+// the first check equations not lost for the lost basis slots (O(k) per pair):
+//   both checks:     the basis; rows P[a-k] and P[b-k];
+//   a basis, b check: check q (the first that is not b) solved for slot a, then
+//                     check b's row with that substituted for slot a;
+//   both basis:       checks 0 and 1 solved for slots a and b (a 2 x 2 solve).
+void pair_correct_rows(const uint8_t* P, unsigned k, unsigned a, unsigned b, uint32_t* sources, uint8_t* rows) {
+    const Field& f = field();
+    uint8_t* const ra = rows;
+    uint8_t* const rb = rows + k;
+    if (a >= k) {
+        for (unsigned l = 0; l < k; ++l) sources[l] = l;
+        std::memcpy(ra, P + size_t(a - k) * k, k);
+        std::memcpy(rb, P + size_t(b - k) * k, k);
+        return;
+    }
+    unsigned n = 0;
+    if (b >= k) {
+        const unsigned q = b == k ? 1 : 0;
+        const uint8_t* const pq = P + size_t(q) * k;
+        const uint8_t* const pb = P + size_t(b - k) * k;
+        const uint8_t ia = f.inv[pq[a]];
+        for (unsigned l = 0; l < k; ++l) {
+            if (l == a) continue;
+            sources[n] = l;
+            ra[n] = f.mul[pq[l]][ia];
+            rb[n] = pb[l] ^ f.mul[pb[a]][ra[n]];
+            ++n;
+        }
+        sources[n] = k + q;
+        ra[n] = ia;
+        rb[n] = f.mul[pb[a]][ia];
+        return;
+    }
+    const uint8_t* const p0 = P;
+    const uint8_t* const p1 = P + k;
+    const uint8_t id = f.inv[f.mul[p0[a]][p1[b]] ^ f.mul[p0[b]][p1[a]]];
+    for (unsigned l = 0; l < k; ++l) {
+        if (l == a || l == b) continue;
+        sources[n] = l;
+        ra[n] = f.mul[f.mul[p1[b]][p0[l]] ^ f.mul[p0[b]][p1[l]]][id];
+        rb[n] = f.mul[f.mul[p1[a]][p0[l]] ^ f.mul[p0[a]][p1[l]]][id];
+        ++n;
+    }
+    sources[n] = k;
+    sources[n + 1] = k + 1;
+    ra[n] = f.mul[p1[b]][id];
+    ra[n + 1] = f.mul[p0[b]][id];
+    rb[n] = f.mul[p1[a]][id];
+    rb[n + 1] = f.mul[p0[a]][id];
+}
+
 // The working words of a call (W = ceil(c/32) + ceil(k/32) per stripe, mismatch
 // bits from bit 0, excluded bits from bit 32*ceil(c/32)) live in the thread's
 // vmask buffer, under run_verify's ev_verify ordering; a host-side culprit is
@@ -1927,11 +2023,17 @@ void correct_rows(const uint8_t* P, unsigned k, unsigned c, uint8_t* R) {
 // in device memory: the host never sees them.
 int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const unsigned* nums, size_t nb, size_t sz,
                size_t nstripes, unsigned* culprit, void* stream, unsigned flags, const char* fn = "fec_locate_batch",
-               bool heal = false) {
+               bool heal = false, bool pairs = false) {
     const unsigned k = code->k, c = static_cast<unsigned>(nb - k), cw = (c + 31) / 32, words = cw + (k + 31) / 32;
     const unsigned xbit = 32 * cw;
     if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
-    const size_t work_bytes = nstripes * words * sizeof(uint32_t), out_bytes = nstripes * sizeof(uint32_t);
+    // fec_locate2_batch / fec_correct2_batch: two verdict planes, and where the pair pass runs the dirty
+    // list (its counter first, cleared with the working words) and the entries' pair words behind the bits
+    const bool pass2 = pairs && sz && pairs_shape_ok(k, c);
+    const size_t pw = pass2 ? pairs_words(static_cast<uint32_t>(nb)) : 0;
+    const size_t work_bytes = nstripes * words * sizeof(uint32_t);
+    const size_t out_bytes = nstripes * sizeof(uint32_t) * (pairs ? 2 : 1);
+    const size_t pair_words = pass2 ? 1 + nstripes + nstripes * pw : 0;
     const int cdev = pointer_device(culprit);
     // device memory on one device, or page-locked host memory (read in place); sz == 0 reads no block
     const BatchBuf buf = {src, (nstripes - 1) * sss + (nb - 1) * sbs + sz, heal ? "blocks" : "src"};
@@ -1944,10 +2046,14 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     // the thread's working words (and scratch): wait (on the GPU) for the call that used them last
     VerifyOrder order{*d, st};
     if (order.init() || order.acquire()) return t_status;
-    if (ensure_verify_buf(*d, d->vmask, d->vmask_cap, work_bytes + (cdev < 0 ? out_bytes : 0))) return t_status;
+    if (ensure_verify_buf(*d, d->vmask, d->vmask_cap,
+                          work_bytes + pair_words * sizeof(uint32_t) + (cdev < 0 ? out_bytes : 0)))
+        return t_status;
     uint32_t* const bits = static_cast<uint32_t*>(d->vmask);
-    uint32_t* const out = cdev < 0 ? bits + nstripes * words : culprit;
-    if ((e = hipMemsetAsync(bits, 0, work_bytes, st)) != hipSuccess)
+    uint32_t* const list = pass2 ? bits + nstripes * words : nullptr;
+    uint32_t* const pairbits = pass2 ? list + 1 + nstripes : nullptr;
+    uint32_t* const out = cdev < 0 ? bits + nstripes * words + pair_words : culprit;
+    if ((e = hipMemsetAsync(bits, 0, work_bytes + (pass2 ? sizeof(uint32_t) : 0), st)) != hipSuccess)
         return hip_fail(e, "hipMemsetAsync (working words)");
     int rc = FEC_OK;
     thread_local std::vector<uint8_t> P, Q, R;
@@ -1980,8 +2086,12 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     if (!rc) {
         // the block-reading kernel stays fec_last_kernel_name()'s answer
         ++t_launches;
-        if ((e = launch_locate_finish(bits, words, k, c, nstripes, out, st)) != hipSuccess)
+        if (pairs) {
+            if ((e = launch_locate2_finish(bits, words, k, c, nstripes, out, list, pairbits, st)) != hipSuccess)
+                rc = hip_fail(e, "launch_locate2_finish");
+        } else if ((e = launch_locate_finish(bits, words, k, c, nstripes, out, st)) != hipSuccess) {
             rc = hip_fail(e, "launch_locate_finish");
+        }
     }
     if (!rc && heal && sz) {
         // row h of the nb x k correction matrix rebuilds slot h (zsrc is the caller's writable blocks)
@@ -1999,6 +2109,46 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
         cs.verdict = out;
         ++t_launches;
         if ((e = launch_correct(cs, st)) != hipSuccess) rc = hip_fail(e, "launch_correct");
+    }
+    if (!rc && pass2) {
+        // plane 0 still reads MANY for the listed stripes: the pair pass names (a, b) and, with heal, rewrites them
+        const unsigned npairs = static_cast<unsigned>(nb * (nb - 1) / 2);
+        const size_t pbytes = 2 + 3 * size_t(c - 2);
+        thread_local std::vector<uint8_t> pivots, crows;
+        thread_local std::vector<uint32_t> sources;
+        pivots.resize(npairs * pbytes);
+        if (heal) {
+            sources.resize(size_t(npairs) * k);
+            crows.resize(size_t(npairs) * 2 * k);
+        }
+        unsigned p = 0;
+        for (unsigned a = 0; a + 1 < nb; ++a)
+            for (unsigned b = a + 1; b < nb && !rc; ++b, ++p) {
+                if (!pair_pivots(P.data(), k, c, a, b, pivots.data() + p * pbytes))
+                    rc = set_status(FEC_ESINGULAR, "%s: slots %u and %u have dependent check columns", fn, a, b);
+                else if (heal)
+                    pair_correct_rows(P.data(), k, a, b, sources.data() + size_t(p) * k,
+                                      crows.data() + size_t(p) * 2 * k);
+            }
+        PairsSpec ps;
+        ps.k = k;
+        ps.c = c;
+        ps.P = P.data();
+        ps.pivots = pivots.data();
+        ps.sources = heal ? sources.data() : nullptr;
+        ps.crows = heal ? crows.data() : nullptr;
+        ps.blocks = const_cast<uint8_t*>(zsrc);
+        ps.bstride = sbs;
+        ps.sstride = sss;
+        ps.sz = sz;
+        ps.nstripes = nstripes;
+        ps.list = list;
+        ps.pairbits = pairbits;
+        ps.culprit = out;
+        if (!rc) {
+            t_launches += heal ? 3 : 2;
+            if ((e = launch_pairs(ps, st)) != hipSuccess) rc = hip_fail(e, "launch_pairs");
+        }
     }
     if (!rc && cdev < 0 && (e = hipMemcpyAsync(culprit, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
         rc = hip_fail(e, "hipMemcpyAsync D2H (culprit)");
@@ -2054,6 +2204,81 @@ FEC_API int fec_correct_batch(const fec_t* code, gf* blocks, size_t block_stride
     return guarded([&] {
         return run_locate(code, blocks, block_stride, stripe_stride, block_nums, num_block_nums, sz, nstripes, culprit,
                           stream, flags, "fec_correct_batch", true);
+    });
+}
+
+// ---- two corrupt blocks per stripe ---------------------------------------------------------
+namespace {
+// The checks of fec_locate2_rows / fec_correct2_rows after the block numbers': the pair, then the checks it needs.
+int check_pair(size_t nb, unsigned k, unsigned a, unsigned b, unsigned cmin, const char* fn) {
+    if (a >= b || b >= nb)
+        return set_status(FEC_EINVAL, "%s: (a, b) = (%u, %u) is no pair of slots a < b < %zu", fn, a, b, nb);
+    if (nb - k < cmin)
+        return set_status(FEC_EINVAL, "%s: %zu checks per stripe, a pair needs at least %u", fn, nb - k, cmin);
+    return FEC_OK;
+}
+}  // namespace
+
+FEC_API int fec_locate2_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, unsigned a,
+                             unsigned b, gf* rows) {
+    if (check_verify_call(code, nullptr, nullptr, block_nums, num_block_nums, rows, "rows")) return t_status;
+    if (check_pair(num_block_nums, code->k, a, b, 4, "fec_locate2_rows")) return t_status;
+    return guarded([&] {
+        const unsigned k = code->k, c = static_cast<unsigned>(num_block_nums - k);
+        thread_local std::vector<uint8_t> P, piv;
+        P.resize(size_t(c) * k);
+        piv.resize(2 + 3 * size_t(c - 2));
+        if (verify_rows(code, block_nums, num_block_nums, P.data())) return t_status;
+        if (!pair_pivots(P.data(), k, c, a, b, piv.data()))
+            return set_status(FEC_ESINGULAR, "fec_locate2_rows: slots %u and %u have dependent check columns", a, b);
+        std::memset(rows, 0, size_t(c - 2) * c);
+        for (unsigned m = 0; m + 2 < c; ++m) {
+            gf* const row = rows + size_t(m) * c;
+            row[piv[2 + 3 * m]] = 1;
+            row[piv[0]] = piv[2 + 3 * m + 1];
+            row[piv[1]] = piv[2 + 3 * m + 2];
+        }
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API int fec_correct2_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, unsigned a,
+                              unsigned b, unsigned* sources, gf* rows) {
+    if (check_verify_call(code, nullptr, nullptr, block_nums, num_block_nums, rows, "rows")) return t_status;
+    if (!sources) return set_status(FEC_EINVAL, "sources is NULL");
+    if (check_pair(num_block_nums, code->k, a, b, 2, "fec_correct2_rows")) return t_status;
+    return guarded([&] {
+        const unsigned k = code->k, c = static_cast<unsigned>(num_block_nums - k);
+        thread_local std::vector<uint8_t> P;
+        P.resize(size_t(c) * k);
+        if (verify_rows(code, block_nums, num_block_nums, P.data())) return t_status;
+        static_assert(sizeof(unsigned) == sizeof(uint32_t), "source slots are 32-bit words");
+        pair_correct_rows(P.data(), k, a, b, reinterpret_cast<uint32_t*>(sources), rows);
+        return set_status(FEC_OK);
+    });
+}
+
+FEC_API int fec_locate2_batch(const fec_t* code, const gf* src, size_t src_block_stride, size_t src_stripe_stride,
+                              const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
+                              unsigned* culprit, void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    if (check_verify_call(code, src, "src", block_nums, num_block_nums, culprit, "culprit")) return t_status;
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_locate(code, src, src_block_stride, src_stripe_stride, block_nums, num_block_nums, sz, nstripes,
+                          culprit, stream, flags, "fec_locate2_batch", false, true);
+    });
+}
+
+FEC_API int fec_correct2_batch(const fec_t* code, gf* blocks, size_t block_stride, size_t stripe_stride,
+                               const unsigned* block_nums, size_t num_block_nums, size_t sz, size_t nstripes,
+                               unsigned* culprit, void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    if (check_verify_call(code, blocks, "blocks", block_nums, num_block_nums, culprit, "culprit")) return t_status;
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_locate(code, blocks, block_stride, stripe_stride, block_nums, num_block_nums, sz, nstripes, culprit,
+                          stream, flags, "fec_correct2_batch", true, true);
     });
 }
 

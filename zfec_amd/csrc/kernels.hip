@@ -31,6 +31,10 @@
 //                       explains them (fec_locate_batch); rows_locate does the
 //                       same past k = 4 or 8 checks, locate_finish turns each
 //                       stripe's bits into its verdict.
+//   pairs_locate        over the stripes locate2_finish listed as MANY: the c
+//                       syndromes in LDS, every pair of slots tested against
+//                       them (fec_locate2_batch); pairs_finish names the one
+//                       pair left, pairs_correct rewrites it (fec_correct2_batch).
 //   matrepair_mixed<K, R> matapply_mixed with R rows per pattern instead of K, each
 //                       row stored only where its pattern's live-row mask says
 //                       so (fec_repair_batch).
@@ -1403,34 +1407,31 @@ struct alignas(16) FinishJob {
 
 __device__ __forceinline__ uint32_t low_bits(uint32_t n) { return n >= 32u ? 0xFFFFFFFFu : (1u << n) - 1u; }
 
-__global__ __launch_bounds__(kBlock) void locate_finish(const FinishJob job) {
-    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
-    if (s >= job.nstripes) return;
-    const uint32_t* const w = job.bits + size_t(s) * job.words;
-    const uint32_t cw = (job.c + 31u) / 32u, kw = (job.k + 31u) / 32u;
+// The verdict of one stripe's working words `w` (rules 1-5).
+__device__ __forceinline__ uint32_t finish_verdict(const uint32_t* w, uint32_t k, uint32_t c) {
+    const uint32_t cw = (c + 31u) / 32u, kw = (k + 31u) / 32u;
     uint32_t nbad = 0, first = 0;
     for (uint32_t i = 0; i < cw; ++i) {
-        const uint32_t v = w[i] & low_bits(job.c - 32u * i);
+        const uint32_t v = w[i] & low_bits(c - 32u * i);
         if (v != 0u && nbad == 0u) first = 32u * i + static_cast<uint32_t>(__builtin_ctz(v));
         nbad += static_cast<uint32_t>(__builtin_popcount(v));
     }
-    uint32_t verdict;
-    if (nbad == 0u) {
-        verdict = kLocateClean;
-    } else if (job.c == 1u) {
-        verdict = kLocateUnknown;
-    } else if (nbad == 1u) {
-        verdict = job.k + first;
-    } else {
-        uint32_t nleft = 0, slot = 0;
-        for (uint32_t i = 0; i < kw; ++i) {
-            const uint32_t v = ~w[cw + i] & low_bits(job.k - 32u * i);
-            if (v != 0u && nleft == 0u) slot = 32u * i + static_cast<uint32_t>(__builtin_ctz(v));
-            nleft += static_cast<uint32_t>(__builtin_popcount(v));
-        }
-        verdict = nleft == 1u ? slot : kLocateMany;
+    if (nbad == 0u) return kLocateClean;
+    if (c == 1u) return kLocateUnknown;
+    if (nbad == 1u) return k + first;
+    uint32_t nleft = 0, slot = 0;
+    for (uint32_t i = 0; i < kw; ++i) {
+        const uint32_t v = ~w[cw + i] & low_bits(k - 32u * i);
+        if (v != 0u && nleft == 0u) slot = 32u * i + static_cast<uint32_t>(__builtin_ctz(v));
+        nleft += static_cast<uint32_t>(__builtin_popcount(v));
     }
-    job.culprit[s] = verdict;
+    return nleft == 1u ? slot : kLocateMany;
+}
+
+__global__ __launch_bounds__(kBlock) void locate_finish(const FinishJob job) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= job.nstripes) return;
+    job.culprit[s] = finish_verdict(job.bits + size_t(s) * job.words, job.k, job.c);
 }
 
 // ---------------------------------------------------------------------------
@@ -1560,6 +1561,240 @@ __global__ __launch_bounds__(kBlock) void rows_correct(const CorrectJob job) {
         if (w >= job.wps) {
             w -= job.wps;
             ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Pair location and correction (fec_locate2_batch / fec_correct2_batch), over
+// the stripes the single-block rules call MANY.
+//
+// locate2_finish: locate_finish's verdicts into plane 0 and NONE into plane 1
+// (plain stores).  A MANY stripe, when the pair pass runs (pw != 0), takes the
+// next entry of the dirty list -- list[0] is the counter, cleared with the
+// working words; a relaxed device-scope fetch_add -- stores its index there
+// and clears the entry's pw pair words, so clean data never touches them.
+//
+// pairs_locate: one wave per workgroup over a grid the host fixes without
+// knowing the list's length.  A wave reads the counter by a scalar load first
+// and leaves at once on an empty list, else walks (entry, 64-unit wave of the
+// stripe) grid-stride.  Per unit the c syndromes are formed in the lane's own
+// LDS slots (row i of lane l at (i * 64 + l) * 16 bytes: lanes read only what
+// they wrote, so no barrier; rows are addressed at wave-uniform offsets, so no
+// dynamically indexed register array exists): the stored checks first, then
+// P[i][j] . basis_j accumulated from P's tables by wave-uniform scalar loads.
+// A wave whose syndromes are all zero refutes nothing.  Otherwise every pair's
+// record is walked: r0, r1 (two rows on which [p_a p_b] has a nonzero minor),
+// then c - 2 entries (i, alpha's table, beta's table) with
+// s_i ^ alpha . s_r0 ^ beta . s_r1 == 0 at every byte iff the syndrome lies in
+// span(p_a, p_b); the first nonzero ballot refutes the pair and ends its walk.
+// Refuted bits leave 32 pairs at a time, from one lane, by a relaxed
+// device-scope fetch_or into the entry's pair words.
+//
+// pairs_finish: one lane per list entry; exactly one zero among the first
+// npairs pair bits names (a, b), written into both planes by plain stores.
+//
+// pairs_correct: rows_correct's walk over the list.  A wave reads its entry's
+// two verdict words first and touches no block unless they name a pair; then
+// record p (k source slots, 2 x k tables) is applied to the sources by
+// wave-uniform address arithmetic, and slots a and b take two streaming stores
+// per unit (store_tail for a block shorter than a chunk).  The targets are
+// never among the sources.  Dirty stripes are rare; speed is not a goal here.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLocateNone = 0xFFFFFFFCu;
+
+struct alignas(16) Finish2Job {
+    const uint32_t* bits;
+    uint32_t* culprit;   // two planes of nstripes words
+    uint32_t* list;      // [0] the counter, [1 + e] the stripe of entry e
+    uint32_t* pairbits;  // pw words per entry
+    uint32_t nstripes, k, c, words;
+    uint32_t pw, pad_[3];  // pw == 0: no pair pass
+};
+
+__global__ __launch_bounds__(kBlock) void locate2_finish(const Finish2Job job) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= job.nstripes) return;
+    const uint32_t v = finish_verdict(job.bits + size_t(s) * job.words, job.k, job.c);
+    job.culprit[s] = v;
+    job.culprit[size_t(job.nstripes) + s] = kLocateNone;
+    if (v == kLocateMany && job.pw != 0u) {
+        const uint32_t e = __hip_atomic_fetch_add(job.list, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        job.list[size_t(1) + e] = s;
+        uint32_t* const p = job.pairbits + size_t(e) * job.pw;
+        for (uint32_t i = 0; i < job.pw; ++i) p[i] = 0u;
+    }
+}
+
+struct alignas(16) PairsJob {
+    uint64_t sz, bstride, sstride;
+    uint32_t nstripes, cps;
+    uint32_t wps;          // waves per stripe
+    uint32_t gs_w, gs_e;   // grid stride expressed as (waves, entries): stride = gs_e*wps + gs_w
+    uint32_t k, c, nb;
+    uint32_t npairs, pw;   // pw = ceil(npairs / 32)
+    uint32_t pad_[2];
+    const uint32_t* list;
+    uint32_t* pairbits;
+    uint32_t* culprit;       // two planes of nstripes words
+    const uint32_t* ptabs;   // pairs_locate: P's c * k tables (row-major)
+    const uint32_t* recs;    // pairs_locate: npairs records of 2 + 11 (c - 2) dwords;
+                             // pairs_correct: npairs records of k + 10 k dwords
+    uint8_t* blocks;         // slot 0 of stripe 0
+};
+
+__device__ __forceinline__ Tab tab_at(CU32 p) { return Tab{p[0], p[1], p[2], p[3], p[4]}; }
+
+__global__ __launch_bounds__(64) void pairs_locate(const PairsJob job) {
+    extern __shared__ u32x4 pairs_syn[];  // c rows of 64 lanes
+    const CU32 list = (CU32)job.list;
+    const uint32_t count = list[0];
+    uint32_t e = blockIdx.x / job.wps, w = blockIdx.x - e * job.wps;
+    if (e >= count) return;  // (the empty list: one scalar load)
+    const uint32_t lane = threadIdx.x;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    const uint32_t k = job.k, c = job.c, rec = 2u + 11u * (c - 2u);
+    const CU32 ptabs = (CU32)job.ptabs, recs = (CU32)job.recs;
+    while (e < count) {
+        const uint32_t s = list[size_t(1) + e];
+        const uint32_t ci = w * 64u + lane;
+        const bool live = ci < job.cps;
+        const Span sp = chunk_span<kChunk, true>(ci, sz, nfull);
+        const uint8_t* const base = job.blocks + s * job.sstride + sp.off;
+        for (uint32_t i = 0; i < c; ++i) pairs_syn[i * 64u + lane] = load_unit(base + (k + i) * job.bstride, live, sp);
+        for (uint32_t j = 0; j < k; ++j) {
+            const u32x4 x = load_unit(base + j * job.bstride, live, sp);
+            const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
+            for (uint32_t i = 0; i < c; ++i) {
+                const Tab t[1] = {tab_at(ptabs + (size_t(i) * k + j) * 5u)};
+                u32x4 v = pairs_syn[i * 64u + lane];
+                v.x ^= gf_dot<1>(t, z[0]);
+                v.y ^= gf_dot<1>(t, z[1]);
+                v.z ^= gf_dot<1>(t, z[2]);
+                v.w ^= gf_dot<1>(t, z[3]);
+                pairs_syn[i * 64u + lane] = v;
+            }
+        }
+        uint32_t any = 0;
+        for (uint32_t i = 0; i < c; ++i) {
+            const u32x4 v = pairs_syn[i * 64u + lane];
+            any |= v.x | v.y | v.z | v.w;
+        }
+        if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {  // wave-uniform
+            uint32_t* const words = job.pairbits + size_t(e) * job.pw;
+            uint32_t refuted = 0;
+            for (uint32_t p = 0; p < job.npairs; ++p) {
+                const CU32 rp = recs + size_t(p) * rec;
+                const u32x4 s0 = pairs_syn[rp[0] * 64u + lane], s1 = pairs_syn[rp[1] * 64u + lane];
+                const Sel z[4][2] = {{selectors(s0.x), selectors(s1.x)},
+                                     {selectors(s0.y), selectors(s1.y)},
+                                     {selectors(s0.z), selectors(s1.z)},
+                                     {selectors(s0.w), selectors(s1.w)}};
+                for (uint32_t m = 0; m + 2u < c; ++m) {
+                    const CU32 q = rp + 2u + 11u * m;
+                    const u32x4 si = pairs_syn[q[0] * 64u + lane];
+                    const Tab t[2] = {tab_at(q + 1), tab_at(q + 6)};
+                    const uint32_t d = (si.x ^ gf_dot<2>(t, z[0])) | (si.y ^ gf_dot<2>(t, z[1])) |
+                                       (si.z ^ gf_dot<2>(t, z[2])) | (si.w ^ gf_dot<2>(t, z[3]));
+                    if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) {
+                        refuted |= 1u << (p & 31u);
+                        break;
+                    }
+                }
+                if ((p & 31u) == 31u || p + 1u == job.npairs) {
+                    if (refuted != 0u && lane == 0u)
+                        (void)__hip_atomic_fetch_or(words + (p >> 5), refuted, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT);
+                    refuted = 0;
+                }
+            }
+        }
+        w += job.gs_w;
+        e += job.gs_e;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++e;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void pairs_finish(const PairsJob job) {
+    const uint32_t count = ((CU32)job.list)[0];
+    for (uint64_t e = uint64_t(blockIdx.x) * kBlock + threadIdx.x; e < count; e += uint64_t(gridDim.x) * kBlock) {
+        const uint32_t s = job.list[1u + e];
+        const uint32_t* const p = job.pairbits + e * job.pw;
+        uint32_t nleft = 0, first = 0;
+        for (uint32_t i = 0; i < job.pw; ++i) {
+            const uint32_t v = ~p[i] & low_bits(job.npairs - 32u * i);
+            if (v != 0u && nleft == 0u) first = 32u * i + static_cast<uint32_t>(__builtin_ctz(v));
+            nleft += static_cast<uint32_t>(__builtin_popcount(v));
+        }
+        if (nleft != 1u) continue;  // the planes stay (MANY, NONE)
+        // pair index a*nb - a(a+1)/2 + (b - a - 1) back into (a, b)
+        uint32_t a = 0, row = job.nb - 1u;
+        while (first >= row) {
+            first -= row;
+            ++a;
+            --row;
+        }
+        job.culprit[s] = a;
+        job.culprit[size_t(job.nstripes) + s] = a + 1u + first;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void pairs_correct(const PairsJob job) {
+    const CU32 list = (CU32)job.list;
+    const uint32_t count = list[0];
+    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t e = gw / job.wps, w = gw - e * job.wps;
+    if (e >= count) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t sz = job.sz;
+    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
+    const uint32_t k = job.k;
+    const CU32 verdict = (CU32)job.culprit, recs = (CU32)job.recs;
+    while (e < count) {
+        const uint32_t s = list[size_t(1) + e];
+        const uint32_t a = verdict[s], b = verdict[size_t(job.nstripes) + s];
+        if (a < b && b < job.nb) {  // wave-uniform
+            const uint32_t ci = w * 64u + lane;
+            const bool live = ci < job.cps;
+            const Span sp = chunk_span<kChunk, true>(ci, sz, nfull);
+            uint8_t* const base = job.blocks + s * job.sstride + sp.off;
+            const uint32_t p = a * job.nb - a * (a + 1u) / 2u + (b - a - 1u);
+            const CU32 rp = recs + size_t(p) * (11u * k);
+            u32x4 ya{0u, 0u, 0u, 0u}, yb{0u, 0u, 0u, 0u};
+            for (uint32_t l = 0; l < k; ++l) {
+                const u32x4 x = load_unit(base + rp[l] * job.bstride, live, sp);
+                const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
+                const Tab ta[1] = {tab_at(rp + k + 5u * l)}, tb[1] = {tab_at(rp + 6u * k + 5u * l)};
+                ya.x ^= gf_dot<1>(ta, z[0]);
+                ya.y ^= gf_dot<1>(ta, z[1]);
+                ya.z ^= gf_dot<1>(ta, z[2]);
+                ya.w ^= gf_dot<1>(ta, z[3]);
+                yb.x ^= gf_dot<1>(tb, z[0]);
+                yb.y ^= gf_dot<1>(tb, z[1]);
+                yb.z ^= gf_dot<1>(tb, z[2]);
+                yb.w ^= gf_dot<1>(tb, z[3]);
+            }
+            if (live) {
+                uint8_t* const oa = base + a * job.bstride;
+                uint8_t* const ob = base + b * job.bstride;
+                if (sp.full) {
+                    store16_pol<0>(oa, ya);
+                    store16_pol<0>(ob, yb);
+                } else {
+                    store_tail(oa, ya, sp.nb);
+                    store_tail(ob, yb, sp.nb);
+                }
+            }
+        }
+        w += job.gs_w;
+        e += job.gs_e;
+        if (w >= job.wps) {
+            w -= job.wps;
+            ++e;
         }
     }
 }
@@ -4799,6 +5034,114 @@ hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream) {
     });
     up.done(stream);
     if (e == hipSuccess) t_last_kernel = reg ? kNames[p.k] : "rows_correct";
+    return e;
+}
+
+hipError_t launch_locate2_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
+                                 uint32_t* culprit, uint32_t* list, uint32_t* pairbits, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (!bits || !culprit || k < 1 || c < 1 || nstripes == 0 || nstripes >= (1ull << 32) ||
+        words != (c + 31) / 32 + (k + 31) / 32 || (list != nullptr) != (pairbits != nullptr) ||
+        (list && !pairs_shape_ok(k, c)))
+        return hipErrorInvalidValue;
+    Finish2Job job;
+    job.bits = bits;
+    job.culprit = culprit;
+    job.list = list;
+    job.pairbits = pairbits;
+    job.nstripes = static_cast<uint32_t>(nstripes);
+    job.k = k;
+    job.c = c;
+    job.words = words;
+    job.pw = list ? pairs_words(k + c) : 0u;
+    job.pad_[0] = job.pad_[1] = job.pad_[2] = 0;
+    const uint32_t grid = static_cast<uint32_t>((nstripes + kBlock - 1) / kBlock);
+    return launch_job(reinterpret_cast<const void*>(locate2_finish), grid, kBlock, 0, stream, job);
+}
+
+hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (!pairs_shape_ok(p.k, p.c) || !p.P || !p.pivots || (p.sources != nullptr) != (p.crows != nullptr) ||
+        !p.blocks || !p.list || !p.pairbits || !p.culprit || p.sz == 0 || p.nstripes == 0 ||
+        p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    const uint32_t k = p.k, c = p.c, nb = k + c, npairs = nb * (nb - 1) / 2;
+    const bool heal = p.sources != nullptr;
+    // one upload: P's tables, the pairs' location records, then (heal) their correction records
+    const size_t prec = 2 + 11 * size_t(c - 2), crec = 11 * size_t(k);
+    const size_t off_loc = size_t(c) * k * 5, off_cor = off_loc + npairs * prec;
+    const size_t dwords = off_cor + (heal ? npairs * crec : 0);
+    StagedUpload up;
+    hipError_t e = up.acquire(dwords * sizeof(uint32_t));
+    if (e != hipSuccess) return e;
+    uint32_t* const ht = reinterpret_cast<uint32_t*>(up.host());
+    for (size_t i = 0; i < size_t(c) * k; ++i) host_tab(ht + i * 5, p.P[i]);
+    const size_t pbytes = 2 + 3 * size_t(c - 2);
+    for (uint32_t q = 0; q < npairs; ++q) {
+        const uint8_t* src = p.pivots + q * pbytes;
+        uint32_t* dst = ht + off_loc + q * prec;
+        dst[0] = src[0];
+        dst[1] = src[1];
+        for (uint32_t m = 0; m + 2 < c; ++m) {
+            dst[2 + 11 * m] = src[2 + 3 * m];
+            host_tab(dst + 2 + 11 * m + 1, src[2 + 3 * m + 1]);
+            host_tab(dst + 2 + 11 * m + 6, src[2 + 3 * m + 2]);
+        }
+        if (!heal) continue;
+        dst = ht + off_cor + q * crec;
+        for (uint32_t l = 0; l < k; ++l) dst[l] = p.sources[size_t(q) * k + l];
+        for (uint32_t l = 0; l < 2 * k; ++l) host_tab(dst + k + 5 * l, p.crows[size_t(q) * 2 * k + l]);
+    }
+    if ((e = up.copy(dwords * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    const uint32_t* const dev = reinterpret_cast<const uint32_t*>(up.dev());
+    PairsJob job;
+    const uint64_t cps = (p.sz + kChunk - 1) / kChunk, wps = (cps + 63) / 64;
+    job.sz = p.sz;
+    job.bstride = p.bstride;
+    job.sstride = p.sstride;
+    job.nstripes = static_cast<uint32_t>(p.nstripes);
+    job.cps = static_cast<uint32_t>(cps);
+    job.wps = static_cast<uint32_t>(wps);
+    job.k = k;
+    job.c = c;
+    job.nb = nb;
+    job.npairs = npairs;
+    job.pw = pairs_words(nb);
+    job.pad_[0] = job.pad_[1] = 0;
+    job.list = p.list;
+    job.pairbits = p.pairbits;
+    job.culprit = p.culprit;
+    job.ptabs = dev;
+    job.recs = dev + off_loc;
+    job.blocks = p.blocks;
+    // The host does not know the list's length: fixed grids, sized to fill the
+    // device for a fully dirty batch, that walk grid-stride.  An empty list
+    // costs every wave one scalar load.
+    const uint64_t waves = p.nstripes * wps;
+    const auto walk = [&](uint64_t per_group, uint64_t groups_per_cu) {
+        const uint64_t need = (waves + per_group - 1) / per_group;
+        const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * groups_per_cu);
+        const uint64_t grid = need < cap ? need : cap, gstride = grid * per_group;
+        job.gs_e = static_cast<uint32_t>(gstride / wps);
+        job.gs_w = static_cast<uint32_t>(gstride % wps);
+        return static_cast<uint32_t>(grid);
+    };
+    uint32_t grid = walk(1, 32);  // one wave per workgroup, c KiB of LDS each
+    e = launch_job(reinterpret_cast<const void*>(pairs_locate), grid, 64, size_t(c) * 64 * sizeof(u32x4), stream, job);
+    if (e == hipSuccess) {
+        const uint64_t need = (p.nstripes + kBlock - 1) / kBlock, cap = hooked_grid_cap(uint64_t(g_num_cu) * 8);
+        e = launch_job(reinterpret_cast<const void*>(pairs_finish), static_cast<uint32_t>(need < cap ? need : cap),
+                       kBlock, 0, stream, job);
+    }
+    if (e == hipSuccess && heal) {
+        job.recs = dev + off_cor;
+        grid = walk(kBlock / 64, 8);
+        e = launch_job(reinterpret_cast<const void*>(pairs_correct), grid, kBlock, 0, stream, job);
+    }
+    up.done(stream);
+    if (e == hipSuccess) t_last_kernel = heal ? "pairs_correct" : "pairs_locate";
     return e;
 }
 

@@ -262,6 +262,46 @@ struct CorrectSpec {
 };
 hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream);
 
+// Pair location and correction (fec_locate2_batch, fec_correct2_batch) over the
+// stripes the single-block rules call MANY, for c >= 4 checks and nb = k + c <=
+// 32 slots.  Pair (a, b), a < b, has index a*nb - a(a+1)/2 + (b - a - 1).
+//
+// launch_locate2_finish (locate2_finish): launch_locate_finish's verdicts into
+// culprit[0..nstripes) and NONE into culprit[nstripes..2 nstripes).  With list
+// and pairbits (both or neither; device memory the library owns, 1 + nstripes
+// and nstripes * pairs_words(nb) words; list[0] cleared by the caller in
+// stream order) every MANY stripe takes the next list entry and has the
+// entry's pair words cleared.
+//
+// launch_pairs: one staged upload (so hipErrorNotSupported under capture), then
+// pairs_locate (refuted pair bits OR-ed into the entries' words), pairs_finish
+// (an entry with exactly one pair left gets (a, b) in the two planes) and, with
+// sources / crows, pairs_correct (slots a and b of such a stripe rewritten in
+// place).  All three run over fixed grids and do nothing on an empty list.
+//   pivots: per pair 2 + 3 (c - 2) bytes: r0, r1, then (i, alpha, beta) for
+//     every other row i: s_i ^ alpha . s_r0 ^ beta . s_r1 vanishes exactly on
+//     span(p_a, p_b);
+//   sources, crows: per pair the k source slots and the 2 x k coefficients
+//     that yield slots a and b from them (fec_correct2_rows).
+constexpr bool pairs_shape_ok(uint32_t k, uint32_t c) { return k >= 1 && c >= 4 && k + c <= 32; }
+constexpr uint32_t pairs_words(uint32_t nb) { return (nb * (nb - 1) / 2 + 31) / 32; }
+struct PairsSpec {
+    uint32_t k, c;
+    const uint8_t* P;         // c x k (host memory, as everything down to crows)
+    const uint8_t* pivots;
+    const uint32_t* sources;  // null: locate only
+    const uint8_t* crows;
+    uint8_t* blocks;          // slot 0 of stripe 0, a kernel-visible address
+    uint64_t bstride, sstride;
+    uint64_t sz, nstripes;
+    const uint32_t* list;
+    uint32_t* pairbits;
+    uint32_t* culprit;  // the two planes, device memory
+};
+hipError_t launch_locate2_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
+                                 uint32_t* culprit, uint32_t* list, uint32_t* pairbits, hipStream_t stream);
+hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
