@@ -150,6 +150,91 @@ int fec_decode_batch(const fec_t* code,
                      const unsigned* index, size_t sz, size_t nstripes,
                      void* stream, unsigned flags);
 
+/* Ragged batches: batched encode and decode whose stripes each have their own
+ * size (a store's objects do not share a length; a file cut into segments ends
+ * in a short one), in one launch.
+ *
+ * Stripe s has blocks of sizes[s] bytes; 0 is allowed, and such a stripe is
+ * neither read nor written.  Input block j of stripe s starts at
+ * src + src_offsets[s] + j*B, with B = src_block_stride when that is nonzero and
+ * B = sizes[s] otherwise: the packed object [block 0 | block 1 | ... | block
+ * k-1], which is what an easyfec-style object whose length is a multiple of k
+ * already is.  Output row i of stripe s starts at dst + dst_offsets[s] + i*B',
+ * B' from dst_block_stride / sizes[s] in the same way.  A nonzero fixed stride
+ * describes block-major arenas: block j of every stripe lies in arena j, and
+ * the offsets are a prefix sum of the sizes.  Offsets are arbitrary bytes: no
+ * alignment, no ordering.  Outputs must not overlap each other or the inputs.
+ *
+ * fec_encode_batch_ragged writes the blocks block_nums[0..num_block_nums) as
+ * fec_encode_batch does (a number below k copies that primary);
+ * fec_decode_batch_ragged takes fec_decode_batch's index (primary i at slot i)
+ * and writes the missing primaries in ascending order, or with
+ * FEC_FLAG_ALL_PRIMARIES all k.  The bytes are those of fec_encode_batch /
+ * fec_decode_batch called once per stripe with nstripes = 1.
+ *
+ * sizes, src_offsets and dst_offsets are three arrays of nstripes 8-byte words
+ * (8-byte aligned), all three in host memory or all three in device memory on
+ * the blocks' device; a mix returns FEC_EINVAL.  Host arrays are copied when the
+ * call is made and may be reused when it returns; device arrays are read where
+ * they are, in stream order, and nothing synchronises the stream.
+ *
+ * src_bytes and dst_bytes are the extents of the two arenas.  A stripe with
+ * sizes[s] > 0 FITS when offset + (rows - 1)*B + sizes[s] <= bytes on both sides
+ * (rows = k for src, the output rows for dst), evaluated without wrapping.
+ * With host arrays a stripe that does not fit is FEC_EINVAL, the message naming
+ * the stripe and the side.  Device arrays the host cannot look at: the kernel
+ * makes the same test per stripe, a stripe that does not fit is neither read
+ * nor written, and no error is reported (the rule an id >= npatterns follows
+ * in fec_decode_batch_mixed) -- a wrong device-side descriptor leaves bytes
+ * untouched instead of causing a wild access.
+ *
+ * src and dst are device memory on one device, or page-locked host memory;
+ * pageable host memory returns FEC_EINVAL (this call does not stage).
+ * FEC_FLAG_ASYNC and FEC_FLAG_LIBRARY_STREAM as in fec_decode_batch;
+ * FEC_FLAG_ROW_PADDING is accepted and ignored.  While the stream is being
+ * captured into a graph the call returns FEC_EINVAL: it stages per call through
+ * slots the library reuses.
+ *
+ * Checked before any GPU work, in this order, each FEC_EINVAL with a message:
+ * an invalid fec_t; a NULL src, dst, sizes, src_offsets, dst_offsets or
+ * block_nums / index; num_block_nums == 0 or a block number >= n (decode: the
+ * checks of fec_decode_batch); nstripes >= 2^32; descriptor arrays of mixed
+ * memory kinds; with host arrays a stripe that does not fit.  Then FEC_ENODEV
+ * when no GPU is visible.  nstripes == 0 returns FEC_OK, and so does a batch
+ * whose sizes are all zero, which with host arrays launches nothing.
+ *
+ * k <= 4 is one launch of matapply_ragged<k,r> per 8 output rows: every wave
+ * walks a contiguous range of 1 KiB wave steps ("units", fec_ragged_units) and
+ * reads each stripe's size and offsets by scalar loads; with device arrays a
+ * short scan kernel (ragged_scan) first writes the units' prefix sum into
+ * memory the library owns.  Wider codes are cut into runs of consecutive
+ * stripes of one size whose two offsets each advance by a constant, each run
+ * one fec_encode_batch / fec_decode_batch-style launch (at worst one per
+ * stripe); on that path device-side arrays are first copied to the host, which
+ * SYNCHRONISES the stream, and stripes that do not fit are skipped there too. */
+int fec_encode_batch_ragged(const fec_t* code,
+                            const gf* src, size_t src_bytes, size_t src_block_stride,
+                            const unsigned long long* src_offsets,
+                            gf* dst, size_t dst_bytes, size_t dst_block_stride,
+                            const unsigned long long* dst_offsets,
+                            const unsigned long long* sizes,
+                            const unsigned* block_nums, size_t num_block_nums,
+                            size_t nstripes, void* stream, unsigned flags);
+int fec_decode_batch_ragged(const fec_t* code,
+                            const gf* src, size_t src_bytes, size_t src_block_stride,
+                            const unsigned long long* src_offsets,
+                            gf* dst, size_t dst_bytes, size_t dst_block_stride,
+                            const unsigned long long* dst_offsets,
+                            const unsigned long long* sizes,
+                            const unsigned* index,
+                            size_t nstripes, void* stream, unsigned flags);
+
+/* Host only, no GPU: the units of a ragged batch.  Stripe s has
+ * u(s) = ceil(sizes[s] / 1024) units -- one unit is one wave step, 64 lanes x
+ * 16 bytes of every block -- and ustart[0..nstripes] receives their exclusive
+ * prefix sum, so ustart[nstripes] is the total.  FEC_OK / FEC_EINVAL (NULL). */
+int fec_ragged_units(const unsigned long long* sizes, size_t nstripes, unsigned long long* ustart);
+
 /* Batched decode, a pattern per stripe: every stripe of the batch may have
  * received different blocks (a storage node repairing many small objects).
  * patterns: npatterns x k block numbers (host memory); pattern p says slot j of

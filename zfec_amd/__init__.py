@@ -179,6 +179,79 @@ def _devices_arg(blocks, devices):
     return devs
 
 
+def _ragged_words(x, what):
+    """One descriptor array of a ragged call as a contiguous 1-D int64 torch
+    tensor: a tensor is checked, a host sequence of ints becomes a CPU tensor."""
+    import torch
+
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.int64 or x.dim() != 1:
+            raise Error("Precondition violation: %s is required to be a 1-D int64 tensor or a sequence of ints" % what)
+        return x.contiguous()
+    try:
+        vals = list(x)
+    except TypeError:
+        raise Error("Precondition violation: %s is required to be a 1-D int64 tensor or a sequence of ints" % what)
+    for v in vals:
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise Error("Precondition violation: %s is required to be a 1-D int64 tensor or a sequence of ints" % what)
+        if v < 0 or v >= 2**63:
+            raise Error("Precondition violation: %s is required to hold sizes and offsets in [0, 2^63), but one was %d"
+                        % (what, v))
+    return torch.tensor(vals, dtype=torch.int64)
+
+
+def _ragged_call(coder, fn, data, sizes, offsets, out, out_offsets, nums, r):
+    """The arguments of Encoder.encode_ragged / Decoder.decode_ragged checked
+    and completed, then capi.Code.<fn>; returns (out, out_offsets)."""
+    import torch
+
+    k = coder.k
+    for t, what in ((data, "data"), (out, "out")):
+        if t is None and what == "out":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+            raise Error("Precondition violation: %s is required to be a 1-D contiguous uint8 device tensor" % what)
+    arrays = [("sizes", _ragged_words(sizes, "sizes"))]
+    if offsets is not None:
+        arrays.append(("offsets", _ragged_words(offsets, "offsets")))
+    if out_offsets is not None:
+        arrays.append(("out_offsets", _ragged_words(out_offsets, "out_offsets")))
+    sizes = arrays[0][1]
+    ns = sizes.numel()
+    for what, a in arrays[1:]:
+        if a.numel() != ns:
+            raise Error("Precondition violation: %s is required to hold one word per stripe: %d, not %d"
+                        % (what, ns, a.numel()))
+    for what, a in arrays[1:]:
+        if a.device != sizes.device:
+            raise Error("Precondition violation: sizes, offsets and out_offsets are required to be all on the data's "
+                        "device or all on the CPU, but sizes is on %s and %s on %s" % (sizes.device, what, a.device))
+    if sizes.is_cuda and sizes.device != data.device:
+        raise Error("Precondition violation: sizes, offsets and out_offsets are required to be all on the data's "
+                    "device or all on the CPU, but sizes is on %s and data on %s" % (sizes.device, data.device))
+    if not sizes.is_cuda:
+        for what, a in arrays:
+            if ns and int(a.min()) < 0:
+                raise Error("Precondition violation: %s is required to hold sizes and offsets in [0, 2^63), but one "
+                            "was %d" % (what, int(a.min())))
+    if not _is_device_tensor(data) or (out is not None and (not _is_device_tensor(out) or out.device != data.device)):
+        raise Error("Precondition violation: data and out are required to be uint8 tensors on one GPU")
+    # the packed object-major layout: stripe after stripe, a stripe's blocks back to back
+    if offsets is None or out_offsets is None:
+        start = torch.cumsum(sizes, 0) - sizes
+    offsets = k * start if offsets is None else dict(arrays)["offsets"]
+    out_offsets = r * start if out_offsets is None else dict(arrays)["out_offsets"]
+    if out is None:
+        out = torch.empty(r * int(sizes.sum()) if ns else 0, dtype=torch.uint8, device=data.device)
+    if ns and r and data.numel() and out.numel():
+        with torch.cuda.device(data.device), _as_error():
+            getattr(_capi_code(coder), fn)(data.data_ptr(), data.numel(), 0, offsets.data_ptr(), out.data_ptr(),
+                                           out.numel(), 0, out_offsets.data_ptr(), sizes.data_ptr(), nums, ns,
+                                           stream=_stream_handle(data.device))
+    return out, out_offsets
+
+
 def _capi_code(coder):
     code = getattr(coder, "_batch_code", None)
     if code is None:
@@ -351,6 +424,32 @@ class Encoder(_fec.Encoder):
                                                   flags=flags)
         return out
 
+    def encode_ragged(self, data, sizes, offsets=None, desired_blocks_nums=None, out=None, out_offsets=None):
+        """Encode many stripes of different sizes in one launch
+        (fec_encode_batch_ragged).
+
+        data and out are 1-D uint8 device tensors, the two arenas; their
+        numel() are the extents no stripe may pass.  Stripe s has k blocks of
+        sizes[s] bytes back to back from data[offsets[s]] (an object of k *
+        sizes[s] bytes), and its r = len(desired_blocks_nums) secondary blocks
+        (default k..m-1) are written back to back from out[out_offsets[s]].
+        sizes, offsets and out_offsets are int64 tensors, all on data's device
+        (nothing then synchronises the stream) or all on the CPU; host
+        sequences of ints are taken too.  The default offsets are the packed
+        layout, stripe after stripe: offsets = k * (cumsum(sizes) - sizes) and
+        out_offsets = r * (cumsum(sizes) - sizes), computed on the sizes'
+        device.  out=None allocates r * sizes.sum() bytes, which with sizes on
+        the device costs one .item(): passing out avoids it.  A device-side
+        stripe that does not fit its arena is left unwritten; a host-side one
+        is an Error.  Returns (out, out_offsets)."""
+        k, m = self.k, self.m
+        nums = list(range(k, m)) if desired_blocks_nums is None else list(desired_blocks_nums)
+        for x in nums:
+            if not isinstance(x, int) or x < k or x >= m:
+                raise Error("Precondition violation: encode_ragged desired block nums are required to be secondary "
+                            "block nums in [k, m-1] = [%d, %d], but one was %r" % (k, m - 1, x))
+        return _ragged_call(self, "encode_batch_ragged", data, sizes, offsets, out, out_offsets, nums, len(nums))
+
     def _encode_device(self, inblocks, desired):
         import torch
 
@@ -430,6 +529,32 @@ class Decoder(_fec.Decoder):
                     _capi_code(self).decode_batch(ptr, sbs, sss, optr, obs, oss, nums, sz, ns, stream=stream,
                                                   flags=flags)
         return out
+
+    def decode_ragged(self, data, sizes, blocknums, offsets=None, out=None, out_offsets=None):
+        """Decode many stripes of different sizes that all received the same
+        block numbers, in one launch (fec_decode_batch_ragged).
+
+        Arguments as Encoder.encode_ragged: slot j of stripe s, holding block
+        blocknums[j], is the sizes[s] bytes from data[offsets[s] + j *
+        sizes[s]]; a primary block must sit at its own slot, as in
+        decode_batch.  The r missing primaries of stripe s (ascending) are
+        written back to back from out[out_offsets[s]].  Returns (out,
+        out_offsets)."""
+        k, m = self.k, self.m
+        try:
+            nums = list(blocknums)
+        except TypeError:
+            raise TypeError("Third argument was not a sequence.")
+        if len(nums) != k or len(set(nums)) != k:
+            raise Error("Precondition violation: blocknums is required to hold k = %d distinct block nums" % k)
+        for i, x in enumerate(nums):
+            if not isinstance(x, int) or x < 0 or x >= m:
+                raise Error("Precondition violation: block nums are required to be in [0, m-1] = [0, %d], but one "
+                            "was %r" % (m - 1, x))
+            if x < k and x != i:
+                raise Error("Precondition violation: decode_ragged requires primary block %d at slot %d" % (x, x))
+        r = sum(1 for x in nums if x >= k)
+        return _ragged_call(self, "decode_batch_ragged", data, sizes, offsets, out, out_offsets, nums, r)
 
     def decode_batch_mixed(self, blocks, blocknums):
         """Decode many independent stripes that each received their own block

@@ -74,6 +74,9 @@ SYMBOLS = [
     ("fec_repair_plan_new", ctypes.c_int, [_P, _UP, _UP, _SZ, _SZ, ctypes.c_int, _PP]),
     ("fec_repair_plan_free", None, [_P]),
     ("fec_repair_batch_planned", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _SZ, _SZ, _P, _U]),
+    ("fec_encode_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _U]),
+    ("fec_decode_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _P, _U]),
+    ("fec_ragged_units", ctypes.c_int, [_P, _SZ, _P]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_LOCATE_NONE = 0xFFFFFFFC  # fec_locate2_batch: the second word of a verdict that is no pair
@@ -168,6 +171,16 @@ def last_wait():
     """1 if the calling thread's last synchronous small-object call waited on
     the completion word its kernel wrote, 0 if on hipStreamSynchronize."""
     return lib().fec_last_wait()
+
+
+def ragged_units(sizes):
+    """fec_ragged_units: the exclusive prefix sum of ceil(size / 1024) over
+    `sizes`, len(sizes) + 1 ints; the last one is the total."""
+    n = len(sizes)
+    arr = (ctypes.c_ulonglong * max(1, n))(*[int(x) for x in sizes])
+    out = (ctypes.c_ulonglong * (n + 1))()
+    check(lib().fec_ragged_units(ctypes.addressof(arr), n, ctypes.addressof(out)))
+    return list(out)
 
 
 def ptr_array(addrs):
@@ -283,6 +296,27 @@ class Code(object):
             arr = uint_array([x for p in rows for x in p])
         st = lib().fec_decode_batch_mixed(self.ptr, src, sbs, sss, dst, dbs, dss, arr, npat, pattern_of_ptr or None, sz,
                                           nstripes, stream or None, flags)
+        if st:
+            check(st)
+
+    def encode_batch_ragged(self, src, src_bytes, sbs, src_offsets_ptr, dst, dst_bytes, dbs, dst_offsets_ptr,
+                            sizes_ptr, block_nums, nstripes, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_encode_batch_ragged: the three `_ptr` arguments are the
+        addresses of nstripes 8-byte words each, all in host or all in device
+        memory, which the caller keeps alive until the call returns."""
+        st = lib().fec_encode_batch_ragged(self.ptr, src, src_bytes, sbs, src_offsets_ptr or None, dst, dst_bytes,
+                                           dbs, dst_offsets_ptr or None, sizes_ptr or None, _nums(block_nums),
+                                           len(block_nums), nstripes, stream or None, flags)
+        if st:
+            check(st)
+
+    def decode_batch_ragged(self, src, src_bytes, sbs, src_offsets_ptr, dst, dst_bytes, dbs, dst_offsets_ptr,
+                            sizes_ptr, index, nstripes, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_decode_batch_ragged: as encode_batch_ragged, with
+        decode_batch's index."""
+        st = lib().fec_decode_batch_ragged(self.ptr, src, src_bytes, sbs, src_offsets_ptr or None, dst, dst_bytes,
+                                           dbs, dst_offsets_ptr or None, sizes_ptr or None, _nums(index), nstripes,
+                                           stream or None, flags)
         if st:
             check(st)
 

@@ -1394,6 +1394,215 @@ FEC_API int fec_decode_batch(const fec_t* code, const gf* src, size_t src_block_
     });
 }
 
+// ---- ragged batches: a size per stripe ------------------------------------------------
+namespace {
+constexpr char kCaptureRagged[] = "the call stages per call through slots the library reuses";
+
+struct RaggedCall {
+    const char* fn;
+    const gf* src;
+    size_t src_bytes, sbs;
+    const unsigned long long* soff;
+    gf* dst;
+    size_t dst_bytes, dbs;
+    const unsigned long long* doff;
+    const unsigned long long* sizes;
+    size_t nstripes;
+    void* stream;
+    unsigned flags;
+};
+
+int ragged_null(const RaggedCall& c, const void* nums, const char* nums_name) {
+    const struct {
+        const void* p;
+        const char* name;
+    } args[] = {{c.src, "src"},          {c.dst, "dst"}, {c.sizes, "sizes"}, {c.soff, "src_offsets"},
+                {c.doff, "dst_offsets"}, {nums, nums_name}};
+    for (const auto& a : args)
+        if (!a.p) return set_status(FEC_EINVAL, "%s: %s is NULL", c.fn, a.name);
+    return FEC_OK;
+}
+
+// Whether stripe s fits both arenas (kernels.hpp ragged_fits); *side: the one it does not.
+bool ragged_stripe_fits(const RaggedCall& c, unsigned k, unsigned r, const unsigned long long* sizes,
+                        const unsigned long long* soff, const unsigned long long* doff, size_t s,
+                        const char** side = nullptr) {
+    const uint64_t sz = sizes[s];
+    if (!ragged_fits(soff[s], c.sbs ? c.sbs : sz, k, sz, c.src_bytes)) {
+        if (side) *side = "src";
+        return false;
+    }
+    if (!ragged_fits(doff[s], c.dbs ? c.dbs : sz, r, sz, c.dst_bytes)) {
+        if (side) *side = "dst";
+        return false;
+    }
+    return true;
+}
+
+// The checks of a ragged call that follow its block numbers, in the header's
+// order: the stripe count, the memory kind of the three descriptor arrays
+// (*ddev: their device, -1 host memory), and with host arrays every stripe's fit.
+int check_ragged(const RaggedCall& c, unsigned k, unsigned r, int* ddev) {
+    if (uint64_t(c.nstripes) >= (1ull << 32))
+        return set_status(FEC_EINVAL, "%s: %zu stripes: a call takes fewer than 2^32", c.fn, c.nstripes);
+    int dv[3] = {-1, -1, -1};
+    if (gpu_available()) {
+        dv[0] = pointer_device(c.sizes);
+        dv[1] = pointer_device(c.soff);
+        dv[2] = pointer_device(c.doff);
+    }
+    if (dv[0] != dv[1] || dv[0] != dv[2])
+        return set_status(FEC_EINVAL, "%s: sizes, src_offsets and dst_offsets are of mixed memory kinds: all three "
+                                      "in host memory, or all three in device memory on the blocks' device", c.fn);
+    *ddev = dv[0];
+    if (*ddev < 0)
+        for (size_t s = 0; s < c.nstripes; ++s) {
+            const char* side = "";
+            if (c.sizes[s] && !ragged_stripe_fits(c, k, r, c.sizes, c.soff, c.doff, s, &side)) {
+                const bool in = side[0] == 's';
+                return set_status(FEC_EINVAL, "%s: stripe %zu does not fit %s: offset %llu, %u rows %llu apart, size "
+                                              "%llu, %s_bytes %zu", c.fn, s, side, in ? c.soff[s] : c.doff[s],
+                                  in ? k : r, static_cast<unsigned long long>(in ? (c.sbs ? c.sbs : c.sizes[s])
+                                                                                 : (c.dbs ? c.dbs : c.sizes[s])),
+                                  c.sizes[s], side, in ? c.src_bytes : c.dst_bytes);
+            }
+        }
+    return FEC_OK;
+}
+
+int run_ragged(const RaggedCall& c, const fec_t* code, const uint8_t* coef, unsigned r, int ddev) {
+    const unsigned k = code->k;
+    const size_t ns = c.nstripes;
+    // device memory on one device, or page-locked host memory (read and written in place)
+    const BatchBuf bufs[2] = {{c.src, c.src_bytes, "src"}, {c.dst, c.dst_bytes, "dst"}};
+    BatchMem mem;
+    if (resolve_batch(mem, c.fn, bufs, 2, "sizes", ddev, c.stream, c.flags, kCaptureRagged)) return t_status;
+    hipStream_t st = mem.st;
+    hipError_t e;
+    if (k <= kMixedMaxK) {
+        RaggedSpec g;
+        g.k = k;
+        g.r = r;
+        g.coef = coef;
+        g.in = mem.z[0];
+        g.out = const_cast<gf*>(mem.z[1]);
+        g.in_bytes = c.src_bytes;
+        g.out_bytes = c.dst_bytes;
+        g.in_bstride = c.sbs;
+        g.out_bstride = c.dbs;
+        g.sizes = reinterpret_cast<const uint64_t*>(c.sizes);
+        g.in_off = reinterpret_cast<const uint64_t*>(c.soff);
+        g.out_off = reinterpret_cast<const uint64_t*>(c.doff);
+        g.desc_host = ddev < 0;
+        g.nstripes = ns;
+        ++t_launches;
+        if ((e = launch_ragged(g, st)) != hipSuccess) return hip_fail(e, "launch_ragged");
+    } else {
+        // wider codes: runs of consecutive stripes of one size whose two offsets
+        // each advance by a constant, each run one shared-matrix batched launch
+        const unsigned long long *sizes = c.sizes, *soff = c.soff, *doff = c.doff;
+        thread_local std::vector<unsigned long long> hd;
+        if (ddev >= 0) {
+            hd.resize(3 * ns);
+            const unsigned long long* from[3] = {c.sizes, c.soff, c.doff};
+            for (int i = 0; i < 3; ++i)
+                if ((e = hipMemcpyAsync(&hd[i * ns], from[i], ns * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                        st)) != hipSuccess)
+                    return hip_fail(e, "hipMemcpyAsync D2H (descriptor arrays)");
+            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+            sizes = hd.data();
+            soff = sizes + ns;
+            doff = soff + ns;
+        }
+        const auto live = [&](size_t s) { return sizes[s] && ragged_stripe_fits(c, k, r, sizes, soff, doff, s); };
+        const unsigned jf = (c.flags & FEC_FLAG_LIBRARY_STREAM) | FEC_FLAG_ASYNC;
+        for (size_t s0 = 0; s0 < ns;) {
+            if (!live(s0)) {  // empty, or (device-side arrays) it does not fit: neither read nor written
+                ++s0;
+                continue;
+            }
+            const size_t sz = sizes[s0];
+            size_t s1 = s0 + 1, dsrc = 0, ddst = 0;
+            if (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s0] && doff[s1] > doff[s0] && live(s1)) {
+                dsrc = soff[s1] - soff[s0];
+                ddst = doff[s1] - doff[s0];
+                ++s1;
+                while (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s1 - 1] && soff[s1] - soff[s1 - 1] == dsrc &&
+                       doff[s1] > doff[s1 - 1] && doff[s1] - doff[s1 - 1] == ddst && live(s1))
+                    ++s1;
+            }
+            if (run_batch(code, coef, r, c.src + soff[s0], c.sbs ? c.sbs : sz, dsrc, c.dst + doff[s0],
+                          c.dbs ? c.dbs : sz, ddst, sz, s1 - s0, c.stream, jf))
+                return t_status;
+            s0 = s1;
+        }
+    }
+    if (!(c.flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+
+int no_gpu() { return set_status(FEC_ENODEV, "no GPU visible to HIP (the engine has no CPU path)"); }
+}  // namespace
+
+FEC_API int fec_ragged_units(const unsigned long long* sizes, size_t nstripes, unsigned long long* ustart) {
+    if ((!sizes && nstripes) || !ustart) return set_status(FEC_EINVAL, "fec_ragged_units: NULL argument");
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "8-byte descriptor words");
+    ragged_units(reinterpret_cast<const uint64_t*>(sizes), nstripes, reinterpret_cast<uint64_t*>(ustart));
+    return set_status(FEC_OK);
+}
+
+FEC_API int fec_encode_batch_ragged(const fec_t* code, const gf* src, size_t src_bytes, size_t src_block_stride,
+                                    const unsigned long long* src_offsets, gf* dst, size_t dst_bytes,
+                                    size_t dst_block_stride, const unsigned long long* dst_offsets,
+                                    const unsigned long long* sizes, const unsigned* block_nums,
+                                    size_t num_block_nums, size_t nstripes, void* stream, unsigned flags) {
+    const RaggedCall c{"fec_encode_batch_ragged", src,         src_bytes, src_block_stride, src_offsets, dst,
+                       dst_bytes,                 dst_block_stride, dst_offsets, sizes,     nstripes,    stream,
+                       flags};
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (ragged_null(c, block_nums, "block_nums")) return t_status;
+    if (num_block_nums == 0) return set_status(FEC_EINVAL, "%s: num_block_nums is 0", c.fn);
+    for (size_t i = 0; i < num_block_nums; ++i)
+        if (block_nums[i] >= code->n)
+            return set_status(FEC_EINVAL, "%s: block number %u out of range (n = %u)", c.fn, block_nums[i],
+                              unsigned(code->n));
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        const unsigned r = static_cast<unsigned>(num_block_nums);
+        int ddev = -1;
+        if (check_ragged(c, code->k, r, &ddev)) return t_status;
+        if (!gpu_available()) return no_gpu();
+        return run_ragged(c, code, encode_rows(code, block_nums, num_block_nums), r, ddev);
+    });
+}
+
+FEC_API int fec_decode_batch_ragged(const fec_t* code, const gf* src, size_t src_bytes, size_t src_block_stride,
+                                    const unsigned long long* src_offsets, gf* dst, size_t dst_bytes,
+                                    size_t dst_block_stride, const unsigned long long* dst_offsets,
+                                    const unsigned long long* sizes, const unsigned* index, size_t nstripes,
+                                    void* stream, unsigned flags) {
+    const RaggedCall c{"fec_decode_batch_ragged", src,         src_bytes, src_block_stride, src_offsets, dst,
+                       dst_bytes,                 dst_block_stride, dst_offsets, sizes,     nstripes,    stream,
+                       flags};
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (ragged_null(c, index, "index")) return t_status;
+    return guarded([&] {
+        thread_local std::vector<uint8_t> rows;
+        unsigned r = 0;
+        if (decode_rows(code, index, rows, r, (flags & FEC_FLAG_ALL_PRIMARIES) != 0)) {
+            const std::string msg = t_msg;  // fec_decode_batch's checks, named as this call's
+            return set_status(t_status, "%s: %s", c.fn, msg.c_str());
+        }
+        if (nstripes == 0) return set_status(FEC_OK);
+        int ddev = -1;
+        if (check_ragged(c, code->k, r, &ddev)) return t_status;
+        if (r == 0) return set_status(FEC_OK);  // no primary is missing: nothing to recover
+        if (!gpu_available()) return no_gpu();
+        return run_ragged(c, code, rows.data(), r, ddev);
+    });
+}
+
 // ---- batched decode, a pattern per stripe ------------------------------------------
 namespace {
 // A pattern's k block numbers: each < n, all distinct.  `p`: its number, for the message.

@@ -22,6 +22,11 @@
 //   matapply_rows<K, R> the same arithmetic, one wave per stripe of short blocks.
 //   matapply_mixed<K>   the same arithmetic, K outputs, each stripe's tables picked
 //                       by its pattern id from a device-side table (scalar loads).
+//   matapply_ragged<K, R> the same arithmetic, every stripe its own size: a wave walks
+//                       a short range of 1 KiB units, finds its stripe by a search
+//                       over their prefix sum (ragged_scan writes it for device-side
+//                       sizes) and reads sizes and offsets by scalar loads
+//                       (fec_encode_batch_ragged / fec_decode_batch_ragged).
 //   matverify_reg<K, R> the same arithmetic, nothing stored: the R rows are compared
 //                       with the stored check blocks and only mismatch bits are
 //                       OR-ed out (fec_verify_batch); rows_differ compares rows
@@ -830,6 +835,268 @@ __global__ __launch_bounds__(kBlock) void matapply_mixed(const MixedJob<K> job) 
         if (w >= job.wps) {
             w -= job.wps;
             ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// matapply_ragged<K, R>: a batch whose stripes each have their own size
+// (fec_encode_batch_ragged / fec_decode_batch_ragged), k <= 4, up to 8 rows
+// per launch, one matrix for all stripes (its tables in the argument block, as
+// RegJob).  A unit is one wave step of one stripe -- 64 lanes x 16 bytes of
+// every block -- so stripe s has ceil(sizes[s] / 1024) units and ustart is
+// their exclusive prefix sum, ustart[nstripes] the total T.
+//
+// The launch has G waves; wave g owns the contiguous units [g*q + min(g, e),
+// ...) with q = T / G, e = T % G (the shard_range rule).  It finds its first
+// stripe by one binary search over ustart (the last s with ustart[s] <= first,
+// which skips zero-size stripes) and walks forward: per stripe it reads the
+// size and the two offsets once, tests that the stripe fits both arenas
+// (ragged_fits; a stripe that does not is neither read nor written), and makes
+// the stripe's wave steps, unit w covering chunks w*64 + lane with
+// chunk_span's overlapped last chunk.  The next stripe's descriptor is
+// requested before the current stripe's units are computed.  Everything about
+// a stripe is the same in every lane: it is formed through readfirstlane and
+// read through constant-address-space pointers (scalar loads), as in
+// matapply_mixed.  ustart, sizes and offsets are written before the launch (a
+// copy, ragged_scan or the caller's earlier work in the stream), never by this
+// kernel.  All byte addresses are 64-bit.
+// ---------------------------------------------------------------------------
+template <int K, int R>
+struct alignas(16) RaggedJob {
+    uint64_t in_bstride, out_bstride;  // 0: the stripe's own size (packed objects)
+    uint64_t in_bytes, out_bytes;      // extents of the two arenas
+    uint32_t nstripes;
+    uint32_t rows_all;  // output rows of the whole call (the fit test)
+    uint32_t row0;      // this launch stores rows row0 .. row0 + R of them
+    uint32_t pad_;
+    const uint64_t* ustart;  // nstripes + 1
+    const uint64_t* sizes;
+    const uint64_t* in_off;
+    const uint64_t* out_off;
+    const uint8_t* in;
+    uint8_t* out;
+    uint32_t tab[K * R * 5];
+};
+
+typedef const __attribute__((address_space(4))) uint64_t* CU64;
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
+    return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+struct RaggedStripe {
+    uint64_t u0, u1;  // its units: [u0, u1)
+    uint64_t sz, ioff, ooff;
+};
+
+template <class J>
+__device__ __forceinline__ RaggedStripe ragged_stripe(const J& job, uint32_t s) {
+    const CU64 us = (CU64)job.ustart;
+    return RaggedStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.in_off)[s], ((CU64)job.out_off)[s]};
+}
+
+// chunk_span<kChunk, true> with a 64-bit chunk number (a stripe is not bounded
+// by 2^32 chunks here: its size is whatever the descriptor says).
+__device__ __forceinline__ Span ragged_span(uint64_t c, uint64_t sz, uint64_t nfull) {
+    const uint64_t off = c * kChunk;
+    if (c < nfull) return Span{off, true, kChunk};
+    if (sz >= kChunk) return Span{sz - kChunk, true, kChunk};
+    return Span{off, false, static_cast<uint32_t>(sz - off)};
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matapply_ragged(const RaggedJob<K, R> job) {
+    using J = RaggedJob<K, R>;
+    // each row's tables are read where they are used: the walk's own wave-uniform
+    // state (two descriptors, the range, the stripe's bases) takes some 50 SGPRs,
+    // so the threshold is lower than reg_argload's
+    constexpr bool AL = K * R * 5 >= 15;
+    Tab T[R][K];
+    if constexpr (!AL) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const uint32_t* t = &job.tab[(r * K + j) * 5];
+                T[r][j] = Tab{t[0], t[1], t[2], t[3], t[4]};
+            }
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t G = gridDim.x * (kBlock / 64);
+    const CU64 us = (CU64)job.ustart;
+    const uint32_t ns = job.nstripes;
+    const uint64_t total = us[ns];
+    // (a launch with a wave per unit or more needs no division)
+    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
+    uint64_t u = uniform64(g * q + (g < e ? g : e));
+    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
+    if (u >= end) return;
+    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (us[mid] <= u)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
+    RaggedStripe cur = ragged_stripe(job, s);
+    for (;;) {
+        RaggedStripe nxt = cur;
+        if (s + 1 < ns) nxt = ragged_stripe(job, s + 1);
+        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+        const uint64_t sz = cur.sz;
+        const uint64_t ib = job.in_bstride ? job.in_bstride : sz, ob = job.out_bstride ? job.out_bstride : sz;
+        if (u < stop && ragged_fits(cur.ioff, ib, K, sz, job.in_bytes) &&
+            ragged_fits(cur.ooff, ob, job.rows_all, sz, job.out_bytes)) {
+            const uint8_t* const in0 = job.in + cur.ioff;
+            uint8_t* const out0 = job.out + cur.ooff + job.row0 * ob;
+            const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
+            for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
+                const uint64_t c = w * 64u + lane;
+                const bool live = c < cps;
+                const Span sp = ragged_span(c, sz, nfull);
+                u32x4 x[K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+                if (live) {
+                    if (sp.full) {
+#pragma unroll
+                        for (int j = 0; j < K; ++j) x[j] = load16(in0 + j * ib + sp.off);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < K; ++j) x[j] = load_tail(in0 + j * ib + sp.off, sp.nb);
+                    }
+                }
+                Sel sel[4][K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    sel[0][j] = selectors(x[j].x);
+                    sel[1][j] = selectors(x[j].y);
+                    sel[2][j] = selectors(x[j].z);
+                    sel[3][j] = selectors(x[j].w);
+                }
+                // the row address advances per lane: R wave-uniform row bases would
+                // live across the unit loop in SGPRs the walk has no room for
+                uint8_t* orow = out0 + sp.off;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    Tab t[K];
+                    if constexpr (AL) {
+                        const KPtr<J> kj = kernarg_job<J>();
+#pragma unroll
+                        for (int j = 0; j < K; ++j) {
+                            const uint32_t i = (r * K + j) * 5;
+                            t[j] = Tab{kj->tab[i], kj->tab[i + 1], kj->tab[i + 2], kj->tab[i + 3], kj->tab[i + 4]};
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < K; ++j) t[j] = T[r][j];
+                    }
+                    const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]),
+                                  gf_dot<K>(t, sel[3])};
+                    if (live) {
+                        if (sp.full)
+                            store16_pol<0>(orow, y);
+                        else
+                            store_tail(orow, y, sp.nb);
+                    }
+                    orow += ob;
+                }
+            }
+        }
+        u = stop;
+        if (u >= end || s + 1 >= ns) break;
+        ++s;
+        cur = nxt;
+        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
+            ++s;
+            cur = ragged_stripe(job, s);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// ragged_scan: ustart[0 .. n] from sizes[0 .. n) in device memory, for a
+// ragged call whose descriptor arrays the host cannot read.  Three launches
+// over tiles of kScanTile sizes: each workgroup sums its tile; one workgroup
+// turns the tile sums into their exclusive prefix and writes the total to
+// ustart[n]; each workgroup scans its tile again from its prefix.  A size
+// larger than `maxsz` (the smaller arena: such a stripe fits neither) counts no
+// units.  Plain vector stores: matapply_ragged, a later kernel of the stream,
+// reads what these wrote through the scalar cache, which starts every kernel
+// empty.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kScanPer = 16, kScanTile = kBlock * kScanPer;
+
+struct ScanJob {
+    const uint64_t* sizes;
+    uint64_t* ustart;  // n + 1
+    uint64_t* tsum;    // one per tile
+    uint64_t n, maxsz;
+    uint32_t ntiles, pad_;
+};
+
+// Exclusive prefix of v over the workgroup's threads; *total: the sum.
+__device__ inline uint64_t scan_block(uint64_t v, uint64_t* total) {
+    __shared__ uint64_t sh[kBlock];
+    const uint32_t t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < kBlock; d <<= 1) {
+        const uint64_t add = t >= d ? sh[t - d] : 0;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    const uint64_t incl = sh[t];
+    *total = sh[kBlock - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__device__ __forceinline__ uint64_t scan_units(const ScanJob& job, uint64_t i) {
+    const uint64_t sz = job.sizes[i];
+    return sz > job.maxsz ? 0 : ragged_units_of(sz);
+}
+
+// PHASE 0: tile sums; 1: their prefix (one workgroup); 2: ustart
+template <int PHASE>
+__global__ __launch_bounds__(kBlock) void ragged_scan(const ScanJob job) {
+    if constexpr (PHASE == 1) {
+        uint64_t carry = 0;
+        for (uint32_t base = 0; base < job.ntiles; base += kBlock) {
+            const uint32_t i = base + threadIdx.x;
+            const uint64_t v = i < job.ntiles ? job.tsum[i] : 0;
+            uint64_t total;
+            const uint64_t ex = scan_block(v, &total);
+            if (i < job.ntiles) job.tsum[i] = carry + ex;
+            carry += total;
+        }
+        if (threadIdx.x == 0) job.ustart[job.n] = carry;
+    } else {
+        const uint64_t i0 = (uint64_t(blockIdx.x) * kBlock + threadIdx.x) * kScanPer;
+        uint64_t v[kScanPer], sum = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kScanPer; ++i) {
+            v[i] = i0 + i < job.n ? scan_units(job, i0 + i) : 0;
+            sum += v[i];
+        }
+        uint64_t total;
+        uint64_t at = scan_block(sum, &total);
+        if constexpr (PHASE == 0) {
+            if (threadIdx.x == 0) job.tsum[blockIdx.x] = total;
+        } else {
+            at += job.tsum[blockIdx.x];
+#pragma unroll
+            for (uint32_t i = 0; i < kScanPer; ++i) {
+                if (i0 + i < job.n) job.ustart[i0 + i] = at;
+                at += v[i];
+            }
         }
     }
 }
@@ -4648,6 +4915,127 @@ hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
     return e;
 }
 
+// ---- matapply_ragged dispatch ---------------------------------------------------------
+// The grid of matapply_ragged: a wave per unit where a unit moves 10 KiB or more
+// (k + r >= 10: the K=3/M=10 encode), else the fewest units per wave that do --
+// two for that code's two-row decode.  Measured on 10^6 stripes of 4 KiB against
+// the uniform call (profiles/ragged_bench.json): the
+// encode 0.96 x with one unit per wave, 1.00 with two, 1.02 with four and 1.05
+// with 122 (a grid of 32 workgroups per CU); the decode 1.25 x with one, 0.95
+// with two, 1.02 with four.  Short ranges keep neighbouring waves on
+// neighbouring KiBs, as the grid-stride walk of the other kernels does; a wave
+// that moves too little cannot hide its one search over ustart.  The cap is the
+// unit kernels' (CUs x 8192 workgroups); past it the ranges lengthen.
+constexpr uint64_t kRaggedGridPerCu = kGridPerCu;
+constexpr uint32_t kRaggedWaveKiB = 10;
+constexpr uint64_t ragged_units_per_wave(uint32_t k, uint32_t r) { return (kRaggedWaveKiB + k + r - 1) / (k + r); }
+
+// The four descriptor arrays in device memory.
+struct RaggedDev {
+    const uint64_t *ustart, *sizes, *in_off, *out_off;
+};
+
+const KrNames g_ragged_names("matapply_ragged");
+
+// Rows [g0, g0 + R) of every stripe.
+struct RaggedKr {
+    template <int K, int R>
+    static hipError_t launch(const RaggedSpec& p, const RaggedDev& d, uint32_t g0, uint32_t grid,
+                             hipStream_t stream) {
+        RaggedJob<K, R> job;
+        job.in_bstride = p.in_bstride;
+        job.out_bstride = p.out_bstride;
+        job.in_bytes = p.in_bytes;
+        job.out_bytes = p.out_bytes;
+        job.nstripes = static_cast<uint32_t>(p.nstripes);
+        job.rows_all = p.r;
+        job.row0 = g0;
+        job.pad_ = 0;
+        job.ustart = d.ustart;
+        job.sizes = d.sizes;
+        job.in_off = d.in_off;
+        job.out_off = d.out_off;
+        job.in = p.in;
+        job.out = p.out;
+        for (int i = 0; i < R * K; ++i) host_tab(&job.tab[i * 5], p.coef[size_t(g0) * K + i]);
+        const hipError_t e =
+            launch_job(reinterpret_cast<const void*>(matapply_ragged<K, R>), grid, kBlock, 0, stream, job);
+        if (e == hipSuccess) t_last_kernel = g_ragged_names.name[K][R];
+        return e;
+    }
+};
+constexpr KrTable<RaggedKr> g_ragged_launch;
+
+// ustart of device-side sizes into `ustart` (n + 1 words) with `tsum` (one word
+// per tile) as scratch, both device memory: the three phases of ragged_scan.
+hipError_t launch_ragged_scan(const uint64_t* sizes, uint64_t n, uint64_t maxsz, uint64_t* ustart, uint64_t* tsum,
+                              hipStream_t stream) {
+    ScanJob job;
+    job.sizes = sizes;
+    job.ustart = ustart;
+    job.tsum = tsum;
+    job.n = n;
+    job.maxsz = maxsz;
+    job.ntiles = static_cast<uint32_t>((n + kScanTile - 1) / kScanTile);
+    job.pad_ = 0;
+    hipError_t e = launch_job(reinterpret_cast<const void*>(ragged_scan<0>), job.ntiles, kBlock, 0, stream, job);
+    if (e == hipSuccess) e = launch_job(reinterpret_cast<const void*>(ragged_scan<1>), 1, kBlock, 0, stream, job);
+    if (e == hipSuccess)
+        e = launch_job(reinterpret_cast<const void*>(ragged_scan<2>), job.ntiles, kBlock, 0, stream, job);
+    return e;
+}
+
+hipError_t launch_ragged_all(const RaggedSpec& p, hipStream_t stream) {
+    const uint64_t ns = p.nstripes;
+    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
+    StagedUpload up;
+    RaggedDev d;
+    hipError_t e;
+    uint64_t units;  // of the whole call, or (device arrays) a bound on them
+    if (p.desc_host) {
+        // [ustart | sizes | in_off | out_off] by one copy
+        const size_t bytes = (4 * ns + 1) * sizeof(uint64_t);
+        if ((e = up.acquire(bytes)) != hipSuccess) return e;
+        uint64_t* h = reinterpret_cast<uint64_t*>(up.host());
+        const uint64_t total = ragged_units(p.sizes, ns, h);
+        if (!total) return hipSuccess;  // every stripe is empty: nothing copied, nothing launched
+        std::memcpy(h + ns + 1, p.sizes, ns * sizeof(uint64_t));
+        std::memcpy(h + 2 * ns + 1, p.in_off, ns * sizeof(uint64_t));
+        std::memcpy(h + 3 * ns + 1, p.out_off, ns * sizeof(uint64_t));
+        if ((e = up.copy(bytes, stream)) != hipSuccess) return e;
+        const uint64_t* dv = reinterpret_cast<const uint64_t*>(up.dev());
+        d = RaggedDev{dv, dv + ns + 1, dv + 2 * ns + 1, dv + 3 * ns + 1};
+        units = total;
+    } else {
+        // the total is not known here; it only sizes the grid, so an estimate
+        // serves: blocks do not overlap, so the sizes sum to at most either arena
+        // over its rows.  The rounding of each stripe's last unit is left out: a
+        // total above the estimate lengthens the ranges a little, one below it
+        // leaves waves with less than their share (or nothing: they exit), which
+        // is what a narrow shape cannot afford (ragged_units_per_wave).
+        const uint64_t in_units = p.in_bytes / (p.in_bstride ? 1 : p.k) / kRaggedUnit;
+        const uint64_t out_units = p.out_bytes / (p.out_bstride ? 1 : p.r) / kRaggedUnit;
+        units = std::max<uint64_t>(1, std::min(in_units, out_units));
+        const uint64_t ntiles = (ns + kScanTile - 1) / kScanTile;
+        if ((e = up.acquire((ns + 1 + ntiles) * sizeof(uint64_t))) != hipSuccess) return e;
+        uint64_t* dv = reinterpret_cast<uint64_t*>(up.slot->dev);
+        e = launch_ragged_scan(p.sizes, ns, p.in_bytes < p.out_bytes ? p.in_bytes : p.out_bytes, dv, dv + ns + 1,
+                               stream);
+        if (e != hipSuccess) {
+            up.done(stream);
+            return e;
+        }
+        d = RaggedDev{dv, p.sizes, p.in_off, p.out_off};
+    }
+    for (uint32_t g0 = 0; g0 < p.r && e == hipSuccess; g0 += kRegR) {
+        const uint32_t rg = std::min<uint32_t>(kRegR, p.r - g0);
+        const uint64_t per_wg = ragged_units_per_wave(p.k, rg) * (kBlock / 64), need = (units + per_wg - 1) / per_wg;
+        e = g_ragged_launch(p.k, rg)(p, d, g0, static_cast<uint32_t>(need < cap ? need : cap), stream);
+    }
+    up.done(stream);
+    return e;
+}
+
 // ---- mix form of the run-time-data bit-sliced kernels (4 < k <= 32) ------------------
 // Waves (row tiles) per unit from r alone -- not from the size of the call as
 // bsr_tiles -- so that a record serves every call: one wave for r <= 10, 2 for
@@ -5175,6 +5563,16 @@ hipError_t launch_mixed(const MixedSpec& m, hipStream_t stream) {
     case 3: return launch_mixed_k<3>(m, stream);
     default: return launch_mixed_k<4>(m, stream);
     }
+}
+
+hipError_t launch_ragged(const RaggedSpec& g, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (g.k < 1 || g.k > static_cast<uint32_t>(kRegK) || g.r < 1 || g.r > 256 || !g.coef || !g.in || !g.out ||
+        !g.sizes || !g.in_off || !g.out_off || g.nstripes == 0 || g.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    return launch_ragged_all(g, stream);
 }
 
 int generic_mode() {

@@ -302,6 +302,63 @@ hipError_t launch_locate2_finish(const uint32_t* bits, uint32_t words, uint32_t 
                                  uint32_t* culprit, uint32_t* list, uint32_t* pairbits, hipStream_t stream);
 hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream);
 
+// A batched encode or decode whose stripes each have their own size
+// (matapply_ragged<K, R>, k <= 4; fec_encode_batch_ragged / fec_decode_batch_ragged).
+// Stripe s has blocks of sizes[s] bytes: input j at in + in_off[s] + j * B, output
+// row i at out + out_off[s] + i * B', with B = in_bstride, or sizes[s] when that
+// is 0 (packed objects), and B' from out_bstride likewise.  All stripes share
+// the r x k matrix `coef`; more than 8 rows run as row groups of at most 8 over
+// one staging.  A stripe is read and written only where it FITS both arenas:
+// off + (rows - 1) * B + size <= bytes (ragged_fits), tested by the kernel per
+// stripe; zero-size stripes are neither read nor written.
+//
+// A unit is one wave step, 64 lanes x kChunk bytes of every block: stripe s has
+// ragged_units_of(sizes[s]) of them, and ustart (ragged_units) is their
+// exclusive prefix sum.  With desc_host the three arrays are host memory: the
+// host computes ustart and uploads all four arrays by one staged copy.
+// Otherwise they are device memory, read where they are, and ragged_scan
+// writes ustart into the staging slot's device half in stream order; there a
+// size that exceeds either arena counts no units.  Both forms use a staging
+// slot, so the call declines under graph capture (hipErrorNotSupported).
+// hipErrorInvalidValue for other shapes (k > 4: the caller cuts runs).
+constexpr uint32_t kRaggedUnit = 64 * kChunk;
+__host__ __device__ inline uint64_t ragged_units_of(uint64_t sz) {
+    return sz / kRaggedUnit + (sz % kRaggedUnit != 0);
+}
+// ustart[0 .. n] from sizes[0 .. n); returns the total
+inline uint64_t ragged_units(const uint64_t* sizes, uint64_t n, uint64_t* ustart) {
+    uint64_t t = 0;
+    for (uint64_t s = 0; s < n; ++s) {
+        ustart[s] = t;
+        t += ragged_units_of(sizes[s]);
+    }
+    ustart[n] = t;
+    return t;
+}
+// off + (rows - 1) * stride + sz <= bytes, evaluated without wrapping (rows <= 2^32)
+__host__ __device__ inline bool ragged_fits(uint64_t off, uint64_t stride, uint32_t rows, uint64_t sz,
+                                            uint64_t bytes) {
+    if (rows == 0) return true;  // nothing is read or written on this side
+    if (sz > bytes || off > bytes - sz) return false;
+    if (rows == 1) return true;
+    const uint64_t room = bytes - sz - off, m = rows - 1;
+    if (stride > room) return false;
+    const uint64_t hi = (stride >> 32) * m + (((stride & 0xFFFFFFFFull) * m) >> 32);  // bits 32.. of the product
+    return (hi >> 32) == 0 && stride * m <= room;
+}
+struct RaggedSpec {
+    uint32_t k, r;
+    const uint8_t* coef;  // r x k coefficients, row-major (host memory)
+    const uint8_t* in;    // the two arenas, kernel-visible addresses
+    uint8_t* out;
+    uint64_t in_bytes, out_bytes;
+    uint64_t in_bstride, out_bstride;
+    const uint64_t *sizes, *in_off, *out_off;  // nstripes each
+    bool desc_host;
+    uint64_t nstripes;
+};
+hipError_t launch_ragged(const RaggedSpec& g, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
