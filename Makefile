@@ -69,6 +69,21 @@ asan: build/address/driver
 tsan: build/thread/driver
 	TSAN_OPTIONS="halt_on_error=0 second_deadlock_stack=1" ./build/thread/driver
 
+# The validation path of the ragged scrub calls (fec_verify_batch_ragged,
+# fec_locate_batch_ragged) under AddressSanitizer and UndefinedBehaviorSanitizer:
+# a stand-alone program, tests/c/ragged_scrub_validate.cpp, over the same host
+# objects; no GPU needed.
+SCRUBSAN := $(filter-out tests/c/sanitize_driver.cpp,$(SANSRC)) tests/c/ragged_scrub_validate.cpp
+
+build/scrub/validate: $(SCRUBSAN) $(SRC)/*.hpp include/zfec_hip.h
+	mkdir -p build/scrub
+	set -e; for f in $(SCRUBSAN); do \
+	  $(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=address,undefined -c $$f -o build/scrub/$$(basename $$f).o; done
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -fno-gpu-sanitize -o $@ build/scrub/*.o -ldl -lpthread
+
+asan-scrub: build/scrub/validate
+	ASAN_OPTIONS=detect_leaks=0 ./build/scrub/validate
+
 # The no-GPU Python tests of the C-ABI (tests/test_cpu_surface.py: validation,
 # JIT registry from threads) against an AddressSanitizer build of the library,
 # loaded through zfec_amd.capi (ZFEC_HIP_LIB) with the ASan runtime preloaded.
@@ -89,4 +104,4 @@ clean:
 	rm -f $(SRC)/*.o $(LIB) $(PYEXT)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle ref clean asan tsan asan-py
+.PHONY: all oracle ref clean asan tsan asan-py asan-scrub

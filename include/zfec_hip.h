@@ -421,6 +421,89 @@ int fec_locate_batch(const fec_t* code,
  * FEC_OK / FEC_EINVAL / FEC_ESINGULAR. */
 int fec_locate_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows);
 
+/* Ragged scrub: fec_verify_batch and fec_locate_batch over stripes that each
+ * have their own size (the arena of fec_encode_batch_ragged), in one launch.
+ *
+ * Stripe s holds nb = num_block_nums blocks of sizes[s] bytes; slot j starts at
+ * src + src_offsets[s] + j*B, with B = src_block_stride when that is nonzero and
+ * B = sizes[s] otherwise: the packed object [slot 0 | ... | slot nb-1].  A
+ * nonzero stride describes block-major arenas.  Offsets are arbitrary bytes.
+ * block_nums means exactly what it means to fec_verify_batch: nb distinct
+ * numbers below n in any order, the first k slots the basis, the other
+ * c = nb - k the checks.
+ *
+ * The results are those of the uniform calls made once per stripe with
+ * nstripes = 1 and sz = sizes[s]: fec_verify_batch_ragged returns W =
+ * ceil(c/32) words per stripe in mismatch[s*W ..], bit i set iff check i
+ * differs somewhere and every other bit 0; fec_locate_batch_ragged one verdict
+ * word per stripe by rules 1-5 of fec_locate_batch.  A zero-size stripe is
+ * neither read nor judged dirty: its words are 0, its verdict
+ * FEC_LOCATE_CLEAN.  The library clears the result words itself, in stream
+ * order.  src is never written, and nothing in caller memory outside the
+ * result words is.
+ *
+ * sizes and src_offsets are two arrays of nstripes 8-byte words (8-byte
+ * aligned), both in host memory or both in device memory on the blocks'
+ * device; a mix returns FEC_EINVAL.  Host arrays are copied when the call is
+ * made and may be reused when it returns; device arrays are read where they
+ * are, in stream order, and nothing synchronises the stream.
+ *
+ * src_bytes is the extent of the arena.  A stripe with sizes[s] > 0 FITS when
+ * offset + (nb - 1)*B + sizes[s] <= src_bytes, evaluated without wrapping.
+ * With host arrays a stripe that does not fit is FEC_EINVAL, the message naming
+ * the stripe.  With device arrays such a stripe is not read and the result
+ * MARKS it: fec_verify_batch_ragged sets all c check bits of the stripe (a
+ * scrub must not vouch for what it did not read), fec_locate_batch_ragged
+ * writes FEC_LOCATE_UNFIT; no error is returned.  This departs on purpose
+ * from the "left untouched" rule of the writing ragged calls: there untouched
+ * output is the safe outcome, here a cleared word would read as "clean".
+ *
+ * src is device memory on one device, or page-locked host memory read in
+ * place; pageable host memory returns FEC_EINVAL.  mismatch / culprit in device
+ * memory is used in place and FEC_FLAG_ASYNC is honoured; in host memory it is
+ * gathered in device words the library owns and copied back, and the call is
+ * synchronous.  Every atomic aims at device memory the library owns or at the
+ * caller's device-side mismatch words, never at host memory.
+ * FEC_FLAG_LIBRARY_STREAM as elsewhere; FEC_FLAG_ROW_PADDING is accepted and
+ * ignored.  While the stream is being captured into a graph the call returns
+ * FEC_EINVAL.
+ *
+ * Checked before any GPU work, in this order, each FEC_EINVAL with a message
+ * naming the call: an invalid fec_t; a NULL src, sizes, src_offsets,
+ * block_nums or mismatch / culprit; nb <= k ("nothing to check"); nb > n; a
+ * block number >= n; a duplicate; nstripes >= 2^32; descriptor arrays of mixed
+ * memory kinds; with host arrays a stripe that does not fit.  Then FEC_ENODEV
+ * when no GPU is visible.  nstripes == 0 returns FEC_OK.
+ *
+ * k <= 4 runs matverify_ragged<k,r> (one launch per 8 checks) or, with
+ * 2 <= c <= 8, matlocate_ragged<k,c>: matapply_ragged's walk around the unit
+ * of matverify_reg / matlocate_reg, the bits accumulated per (wave, stripe) and
+ * OR-ed out once where nonzero, so clean data performs no store and no atomic;
+ * locate_finish forms the verdicts after the launch.  c == 1 locates with
+ * matverify_ragged (FEC_LOCATE_UNKNOWN for a dirty stripe).  With device
+ * arrays ragged_scan and a one-lane-per-stripe marking kernel run in the same
+ * stream.  Other shapes (k > 4; a location with c > 8) are cut into runs of
+ * consecutive stripes of one size whose offset advances by a constant, each
+ * run one fec_verify_batch / fec_locate_batch-style launch (at worst one per
+ * stripe); on that path device-side arrays are first copied to the host, which
+ * SYNCHRONISES the stream.  fec_last_kernel_name() names the kernel that read
+ * the blocks last. */
+#define FEC_LOCATE_UNFIT   0xFFFFFFFBu
+int fec_verify_batch_ragged(const fec_t* code,
+                            const gf* src, size_t src_bytes, size_t src_block_stride,
+                            const unsigned long long* src_offsets,
+                            const unsigned long long* sizes,
+                            const unsigned* block_nums, size_t num_block_nums,
+                            size_t nstripes,
+                            unsigned* mismatch, void* stream, unsigned flags);
+int fec_locate_batch_ragged(const fec_t* code,
+                            const gf* src, size_t src_bytes, size_t src_block_stride,
+                            const unsigned long long* src_offsets,
+                            const unsigned long long* sizes,
+                            const unsigned* block_nums, size_t num_block_nums,
+                            size_t nstripes,
+                            unsigned* culprit, void* stream, unsigned flags);
+
 /* Batched in-place correction: scrub, locate and heal in ONE call.  The
  * arguments are exactly those of fec_locate_batch, except that `blocks` is
  * writable.  Over all sz bytes of each stripe:

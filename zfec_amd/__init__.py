@@ -24,13 +24,15 @@ __version__ = "0.1.0"
 
 __all__ = ["Encoder", "Decoder", "RepairPlan", "Error", "easyfec", "filefec", "cmdline_zfec", "cmdline_zunfec", "test_from_agl",
            "device_count", "version", "reuse_host_memory", "LOCATE_CLEAN", "LOCATE_MANY", "LOCATE_UNKNOWN",
-           "LOCATE_NONE"]
+           "LOCATE_NONE", "LOCATE_UNFIT"]
 
 # Decoder.locate_batch verdicts that are not a slot: FEC_LOCATE_CLEAN / _MANY /
 # _UNKNOWN (include/zfec_hip.h) read as int32
 LOCATE_CLEAN, LOCATE_MANY, LOCATE_UNKNOWN = -1, -2, -3
 # Decoder.locate2_batch: the second word of a verdict that is no pair (FEC_LOCATE_NONE as int32)
 LOCATE_NONE = -4
+# Decoder.locate_ragged: a device-side descriptor that does not fit the data (FEC_LOCATE_UNFIT as int32)
+LOCATE_UNFIT = -5
 
 
 def _is_device_tensor(x):
@@ -940,6 +942,90 @@ class Decoder(_fec.Decoder):
             _capi_code(self).locate_batch(ptr, sbs, sss, nums, sz, ns, out.data_ptr(), stream=stream, flags=flags)
         return out
 
+    def verify_ragged(self, data, sizes, blocknums, offsets=None):
+        """verify_batch over stripes that each have their own size, in one
+        launch (fec_verify_batch_ragged).
+
+        data: 1-D contiguous uint8 device tensor, the arena; data.numel() is
+        its extent.  sizes: one block size per stripe, a 1-D int64 tensor (on
+        the data's device or the CPU) or a sequence of ints.  Stripe s is the
+        packed object of nb = len(blocknums) blocks of sizes[s] bytes from
+        data[offsets[s]], slot j holding block blocknums[j] (blocknums as in
+        verify_batch).  offsets defaults to nb * (cumsum(sizes) - sizes),
+        computed on the sizes' device.  Returns a torch.bool tensor
+        [nstripes, nb - k] on the data's device, as verify_batch does; a
+        zero-size stripe has no bit set.  With descriptors on the device
+        nothing synchronises with the host, and a stripe whose descriptor does
+        not fit the data is not read and has EVERY bit set; with descriptors
+        on the CPU such a stripe is an Error."""
+        import torch
+
+        nums, ns, szs, offs = self._ragged_scrub_args(data, sizes, blocknums, offsets)
+        c = len(nums) - self.k
+        words = (c + 31) // 32
+        if not ns:
+            return torch.zeros((0, c), dtype=torch.bool, device=data.device)
+        mask = torch.empty((ns, words), dtype=torch.int32, device=data.device)  # the library clears it
+        with torch.cuda.device(data.device), _as_error():
+            _capi_code(self).verify_batch_ragged(data.data_ptr(), data.numel(), 0, offs.data_ptr(), szs.data_ptr(),
+                                                 nums, ns, mask.data_ptr(), stream=_stream_handle(data.device))
+        shifts = torch.arange(32, dtype=torch.int32, device=data.device)
+        bits = (mask.unsqueeze(-1) >> shifts) & 1
+        return bits.reshape(ns, words * 32)[:, :c].ne(0)
+
+    def locate_ragged(self, data, sizes, blocknums, offsets=None):
+        """locate_batch over stripes that each have their own size, in one
+        launch (fec_locate_batch_ragged).
+
+        Arguments as verify_ragged.  Returns a torch.int32 tensor [nstripes]
+        on the data's device with locate_batch's verdicts; a zero-size stripe
+        is LOCATE_CLEAN, and with descriptors on the device a stripe whose
+        descriptor does not fit the data is not read and is LOCATE_UNFIT
+        (-5)."""
+        import torch
+
+        nums, ns, szs, offs = self._ragged_scrub_args(data, sizes, blocknums, offsets)
+        out = torch.empty((ns,), dtype=torch.int32, device=data.device)
+        if ns:
+            with torch.cuda.device(data.device), _as_error():
+                _capi_code(self).locate_batch_ragged(data.data_ptr(), data.numel(), 0, offs.data_ptr(), szs.data_ptr(),
+                                                     nums, ns, out.data_ptr(), stream=_stream_handle(data.device))
+        return out
+
+    def _ragged_scrub_args(self, data, sizes, blocknums, offsets):
+        """The preconditions of verify_ragged / locate_ragged; returns
+        (nums, nstripes, sizes, offsets), the two descriptor tensors on one device."""
+        import torch
+
+        nums = self._scrub_nums(blocknums)
+        if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1 \
+                or not data.is_contiguous():
+            raise Error("Precondition violation: data is required to be a 1-D contiguous uint8 device tensor")
+        sizes = _ragged_words(sizes, "sizes")
+        ns = sizes.numel()
+        if offsets is not None:
+            offsets = _ragged_words(offsets, "offsets")
+            if offsets.numel() != ns:
+                raise Error("Precondition violation: offsets is required to hold one word per stripe: %d, not %d"
+                            % (ns, offsets.numel()))
+            if offsets.device != sizes.device:
+                raise Error("Precondition violation: sizes and offsets are required to be both on the data's device "
+                            "or both on the CPU, but sizes is on %s and offsets on %s"
+                            % (sizes.device, offsets.device))
+        if sizes.is_cuda and sizes.device != data.device:
+            raise Error("Precondition violation: sizes and offsets are required to be both on the data's device or "
+                        "both on the CPU, but sizes is on %s and data on %s" % (sizes.device, data.device))
+        if not sizes.is_cuda:
+            for what, a in (("sizes", sizes), ("offsets", offsets)):
+                if a is not None and ns and int(a.min()) < 0:
+                    raise Error("Precondition violation: %s is required to hold sizes and offsets in [0, 2^63), but "
+                                "one was %d" % (what, int(a.min())))
+        if not _is_device_tensor(data):
+            raise Error("Precondition violation: data is required to be a uint8 tensor on a GPU")
+        if offsets is None:  # the packed object-major layout: stripe after stripe, a stripe's blocks back to back
+            offsets = len(nums) * (torch.cumsum(sizes, 0) - sizes)
+        return nums, ns, sizes, offsets
+
     def correct_batch(self, blocks, blocknums):
         """Scrub, locate and heal in place, in one call (fec_correct_batch).
 
@@ -1015,10 +1101,27 @@ class Decoder(_fec.Decoder):
         (nums, nb, nstripes, sz, block stride, stripe stride, address)."""
         import torch
 
-        k, m = self.k, self.m
         if _is_host_array(blocks):
             raise Error("Precondition violation: %s takes a device tensor; host (numpy) blocks are not "
                         "staged by this call" % what)
+        nums = self._scrub_nums(blocknums)
+        nb = len(nums)
+        is_tensor = type(blocks).__module__.startswith("torch") and hasattr(blocks, "data_ptr")
+        if not is_tensor or blocks.dtype != torch.uint8 or blocks.dim() != 3:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz]"
+                        % nb)
+        if blocks.shape[1] != nb:
+            raise Error("Precondition violation: blocks is required to hold %d blocks per stripe, not %d"
+                        % (nb, blocks.shape[1]))
+        if not blocks.is_cuda:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
+                        "not a host tensor" % nb)
+        ns, sz, sbs, sss, ptr = _batch_view(blocks, nb, "blocks")
+        return nums, nb, ns, sz, sbs, sss, ptr
+
+    def _scrub_nums(self, blocknums):
+        """The block numbers of a scrub call as a list: k + 1 to m distinct ints in [0, m-1]."""
+        k, m = self.k, self.m
         try:
             nums = list(blocknums)
         except TypeError:
@@ -1033,18 +1136,7 @@ class Decoder(_fec.Decoder):
                             "was %r" % (m - 1, x))
         if len(set(nums)) != nb:
             raise Error("Precondition violation: block nums are required to be distinct, but got %r" % (nums,))
-        is_tensor = type(blocks).__module__.startswith("torch") and hasattr(blocks, "data_ptr")
-        if not is_tensor or blocks.dtype != torch.uint8 or blocks.dim() != 3:
-            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz]"
-                        % nb)
-        if blocks.shape[1] != nb:
-            raise Error("Precondition violation: blocks is required to hold %d blocks per stripe, not %d"
-                        % (nb, blocks.shape[1]))
-        if not blocks.is_cuda:
-            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
-                        "not a host tensor" % nb)
-        ns, sz, sbs, sss, ptr = _batch_view(blocks, nb, "blocks")
-        return nums, nb, ns, sz, sbs, sss, ptr
+        return nums
 
     def _check_blocknums(self, blocknums):
         """Validated list of k block numbers (the reference's checks,

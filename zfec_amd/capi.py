@@ -77,9 +77,13 @@ SYMBOLS = [
     ("fec_encode_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _U]),
     ("fec_decode_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _P, _U]),
     ("fec_ragged_units", ctypes.c_int, [_P, _SZ, _P]),
+    ("fec_verify_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
+    ("fec_locate_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_LOCATE_NONE = 0xFFFFFFFC  # fec_locate2_batch: the second word of a verdict that is no pair
+FEC_LOCATE_UNFIT = 0xFFFFFFFB  # fec_locate_batch_ragged: a device-side descriptor that does not fit the arena
+LOCATE_UNFIT = -5  # the same as the int32 the Python methods return
 FEC_REPAIR_NONE = 0xFFFFFFFF  # a target slot its pattern does not use
 
 JIT_OFF, JIT_AUTO, JIT_FORCE = 0, 1, 2
@@ -368,6 +372,29 @@ class Code(object):
         _UNKNOWN."""
         st = lib().fec_locate_batch(self.ptr, src, sbs, sss, _nums(block_nums), len(block_nums), sz, nstripes,
                                     culprit_ptr or None, stream or None, flags)
+        if st:
+            check(st)
+
+    def verify_batch_ragged(self, src, src_bytes, sbs, src_offsets_ptr, sizes_ptr, block_nums, nstripes, mismatch_ptr,
+                            stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_verify_batch_ragged: verify_batch over stripes that each have
+        their own size; the two `_ptr` descriptor arguments are the addresses
+        of nstripes 8-byte words each, both in host or both in device memory,
+        which the caller keeps alive until the call returns."""
+        st = lib().fec_verify_batch_ragged(self.ptr, src, src_bytes, sbs, src_offsets_ptr or None, sizes_ptr or None,
+                                           _nums(block_nums), len(block_nums), nstripes, mismatch_ptr or None,
+                                           stream or None, flags)
+        if st:
+            check(st)
+
+    def locate_batch_ragged(self, src, src_bytes, sbs, src_offsets_ptr, sizes_ptr, block_nums, nstripes, culprit_ptr,
+                            stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_locate_batch_ragged: as verify_batch_ragged, with locate_batch's
+        verdict words (and FEC_LOCATE_UNFIT for a device-side descriptor that
+        does not fit)."""
+        st = lib().fec_locate_batch_ragged(self.ptr, src, src_bytes, sbs, src_offsets_ptr or None, sizes_ptr or None,
+                                           _nums(block_nums), len(block_nums), nstripes, culprit_ptr or None,
+                                           stream or None, flags)
         if st:
             check(st)
 

@@ -2399,6 +2399,253 @@ FEC_API int fec_locate_batch(const fec_t* code, const gf* src, size_t src_block_
     });
 }
 
+// ---- ragged scrub: verify and locate, a size per stripe --------------------------------------
+namespace {
+struct ScrubCall {
+    const char* fn;
+    bool locate;
+    const gf* src;
+    size_t src_bytes, sbs;
+    const unsigned long long* soff;
+    const unsigned long long* sizes;
+    const unsigned* nums;
+    size_t nb, nstripes;
+    unsigned* out;  // mismatch or culprit
+    void* stream;
+    unsigned flags;
+};
+
+bool scrub_stripe_fits(const ScrubCall& c, const unsigned long long* sizes, const unsigned long long* soff, size_t s) {
+    const uint64_t sz = sizes[s];
+    return ragged_fits(soff[s], c.sbs ? c.sbs : sz, static_cast<uint32_t>(c.nb), sz, c.src_bytes);
+}
+
+// Every check of a ragged scrub call that needs no GPU, in the header's order.
+// *ddev: the descriptor arrays' device, -1 host memory.
+int check_ragged_scrub(const fec_t* code, const ScrubCall& c, int* ddev) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "%s: invalid fec_t", c.fn);
+    const struct {
+        const void* p;
+        const char* name;
+    } args[] = {{c.src, "src"},
+                {c.sizes, "sizes"},
+                {c.soff, "src_offsets"},
+                {c.nums, "block_nums"},
+                {c.out, c.locate ? "culprit" : "mismatch"}};
+    for (const auto& a : args)
+        if (!a.p) return set_status(FEC_EINVAL, "%s: %s is NULL", c.fn, a.name);
+    if (check_verify_nums(code, c.nums, c.nb)) {
+        const std::string msg = t_msg;  // fec_verify_batch's checks, named as this call's
+        return set_status(t_status, "%s: %s", c.fn, msg.c_str());
+    }
+    if (uint64_t(c.nstripes) >= (1ull << 32))
+        return set_status(FEC_EINVAL, "%s: %zu stripes: a call takes fewer than 2^32", c.fn, c.nstripes);
+    int dv[2] = {-1, -1};
+    if (gpu_available() && c.nstripes) {
+        dv[0] = pointer_device(c.sizes);
+        dv[1] = pointer_device(c.soff);
+    }
+    if (dv[0] != dv[1])
+        return set_status(FEC_EINVAL, "%s: sizes and src_offsets are of mixed memory kinds: both in host memory, or "
+                                      "both in device memory on the blocks' device", c.fn);
+    *ddev = dv[0];
+    if (*ddev < 0)
+        for (size_t s = 0; s < c.nstripes; ++s)
+            if (c.sizes[s] && !scrub_stripe_fits(c, c.sizes, c.soff, s))
+                return set_status(FEC_EINVAL, "%s: stripe %zu does not fit src: offset %llu, %zu rows %llu apart, "
+                                              "size %llu, src_bytes %zu", c.fn, s, c.soff[s], c.nb,
+                                  static_cast<unsigned long long>(c.sbs ? c.sbs : c.sizes[s]), c.sizes[s],
+                                  c.src_bytes);
+    return FEC_OK;
+}
+
+// k <= 4 (a location: c <= 8): matverify_ragged / matlocate_ragged.  The
+// working words of a location, and a host-side result gathered behind them,
+// live in the thread's vmask buffer under run_verify's ev_verify ordering.
+int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int rdev, BatchMem& mem) {
+    const unsigned k = code->k, cc = static_cast<unsigned>(c.nb - k), cw = (cc + 31) / 32;
+    const unsigned words = c.locate ? cw + (k + 31) / 32 : cw, xbit = 32 * cw;
+    const size_t ns = c.nstripes;
+    const size_t work_bytes = ns * words * sizeof(uint32_t);
+    const size_t out_bytes = ns * (c.locate ? 1 : cw) * sizeof(uint32_t);
+    DevCtx* const d = mem.d;
+    hipStream_t st = mem.st;
+    hipError_t e;
+    VerifyOrder order{*d, st};
+    if (order.init()) return t_status;
+    const bool own = c.locate || rdev < 0;  // words the library owns are in use
+    if (own) {
+        if (order.acquire()) return t_status;
+        if (ensure_verify_buf(*d, d->vmask, d->vmask_cap, (c.locate ? work_bytes : 0) + (rdev < 0 ? out_bytes : 0)))
+            return t_status;
+    }
+    uint32_t* const vm = static_cast<uint32_t*>(d->vmask);
+    uint32_t* const bits = own ? vm : c.out;
+    uint32_t* const out = rdev >= 0 ? c.out : c.locate ? vm + ns * words : vm;
+    if ((e = hipMemsetAsync(bits, 0, work_bytes, st)) != hipSuccess)
+        return hip_fail(e, "hipMemsetAsync (result words)");
+    thread_local std::vector<uint8_t> P, Q;
+    P.resize(size_t(cc) * k);
+    Q.resize(size_t(cc) * k);
+    int rc = verify_rows(code, c.nums, c.nb, P.data());
+    const bool hyp = c.locate && cc >= 2;
+    if (!rc && hyp) locate_rows(P.data(), k, cc, Q.data());
+    const uint64_t* const sizes = reinterpret_cast<const uint64_t*>(c.sizes);
+    const uint64_t* const soff = reinterpret_cast<const uint64_t*>(c.soff);
+    const auto unfit = [&](unsigned checks, uint32_t* to) {
+        ++t_launches;
+        const hipError_t ue = launch_ragged_unfit(sizes, soff, ns, static_cast<uint32_t>(c.nb), c.sbs, c.src_bytes,
+                                                  checks, to, st);
+        return ue == hipSuccess ? int(FEC_OK) : hip_fail(ue, "launch_ragged_unfit");
+    };
+    // a verify's marks follow the clearing and precede the block kernel, which only ORs
+    if (!rc && !c.locate && ddev >= 0) rc = unfit(cc, bits);
+    if (!rc) {
+        RaggedScrubSpec g;
+        g.k = k;
+        g.c = cc;
+        g.P = P.data();
+        g.Q = hyp ? Q.data() : nullptr;
+        g.src = mem.z[0];
+        g.bytes = c.src_bytes;
+        g.bstride = c.sbs;
+        g.sizes = sizes;
+        g.off = soff;
+        g.desc_host = ddev < 0;
+        g.nstripes = ns;
+        g.bits = bits;
+        g.words = words;
+        g.xbit = xbit;
+        ++t_launches;
+        if ((e = launch_ragged_scrub(g, st)) != hipSuccess) rc = hip_fail(e, "launch_ragged_scrub");
+    }
+    if (!rc && c.locate) {
+        // the block-reading kernel stays fec_last_kernel_name()'s answer
+        ++t_launches;
+        if ((e = launch_locate_finish(bits, words, k, cc, ns, out, st)) != hipSuccess)
+            rc = hip_fail(e, "launch_locate_finish");
+        if (!rc && ddev >= 0) rc = unfit(0, out);  // overwrites the verdict of what was not read
+    }
+    if (!rc && rdev < 0 && (e = hipMemcpyAsync(c.out, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpyAsync D2H (result words)");
+    order.release();
+    if (rc) return rc;
+    if ((rdev < 0 || !(c.flags & FEC_FLAG_ASYNC)) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+
+// Every other shape: runs of consecutive stripes of one size whose offset
+// advances by a constant, each run one uniform verify / locate over the result
+// words at + s0 * W or + s0 (run_ragged's cut for wide codes).  Device-side
+// arrays are first copied to the host, which synchronises the stream.
+int run_ragged_scrub_runs(const fec_t* code, const ScrubCall& c, int ddev, int rdev, BatchMem& mem) {
+    const unsigned k = code->k, cc = static_cast<unsigned>(c.nb - k), cw = (cc + 31) / 32;
+    const size_t ns = c.nstripes, W = c.locate ? 1 : cw;
+    hipStream_t st = mem.st;
+    hipError_t e;
+    const unsigned long long *sizes = c.sizes, *soff = c.soff;
+    thread_local std::vector<unsigned long long> hd;
+    if (ddev >= 0) {
+        hd.resize(2 * ns);
+        const unsigned long long* from[2] = {c.sizes, c.soff};
+        for (int i = 0; i < 2; ++i)
+            if ((e = hipMemcpyAsync(&hd[i * ns], from[i], ns * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                    st)) != hipSuccess)
+                return hip_fail(e, "hipMemcpyAsync D2H (descriptor arrays)");
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+        sizes = hd.data();
+        soff = sizes + ns;
+    }
+    const auto live = [&](size_t s) { return sizes[s] && scrub_stripe_fits(c, sizes, soff, s); };
+    // every word cleared (a location: CLEAN), then the marks of what will not be read
+    const size_t out_bytes = ns * W * sizeof(uint32_t);
+    const int fill = c.locate ? 0xFF : 0;
+    if (rdev >= 0) {
+        if ((e = hipMemsetAsync(c.out, fill, out_bytes, st)) != hipSuccess)
+            return hip_fail(e, "hipMemsetAsync (result words)");
+        if (ddev >= 0) {
+            ++t_launches;
+            e = launch_ragged_unfit(reinterpret_cast<const uint64_t*>(c.sizes),
+                                    reinterpret_cast<const uint64_t*>(c.soff), ns, static_cast<uint32_t>(c.nb), c.sbs,
+                                    c.src_bytes, c.locate ? 0 : cc, c.out, st);
+            if (e != hipSuccess) return hip_fail(e, "launch_ragged_unfit");
+        }
+    } else {
+        std::memset(c.out, fill, out_bytes);
+        for (size_t s = 0; s < ns; ++s) {
+            if (!sizes[s] || live(s)) continue;
+            if (c.locate)
+                c.out[s] = FEC_LOCATE_UNFIT;
+            else
+                for (unsigned i = 0; i < cw; ++i)
+                    c.out[s * cw + i] = cc - 32 * i >= 32 ? ~0u : (1u << (cc - 32 * i)) - 1u;
+        }
+    }
+    const unsigned jf = (c.flags & FEC_FLAG_LIBRARY_STREAM) | FEC_FLAG_ASYNC;
+    for (size_t s0 = 0; s0 < ns;) {
+        if (!live(s0)) {  // empty, or (device-side arrays) it does not fit: not read
+            ++s0;
+            continue;
+        }
+        const size_t sz = sizes[s0];
+        size_t s1 = s0 + 1, dsrc = 0;
+        if (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s0] && live(s1)) {
+            dsrc = soff[s1] - soff[s0];
+            ++s1;
+            while (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s1 - 1] && soff[s1] - soff[s1 - 1] == dsrc && live(s1))
+                ++s1;
+        }
+        const size_t bs = c.sbs ? c.sbs : sz;
+        if (c.locate ? run_locate(code, c.src + soff[s0], bs, dsrc, c.nums, c.nb, sz, s1 - s0, c.out + s0, c.stream, jf,
+                                  c.fn)
+                     : run_verify(code, c.src + soff[s0], bs, dsrc, c.nums, c.nb, sz, s1 - s0, c.out + s0 * cw,
+                                  c.stream, jf))
+            return t_status;
+        s0 = s1;
+    }
+    if (!(c.flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+
+int ragged_scrub(const fec_t* code, const ScrubCall& c) {
+    int ddev = -1;
+    if (check_ragged_scrub(code, c, &ddev)) return t_status;
+    if (c.nstripes == 0) return set_status(FEC_OK);
+    if (!gpu_available()) return no_gpu();
+    const unsigned k = code->k, cc = static_cast<unsigned>(c.nb - k);
+    const char* const out_name = c.locate ? "culprit" : "mismatch";
+    const int rdev = pointer_device(c.out);
+    // device memory on one device, or page-locked host memory (read in place)
+    const BatchBuf buf = {c.src, c.src_bytes, "src"};
+    BatchMem mem;
+    if (resolve_batch(mem, c.fn, &buf, 1, out_name, rdev, c.stream, c.flags, kCaptureRagged)) return t_status;
+    if (ddev >= 0 && ddev != mem.dev)
+        return set_status(FEC_EINVAL, "%s: sizes lives on device %d, the blocks on device %d", c.fn, ddev, mem.dev);
+    if (k <= kMixedMaxK && (!c.locate || cc <= 8)) return run_ragged_scrub_fused(code, c, ddev, rdev, mem);
+    return run_ragged_scrub_runs(code, c, ddev, rdev, mem);
+}
+}  // namespace
+
+FEC_API int fec_verify_batch_ragged(const fec_t* code, const gf* src, size_t src_bytes, size_t src_block_stride,
+                                    const unsigned long long* src_offsets, const unsigned long long* sizes,
+                                    const unsigned* block_nums, size_t num_block_nums, size_t nstripes,
+                                    unsigned* mismatch, void* stream, unsigned flags) {
+    const ScrubCall c{"fec_verify_batch_ragged", false, src, src_bytes, src_block_stride, src_offsets, sizes,
+                      block_nums, num_block_nums, nstripes, mismatch, stream, flags};
+    return guarded([&] { return ragged_scrub(code, c); });
+}
+
+FEC_API int fec_locate_batch_ragged(const fec_t* code, const gf* src, size_t src_bytes, size_t src_block_stride,
+                                    const unsigned long long* src_offsets, const unsigned long long* sizes,
+                                    const unsigned* block_nums, size_t num_block_nums, size_t nstripes,
+                                    unsigned* culprit, void* stream, unsigned flags) {
+    const ScrubCall c{"fec_locate_batch_ragged", true, src, src_bytes, src_block_stride, src_offsets, sizes,
+                      block_nums, num_block_nums, nstripes, culprit, stream, flags};
+    return guarded([&] { return ragged_scrub(code, c); });
+}
+
 // ---- batched in-place correction: scrub, locate and heal in one call ------------------------
 FEC_API int fec_correct_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums, gf* rows) {
     return rows_from_P(code, block_nums, num_block_nums, rows, correct_rows);

@@ -36,6 +36,12 @@
 //                       explains them (fec_locate_batch); rows_locate does the
 //                       same past k = 4 or 8 checks, locate_finish turns each
 //                       stripe's bits into its verdict.
+//   matverify_ragged<K, R>, matlocate_ragged<K, R>
+//                       those two units inside matapply_ragged's walk: the bits of
+//                       a stripe are gathered per wave and OR-ed out once, and
+//                       ragged_unfit marks the stripes a device-side descriptor
+//                       put outside the arena (fec_verify_batch_ragged /
+//                       fec_locate_batch_ragged).
 //   pairs_locate        over the stripes locate2_finish listed as MANY: the c
 //                       syndromes in LDS, every pair of slots tested against
 //                       them (fec_locate2_batch); pairs_finish names the one
@@ -1699,6 +1705,261 @@ __global__ __launch_bounds__(kBlock) void locate_finish(const FinishJob job) {
     const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
     if (s >= job.nstripes) return;
     job.culprit[s] = finish_verdict(job.bits + size_t(s) * job.words, job.k, job.c);
+}
+
+// ---------------------------------------------------------------------------
+// matverify_ragged<K, R> / matlocate_ragged<K, R>: the scrub of a batch whose
+// stripes each have their own size (fec_verify_batch_ragged /
+// fec_locate_batch_ragged), k <= 4 and up to 8 checks per launch.  One body,
+// LOC choosing the family: the walk of matapply_ragged (1 KiB units, the
+// shard_range split of T over the launched waves, one binary search over
+// ustart, the stripe's size and offset by scalar loads with the next stripe's
+// requested early, the fit test, 64-bit addresses, ragged_span's overlapped
+// last chunk, the tail zero-filled on both sides) around the unit of
+// matverify_reg / matlocate_reg (the syndromes in registers; with LOC the k
+// hypotheses against the Q tables, read through the kernel-argument pointer
+// under the wave-uniform mask != 0 branch only).
+//
+// There is ONE base pointer: slot j of a stripe is base + off + j * B, so the
+// first check slot of a launch (K + bit0) is a number, not a pointer array.
+//
+// A wave walks several units of one stripe and several stripes in one range,
+// so mismatch and excluded bits are accumulated per (wave, stripe) in two
+// wave-uniform words, reset at every stripe boundary.  One lane ORs them into
+// the stripe's words once, when the wave leaves the stripe, and only if they
+// are nonzero: clean data performs no store and no atomic.  A stripe that
+// does not fit, or has no bytes, is not read and contributes no bit.  The
+// verdict of a stripe is formed after the launch from the OR over all waves
+// (locate_finish), never per wave: two waves that each saw another single
+// corrupt slot leave both slots' rivals excluded, which is MANY.
+// ---------------------------------------------------------------------------
+template <int K, int R, bool LOC>
+struct alignas(16) RaggedScrubJob {
+    uint64_t bstride;  // 0: the stripe's own size (packed objects)
+    uint64_t bytes;    // extent of the arena
+    uint32_t nstripes;
+    uint32_t slots;  // blocks per stripe of the whole call (the fit test)
+    uint32_t chk0;   // slot of this launch's first check row
+    uint32_t bit0;   // its bit index
+    uint32_t words;  // result (verify) or working (locate) words per stripe
+    uint32_t xbit;   // bit index of basis slot 0's excluded bit (locate)
+    const uint64_t* ustart;  // nstripes + 1
+    const uint64_t* sizes;
+    const uint64_t* off;
+    const uint8_t* src;
+    uint32_t* bits;
+    uint32_t tab[K * R * 5];                       // row i, input j at (i*K + j)*5
+    uint32_t qtab[LOC ? K * (R - 1) * 5 : 1];      // Q[r][j], r = 1..R-1, at ((r-1)*K + j)*5
+};
+
+struct ScrubStripe {
+    uint64_t u0, u1;  // its units: [u0, u1)
+    uint64_t sz, off;
+};
+
+template <class J>
+__device__ __forceinline__ ScrubStripe scrub_stripe(const J& job, uint32_t s) {
+    const CU64 us = (CU64)job.ustart;
+    return ScrubStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.off)[s]};
+}
+
+// The lane's address of the next slot.  The empty asm keeps it a per-lane
+// 64-bit add: left to itself the compiler may form multiples j * B as
+// wave-uniform values that live across the unit loop, in SGPRs the walk does
+// not have (matlocate_ragged<4,8> spilled two without it).
+__device__ __forceinline__ const uint8_t* next_row(const uint8_t* row, uint64_t B) {
+    row += B;
+    asm volatile("" : "+v"(row));
+    return row;
+}
+
+template <int K, int R, bool LOC>
+__device__ __forceinline__ void scrub_ragged_body(const RaggedScrubJob<K, R, LOC>& job) {
+    using J = RaggedScrubJob<K, R, LOC>;
+    // as matapply_ragged: the walk's wave-uniform state leaves few SGPRs, so each
+    // row's tables are read where they are used from a lower threshold on
+    // (matlocate_ragged<1,2> spilled three with its tables held)
+    constexpr bool AL = K * R * 5 >= (LOC ? 10 : 15);
+    Tab T[R][K];
+    if constexpr (!AL) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const uint32_t* t = &job.tab[(r * K + j) * 5];
+                T[r][j] = Tab{t[0], t[1], t[2], t[3], t[4]};
+            }
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t G = gridDim.x * (kBlock / 64);
+    const CU64 us = (CU64)job.ustart;
+    const uint32_t ns = job.nstripes;
+    const uint64_t total = us[ns];
+    // (a launch with a wave per unit or more needs no division)
+    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
+    uint64_t u = uniform64(g * q + (g < e ? g : e));
+    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
+    if (u >= end) return;
+    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (us[mid] <= u)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
+    ScrubStripe cur = scrub_stripe(job, s);
+    for (;;) {
+        ScrubStripe nxt = cur;
+        if (s + 1 < ns) nxt = scrub_stripe(job, s + 1);
+        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+        const uint64_t sz = cur.sz;
+        const uint64_t B = job.bstride ? job.bstride : sz;
+        uint32_t smask = 0, sexcl = 0;  // this wave's bits of stripe s
+        if (u < stop && ragged_fits(cur.off, B, job.slots, sz, job.bytes)) {
+            const uint8_t* const in0 = job.src + cur.off;
+            const uint64_t coff = job.chk0 * B;
+            const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
+            for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
+                const uint64_t c = w * 64u + lane;
+                const bool live = c < cps;
+                const Span sp = ragged_span(c, sz, nfull);
+                u32x4 x[K], y[R];
+#pragma unroll
+                for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int r = 0; r < R; ++r) y[r] = u32x4{0u, 0u, 0u, 0u};
+                if (live) {
+                    // the row address advances per lane, as matapply_ragged's output rows do
+                    const uint8_t* row = in0 + sp.off;
+                    const uint8_t* crow = row + coff;
+                    if (sp.full) {
+#pragma unroll
+                        for (int j = 0; j < K; ++j, row = next_row(row, B)) x[j] = load16(row);
+#pragma unroll
+                        for (int r = 0; r < R; ++r, crow = next_row(crow, B)) y[r] = load16(crow);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < K; ++j, row = next_row(row, B)) x[j] = load_tail(row, sp.nb);
+#pragma unroll
+                        for (int r = 0; r < R; ++r, crow = next_row(crow, B)) y[r] = load_tail(crow, sp.nb);
+                    }
+                }
+                Sel sel[4][K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    sel[0][j] = selectors(x[j].x);
+                    sel[1][j] = selectors(x[j].y);
+                    sel[2][j] = selectors(x[j].z);
+                    sel[3][j] = selectors(x[j].w);
+                }
+                uint32_t mask = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    Tab t[K];
+                    if constexpr (AL) {
+                        // the pointer is formed after the previous row's ballot (mask), so at
+                        // most two rows' tables are in SGPRs at a time: left free, the
+                        // scheduler requests several rows at once and the walk's state spills
+                        KPtr<J> kj = kernarg_job<J>();
+                        asm volatile("" : "+s"(kj) : "s"(mask));
+#pragma unroll
+                        for (int j = 0; j < K; ++j) {
+                            const uint32_t i = (r * K + j) * 5;
+                            t[j] = Tab{kj->tab[i], kj->tab[i + 1], kj->tab[i + 2], kj->tab[i + 3], kj->tab[i + 4]};
+                        }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < K; ++j) t[j] = T[r][j];
+                    }
+                    // the syndrome of row r replaces the stored row
+                    y[r].x ^= gf_dot<K>(t, sel[0]);
+                    y[r].y ^= gf_dot<K>(t, sel[1]);
+                    y[r].z ^= gf_dot<K>(t, sel[2]);
+                    y[r].w ^= gf_dot<K>(t, sel[3]);
+                    const uint32_t d = y[r].x | y[r].y | y[r].z | y[r].w;
+                    if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << r;
+                }
+                smask |= mask;
+                if constexpr (LOC) {
+                    if (mask != 0u) {  // wave-uniform: a scalar branch, not taken on clean data
+                        const Sel z[4][1] = {
+                            {selectors(y[0].x)}, {selectors(y[0].y)}, {selectors(y[0].z)}, {selectors(y[0].w)}};
+#pragma unroll
+                        for (int j = 0; j < K; ++j) {
+                            uint32_t d = 0;
+#pragma unroll
+                            for (int r = 1; r < R; ++r) {
+                                const KPtr<J> kj = kernarg_job<J>();
+                                const uint32_t i = ((r - 1) * K + j) * 5;
+                                const Tab qt[1] = {Tab{kj->qtab[i], kj->qtab[i + 1], kj->qtab[i + 2], kj->qtab[i + 3],
+                                                       kj->qtab[i + 4]}};
+                                d |= (y[r].x ^ gf_dot<1>(qt, z[0])) | (y[r].y ^ gf_dot<1>(qt, z[1])) |
+                                     (y[r].z ^ gf_dot<1>(qt, z[2])) | (y[r].w ^ gf_dot<1>(qt, z[3]));
+                            }
+                            if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) sexcl |= 1u << j;
+                        }
+                    }
+                }
+            }
+        }
+        // leaving stripe s: its bits go out once per (wave, stripe)
+        if ((smask | sexcl) != 0u && lane == 0u) {
+            uint32_t* const base = job.bits + size_t(s) * job.words;
+            if (smask != 0u) mismatch_or(base, job.bit0, smask);
+            if (LOC && sexcl != 0u) mismatch_or(base, job.xbit, sexcl);
+        }
+        u = stop;
+        if (u >= end || s + 1 >= ns) break;
+        ++s;
+        cur = nxt;
+        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
+            ++s;
+            cur = scrub_stripe(job, s);
+        }
+    }
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matverify_ragged(const RaggedScrubJob<K, R, false> job) {
+    scrub_ragged_body<K, R, false>(job);
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matlocate_ragged(const RaggedScrubJob<K, R, true> job) {
+    scrub_ragged_body<K, R, true>(job);
+}
+
+// ---------------------------------------------------------------------------
+// ragged_unfit: the marks of a ragged scrub whose descriptor arrays are device
+// memory.  One lane per stripe tests the fit (a size past the arena, which
+// ragged_scan gave no units, fails it too) and marks a nonempty stripe that
+// does not fit, which the block kernel did not read: all c check bits
+// (verify: a scrub must not vouch for what it did not read) or, with c == 0,
+// the verdict FEC_LOCATE_UNFIT.  Plain vector stores.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kLocateUnfit = 0xFFFFFFFBu;
+
+struct alignas(16) UnfitJob {
+    const uint64_t* sizes;
+    const uint64_t* off;
+    uint64_t bstride, bytes;
+    uint32_t* out;
+    uint32_t nstripes, slots, words, c;
+};
+
+__global__ __launch_bounds__(kBlock) void ragged_unfit(const UnfitJob job) {
+    const uint32_t s = blockIdx.x * kBlock + threadIdx.x;
+    if (s >= job.nstripes) return;
+    const uint64_t sz = job.sizes[s];
+    if (sz == 0 || ragged_fits(job.off[s], job.bstride ? job.bstride : sz, job.slots, sz, job.bytes)) return;
+    if (job.c == 0u) {
+        job.out[s] = kLocateUnfit;
+        return;
+    }
+    for (uint32_t i = 0; i < job.words; ++i) job.out[size_t(s) * job.words + i] = low_bits(job.c - 32u * i);
 }
 
 // ---------------------------------------------------------------------------
@@ -5036,6 +5297,109 @@ hipError_t launch_ragged_all(const RaggedSpec& p, hipStream_t stream) {
     return e;
 }
 
+// ---- matverify_ragged / matlocate_ragged dispatch -------------------------------------
+// The three descriptor arrays of a ragged scrub in device memory.
+struct ScrubDev {
+    const uint64_t *ustart, *sizes, *off;
+};
+
+const KrNames g_ragged_verify_names("matverify_ragged");
+const KrNames g_ragged_locate_names("matlocate_ragged");
+
+template <int K, int R, bool LOC>
+hipError_t launch_ragged_scrub_kr(const RaggedScrubSpec& p, const ScrubDev& d, uint32_t g0, uint32_t grid,
+                                  hipStream_t stream) {
+    RaggedScrubJob<K, R, LOC> job;
+    job.bstride = p.bstride;
+    job.bytes = p.bytes;
+    job.nstripes = static_cast<uint32_t>(p.nstripes);
+    job.slots = p.k + p.c;
+    job.chk0 = p.k + g0;
+    job.bit0 = g0;
+    job.words = p.words;
+    job.xbit = p.xbit;
+    job.ustart = d.ustart;
+    job.sizes = d.sizes;
+    job.off = d.off;
+    job.src = p.src;
+    job.bits = p.bits;
+    for (int i = 0; i < R * K; ++i) host_tab(&job.tab[i * 5], p.P[size_t(g0) * K + i]);
+    job.qtab[0] = 0;
+    if constexpr (LOC)
+        for (int i = 0; i < (R - 1) * K; ++i) host_tab(&job.qtab[i * 5], p.Q[i]);
+    const void* fn;
+    if constexpr (LOC)
+        fn = reinterpret_cast<const void*>(matlocate_ragged<K, R>);
+    else
+        fn = reinterpret_cast<const void*>(matverify_ragged<K, R>);
+    const hipError_t e = launch_job(fn, grid, kBlock, 0, stream, job);
+    if (e == hipSuccess) t_last_kernel = (LOC ? g_ragged_locate_names : g_ragged_verify_names).name[K][R];
+    return e;
+}
+
+struct RaggedVerifyKr {
+    template <int K, int R>
+    static hipError_t launch(const RaggedScrubSpec& p, const ScrubDev& d, uint32_t g0, uint32_t grid,
+                             hipStream_t stream) {
+        return launch_ragged_scrub_kr<K, R, false>(p, d, g0, grid, stream);
+    }
+};
+struct RaggedLocateKr {
+    template <int K, int R>
+    static hipError_t launch(const RaggedScrubSpec& p, const ScrubDev& d, uint32_t g0, uint32_t grid,
+                             hipStream_t stream) {
+        return launch_ragged_scrub_kr<K, R, true>(p, d, g0, grid, stream);
+    }
+};
+constexpr KrTable<RaggedVerifyKr> g_ragged_verify_launch;
+constexpr KrTable<RaggedLocateKr, 2> g_ragged_locate_launch;
+
+// The grid rule is matapply_ragged's, ceil(10 / (k + r)) units per wave with r
+// the launch's checks: measured there for stored rows at k + r = 10 and 5, not
+// for this read-only traffic.
+hipError_t launch_ragged_scrub_all(const RaggedScrubSpec& p, hipStream_t stream) {
+    const uint64_t ns = p.nstripes;
+    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
+    StagedUpload up;
+    ScrubDev d;
+    hipError_t e;
+    uint64_t units;  // of the whole call, or (device arrays) a bound on them
+    if (p.desc_host) {
+        // [ustart | sizes | offsets] by one copy
+        const size_t bytes = (3 * ns + 1) * sizeof(uint64_t);
+        if ((e = up.acquire(bytes)) != hipSuccess) return e;
+        uint64_t* h = reinterpret_cast<uint64_t*>(up.host());
+        const uint64_t total = ragged_units(p.sizes, ns, h);
+        if (!total) return hipSuccess;  // every stripe is empty: nothing copied, nothing launched
+        std::memcpy(h + ns + 1, p.sizes, ns * sizeof(uint64_t));
+        std::memcpy(h + 2 * ns + 1, p.off, ns * sizeof(uint64_t));
+        if ((e = up.copy(bytes, stream)) != hipSuccess) return e;
+        const uint64_t* dv = reinterpret_cast<const uint64_t*>(up.dev());
+        d = ScrubDev{dv, dv + ns + 1, dv + 2 * ns + 1};
+        units = total;
+    } else {
+        // an estimate sizes the grid (launch_ragged_all): blocks do not overlap
+        units = std::max<uint64_t>(1, p.bytes / (p.bstride ? 1 : p.k + p.c) / kRaggedUnit);
+        const uint64_t ntiles = (ns + kScanTile - 1) / kScanTile;
+        if ((e = up.acquire((ns + 1 + ntiles) * sizeof(uint64_t))) != hipSuccess) return e;
+        uint64_t* dv = reinterpret_cast<uint64_t*>(up.slot->dev);
+        if ((e = launch_ragged_scan(p.sizes, ns, p.bytes, dv, dv + ns + 1, stream)) != hipSuccess) {
+            up.done(stream);
+            return e;
+        }
+        d = ScrubDev{dv, p.sizes, p.off};
+    }
+    for (uint32_t g0 = 0; g0 < p.c && e == hipSuccess; g0 += kRegR) {
+        const uint32_t rg = std::min<uint32_t>(kRegR, p.c - g0);
+        const uint64_t per_wg = ragged_units_per_wave(p.k, rg) * (kBlock / 64), need = (units + per_wg - 1) / per_wg;
+        const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
+        e = p.Q ? g_ragged_locate_launch(p.k, rg)(p, d, g0, grid, stream)
+                : g_ragged_verify_launch(p.k, rg)(p, d, g0, grid, stream);
+    }
+    up.done(stream);
+    return e;
+}
+
 // ---- mix form of the run-time-data bit-sliced kernels (4 < k <= 32) ------------------
 // Waves (row tiles) per unit from r alone -- not from the size of the call as
 // bsr_tiles -- so that a record serves every call: one wave for r <= 10, 2 for
@@ -5573,6 +5937,37 @@ hipError_t launch_ragged(const RaggedSpec& g, hipStream_t stream) {
     if (stream_capturing(stream)) return hipErrorNotSupported;
     reset_signal();
     return launch_ragged_all(g, stream);
+}
+
+hipError_t launch_ragged_scrub(const RaggedScrubSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    const uint32_t cw = (p.c + 31) / 32;
+    if (p.k < 1 || p.k > static_cast<uint32_t>(kRegK) || p.c < 1 || p.k + p.c > 256 || !p.P || !p.src || !p.sizes ||
+        !p.off || !p.bits || p.nstripes == 0 || p.nstripes >= (1ull << 32) || p.words < cw ||
+        (p.Q && (p.c < 2 || p.c > static_cast<uint32_t>(kRegR) || p.xbit < p.c ||
+                 uint64_t(p.xbit) + p.k > uint64_t(p.words) * 32)))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    return launch_ragged_scrub_all(p, stream);
+}
+
+hipError_t launch_ragged_unfit(const uint64_t* sizes, const uint64_t* off, uint64_t nstripes, uint32_t slots,
+                               uint64_t bstride, uint64_t bytes, uint32_t c, uint32_t* out, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (!sizes || !off || !out || slots < 1 || nstripes == 0 || nstripes >= (1ull << 32)) return hipErrorInvalidValue;
+    UnfitJob job;
+    job.sizes = sizes;
+    job.off = off;
+    job.bstride = bstride;
+    job.bytes = bytes;
+    job.out = out;
+    job.nstripes = static_cast<uint32_t>(nstripes);
+    job.slots = slots;
+    job.words = (c + 31) / 32;
+    job.c = c;
+    const uint32_t grid = static_cast<uint32_t>((nstripes + kBlock - 1) / kBlock);
+    return launch_job(reinterpret_cast<const void*>(ragged_unfit), grid, kBlock, 0, stream, job);
 }
 
 int generic_mode() {

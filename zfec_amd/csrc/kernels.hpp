@@ -359,6 +359,42 @@ struct RaggedSpec {
 };
 hipError_t launch_ragged(const RaggedSpec& g, hipStream_t stream);
 
+// The scrub of such a batch (matverify_ragged<K, R> / matlocate_ragged<K, R>,
+// k <= 4; fec_verify_batch_ragged / fec_locate_batch_ragged).  Stripe s holds
+// k + c blocks of sizes[s] bytes, slot j at src + off[s] + j * B with B =
+// bstride, or sizes[s] when that is 0; P is the c x k matrix of the checks.
+// Q null: a verify; bit i of the stripe's `words` words at bits + s * words is
+// OR-ed in when check i differs, more than 8 checks as row groups of 8 over
+// one staging.  Q set ((c-1) x k, 2 <= c <= 8): a location; mismatch bits from
+// bit 0 and excluded bits from bit xbit of the stripe's working words, for
+// launch_locate_finish.  The words are device memory the caller cleared in
+// stream order.  Bits are accumulated per (wave, stripe) and OR-ed out once,
+// only where nonzero.  A stripe is read only where it fits the arena; an empty
+// or unfit one contributes no bit.  Descriptors, units and staging as
+// launch_ragged (ragged_scan with maxsz = bytes); hipErrorNotSupported under
+// capture, hipErrorInvalidValue for other shapes.
+//
+// launch_ragged_unfit (ragged_unfit): for descriptor arrays in device memory,
+// one lane per stripe marks every nonempty stripe that does not fit: all c
+// check bits of its ceil(c / 32) words at out + s * words, or with c == 0 the
+// verdict FEC_LOCATE_UNFIT at out + s.  Plain stores; it stages nothing and
+// leaves matapply_last_kernel() as it was.
+struct RaggedScrubSpec {
+    uint32_t k, c;
+    const uint8_t* P;    // c x k coefficients, row-major (host memory)
+    const uint8_t* Q;    // (c-1) x k, or null: verify
+    const uint8_t* src;  // the arena, a kernel-visible address
+    uint64_t bytes, bstride;
+    const uint64_t *sizes, *off;  // nstripes each
+    bool desc_host;
+    uint64_t nstripes;
+    uint32_t* bits;
+    uint32_t words, xbit;
+};
+hipError_t launch_ragged_scrub(const RaggedScrubSpec& p, hipStream_t stream);
+hipError_t launch_ragged_unfit(const uint64_t* sizes, const uint64_t* off, uint64_t nstripes, uint32_t slots,
+                               uint64_t bstride, uint64_t bytes, uint32_t c, uint32_t* out, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
