@@ -84,6 +84,19 @@ build/scrub/validate: $(SCRUBSAN) $(SRC)/*.hpp include/zfec_hip.h
 asan-scrub: build/scrub/validate
 	ASAN_OPTIONS=detect_leaks=0 ./build/scrub/validate
 
+# The same for the validation path of fec_repair_batch_ragged and
+# fec_correct_batch_ragged: tests/c/ragged_repair_validate.cpp.
+REPAIRSAN := $(filter-out tests/c/sanitize_driver.cpp,$(SANSRC)) tests/c/ragged_repair_validate.cpp
+
+build/repair/validate: $(REPAIRSAN) $(SRC)/*.hpp include/zfec_hip.h
+	mkdir -p build/repair
+	set -e; for f in $(REPAIRSAN); do \
+	  $(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=address,undefined -c $$f -o build/repair/$$(basename $$f).o; done
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -fno-gpu-sanitize -o $@ build/repair/*.o -ldl -lpthread
+
+asan-repair: build/repair/validate
+	ASAN_OPTIONS=detect_leaks=0 ./build/repair/validate
+
 # The no-GPU Python tests of the C-ABI (tests/test_cpu_surface.py: validation,
 # JIT registry from threads) against an AddressSanitizer build of the library,
 # loaded through zfec_amd.capi (ZFEC_HIP_LIB) with the ASan runtime preloaded.
@@ -104,4 +117,4 @@ clean:
 	rm -f $(SRC)/*.o $(LIB) $(PYEXT)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle ref clean asan tsan asan-py asan-scrub
+.PHONY: all oracle ref clean asan tsan asan-py asan-scrub asan-repair

@@ -787,6 +787,97 @@ int fec_repair_batch_planned(const fec_repair_plan_t* plan,
                              const unsigned* pattern_of, size_t sz, size_t nstripes,
                              void* stream, unsigned flags);
 
+/* Ragged repair: fec_repair_batch over stripes that each have their own size,
+ * in one launch.  The arena arguments are those of fec_encode_batch_ragged,
+ * the pattern arguments those of fec_repair_batch.
+ *
+ * Slot j of stripe s starts at src + src_offsets[s] + j*B, with B =
+ * src_block_stride, or sizes[s] when the stride is 0; output row i starts at
+ * dst + dst_offsets[s] + i*B', B' formed the same way from dst_block_stride.
+ * Offsets are arbitrary bytes.  A zero-size stripe is neither read nor
+ * written.  Stripe s uses pattern p = pattern_of[s]: slot j holds block
+ * present[p*k + j], in any slot order, and row i receives block
+ * targets[p*ntargets + i].  A FEC_REPAIR_NONE row is not written: none of its
+ * bytes and nothing past them.  pattern_of == NULL requires npatterns == 1,
+ * and every stripe then uses pattern 0.  The bytes are those of
+ * fec_repair_batch called once per stripe with nstripes = 1 and sz = sizes[s].
+ * A decode with a pattern per stripe is this call with targets 0..k-1.
+ *
+ * sizes, src_offsets and dst_offsets are all in host memory or all in device
+ * memory on the blocks' device (a mix is FEC_EINVAL); pattern_of is
+ * independently host or device memory, as in fec_repair_batch.  Host arrays
+ * are copied when the call is made; device arrays are read where they are, in
+ * stream order, and nothing synchronises the stream.
+ *
+ * A stripe with sizes[s] > 0 FITS when offset + (rows - 1)*B + sizes[s] <=
+ * bytes holds on both sides, evaluated without wrapping, rows being k for src
+ * and ntargets for dst: the place of a FEC_REPAIR_NONE row must exist although
+ * it is not written.  With host descriptor arrays a stripe that does not fit
+ * is FEC_EINVAL, the message naming the stripe and the side; a host-side id >=
+ * npatterns is FEC_EINVAL, naming the stripe.  With device arrays the kernel
+ * makes both tests per stripe: a stripe that does not fit, or whose id is >=
+ * npatterns, is neither read nor written, and no error is reported -- the rule
+ * of the other writing ragged calls and of fec_repair_batch.
+ *
+ * Checked in this order, each FEC_EINVAL with a message naming the call:
+ * fec_repair_batch's checks of the code and the pattern arguments, in its
+ * order; a NULL sizes, src_offsets or dst_offsets; nstripes >= 2^32;
+ * descriptor arrays of mixed memory kinds; a host-side id out of range; with
+ * host arrays a stripe that does not fit.  Then FEC_ENODEV when no GPU is
+ * visible.  nstripes == 0 returns FEC_OK.  A batch whose sizes are all zero,
+ * or whose targets are all FEC_REPAIR_NONE, launches nothing.  src and dst are
+ * device memory on one device or page-locked host memory; pageable memory
+ * returns FEC_EINVAL.  The call stages per call, so it returns FEC_EINVAL while
+ * the stream is being captured into a graph.  dst must not overlap src.
+ *
+ * k <= 4 runs matrepair_ragged<k,r>: matapply_ragged's walk with
+ * matrepair_mixed's per-stripe record, one launch per 8 targets, a group of 8
+ * no pattern uses skipped.  Wider codes are cut into runs of consecutive
+ * stripes of one size and one pattern id whose two offsets each advance by a
+ * constant, each run one shared-matrix launch of that pattern's used rows (at
+ * worst one launch per stripe); device-side arrays are first copied to the
+ * host there, which SYNCHRONISES the stream, and stripes that do not fit or
+ * have a bad id are skipped. */
+int fec_repair_batch_ragged(const fec_t* code,
+                            const gf* src, size_t src_bytes, size_t src_block_stride,
+                            const unsigned long long* src_offsets,
+                            gf* dst, size_t dst_bytes, size_t dst_block_stride,
+                            const unsigned long long* dst_offsets,
+                            const unsigned long long* sizes,
+                            const unsigned* present, const unsigned* targets, size_t ntargets,
+                            size_t npatterns, const unsigned* pattern_of,
+                            size_t nstripes, void* stream, unsigned flags);
+
+/* Ragged in-place correction: fec_correct_batch over stripes that each have
+ * their own size.  The arguments are exactly fec_locate_batch_ragged's, with
+ * the arena writable.
+ *
+ * culprit[s] is the verdict fec_locate_batch_ragged gives for the blocks as
+ * they were on entry, FEC_LOCATE_UNFIT included.  For a verdict h < nb the
+ * sizes[s] bytes of slot h are rewritten by row h of fec_correct_rows from
+ * slots 0..k-1, check 0 standing in for h when h < k.  Nothing else in caller
+ * memory is written: no byte of a CLEAN, MANY, UNKNOWN, UNFIT or zero-size
+ * stripe, no other slot of a corrected stripe, no byte past sizes[s] of slot h
+ * (in a packed object that byte belongs to slot h + 1 or to the next stripe).
+ * The guarantees are fec_correct_batch's.
+ *
+ * Memory kinds, result words in host or device memory, flags, capture and the
+ * validation order are fec_locate_batch_ragged's, the messages naming this
+ * call.  The location runs exactly as there; for k <= 4 and at most 8 checks
+ * matcorrect_ragged<k> follows in the same stream over the verdict words in
+ * device memory and the descriptors the location staged, a clean stripe costing
+ * it scalar loads only, and it makes its own fit test.  For the shapes the
+ * ragged location cuts into runs, each run's location is followed by the
+ * uniform correction over that run's verdict words.  fec_last_kernel_name()
+ * names the correction kernel where one ran. */
+int fec_correct_batch_ragged(const fec_t* code,
+                             gf* blocks, size_t bytes, size_t block_stride,
+                             const unsigned long long* offsets,
+                             const unsigned long long* sizes,
+                             const unsigned* block_nums, size_t num_block_nums,
+                             size_t nstripes,
+                             unsigned* culprit, void* stream, unsigned flags);
+
 /* Batched calls over several GPUs of this process.  The nstripes stripes are
  * split into contiguous, balanced ranges, one per entry of devices[] (entry d
  * gets stripes [d*q + min(d, e), ...), q = nstripes / ndevices, e = the

@@ -205,7 +205,8 @@ def _ragged_words(x, what):
 
 def _ragged_call(coder, fn, data, sizes, offsets, out, out_offsets, nums, r):
     """The arguments of Encoder.encode_ragged / Decoder.decode_ragged checked
-    and completed, then capi.Code.<fn>; returns (out, out_offsets)."""
+    and completed, then capi.Code.<fn> (or fn itself, a callable that takes
+    that method's arguments: Decoder.repair_ragged); returns (out, out_offsets)."""
     import torch
 
     k = coder.k
@@ -248,9 +249,9 @@ def _ragged_call(coder, fn, data, sizes, offsets, out, out_offsets, nums, r):
         out = torch.empty(r * int(sizes.sum()) if ns else 0, dtype=torch.uint8, device=data.device)
     if ns and r and data.numel() and out.numel():
         with torch.cuda.device(data.device), _as_error():
-            getattr(_capi_code(coder), fn)(data.data_ptr(), data.numel(), 0, offsets.data_ptr(), out.data_ptr(),
-                                           out.numel(), 0, out_offsets.data_ptr(), sizes.data_ptr(), nums, ns,
-                                           stream=_stream_handle(data.device))
+            call = fn if callable(fn) else getattr(_capi_code(coder), fn)
+            call(data.data_ptr(), data.numel(), 0, offsets.data_ptr(), out.data_ptr(), out.numel(), 0,
+                 out_offsets.data_ptr(), sizes.data_ptr(), nums, ns, stream=_stream_handle(data.device))
     return out, out_offsets
 
 
@@ -712,6 +713,54 @@ class Decoder(_fec.Decoder):
                         % (k, blocks.shape[1]))
         ns = blocks.shape[0]
 
+        pats, tgts, ids_host, ids_dev = self._repair_patterns(ns, blocknums, targets)
+        t, npat = tgts.shape[1], pats.shape[0]
+        sz = blocks.shape[2]
+        if out is not None:
+            out_ok = type(out).__module__.startswith("torch") and hasattr(out, "data_ptr")
+            if not out_ok or str(out.dtype) != "torch.uint8" or tuple(out.shape) != (ns, t, sz):
+                raise Error("Precondition violation: out is required to be a uint8 tensor [nstripes, t, sz] = "
+                            "[%d, %d, %d]" % (ns, t, sz))
+            if out.device != blocks.device:
+                raise Error("Precondition violation: out is required to be on the blocks' device")
+            if (sz > 1 and out.stride(2) != 1) or min(out.stride(0), out.stride(1)) < 0:
+                raise Error("Precondition violation: out rows are required to be contiguous along sz")
+        if not blocks.is_cuda:
+            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
+                        "not a host tensor" % k)
+        ns, sz, sbs, sss, ptr = _batch_view(blocks, k, "blocks")
+        if out is None:
+            out = _batch_out(blocks, sss < sbs, ns, t, sz)
+        if ns and sz and npat:
+            import torch
+
+            if ids_dev is not None:
+                if ids_dev.device != blocks.device:
+                    raise Error("Precondition violation: device blocknums are required to be on the blocks' device")
+                ids = ids_dev.to(torch.int32).contiguous()  # non-negative ids: the bits of uint32
+                ids_ptr = ids.data_ptr()
+            else:
+                ids = np.ascontiguousarray(ids_host, dtype=np.uint32)
+                ids_ptr = ids.ctypes.data
+            optr, obs, oss = _batch_strides(out)
+            stream, flags = _batch_call_args(blocks)
+            # `ids` need only outlive the call: host ids are copied into the
+            # library's staging, device ids are read by work of this stream
+            with _as_error():
+                _capi_code(self).repair_batch(ptr, sbs, sss, optr, obs, oss, np.ascontiguousarray(pats, dtype=np.int64),
+                                              np.ascontiguousarray(tgts, dtype=np.int64), ids_ptr, sz, ns,
+                                              stream=stream, flags=flags)
+        return out
+
+    def _repair_patterns(self, ns, blocknums, targets):
+        """The two forms of repair_batch's blocknums and targets reduced to
+        patterns: (patterns [P, k], targets [P, t], ids_host, ids_dev), numpy
+        tables checked against k and m, and the nstripes pattern ids as a
+        numpy array or a device tensor (the other None)."""
+        import numpy as np
+
+        k, m = self.k, self.m
+
         def host_table(x, what):
             a = x.cpu().numpy() if hasattr(x, "data_ptr") else np.asarray(x)
             if a.ndim != 2 or (a.size and a.dtype.kind not in "iu"):
@@ -794,42 +843,53 @@ class Decoder(_fec.Decoder):
         npat = pats.shape[0]
         if ids_host is not None and ids_host.size and (ids_host.min() < 0 or ids_host.max() >= npat):
             raise Error("Precondition violation: pattern_of ids are required to be in [0, %d]" % (npat - 1))
-        sz = blocks.shape[2]
-        if out is not None:
-            out_ok = type(out).__module__.startswith("torch") and hasattr(out, "data_ptr")
-            if not out_ok or str(out.dtype) != "torch.uint8" or tuple(out.shape) != (ns, t, sz):
-                raise Error("Precondition violation: out is required to be a uint8 tensor [nstripes, t, sz] = "
-                            "[%d, %d, %d]" % (ns, t, sz))
-            if out.device != blocks.device:
-                raise Error("Precondition violation: out is required to be on the blocks' device")
-            if (sz > 1 and out.stride(2) != 1) or min(out.stride(0), out.stride(1)) < 0:
-                raise Error("Precondition violation: out rows are required to be contiguous along sz")
-        if not blocks.is_cuda:
-            raise Error("Precondition violation: blocks is required to be a uint8 device tensor [nstripes, %d, sz], "
-                        "not a host tensor" % k)
-        ns, sz, sbs, sss, ptr = _batch_view(blocks, k, "blocks")
-        if out is None:
-            out = _batch_out(blocks, sss < sbs, ns, t, sz)
-        if ns and sz and npat:
-            import torch
+        return pats, tgts, ids_host, ids_dev
 
-            if ids_dev is not None:
-                if ids_dev.device != blocks.device:
-                    raise Error("Precondition violation: device blocknums are required to be on the blocks' device")
-                ids = ids_dev.to(torch.int32).contiguous()  # non-negative ids: the bits of uint32
-                ids_ptr = ids.data_ptr()
-            else:
-                ids = np.ascontiguousarray(ids_host, dtype=np.uint32)
-                ids_ptr = ids.ctypes.data
-            optr, obs, oss = _batch_strides(out)
-            stream, flags = _batch_call_args(blocks)
+    def repair_ragged(self, data, sizes, blocknums, targets, offsets=None, out=None, out_offsets=None):
+        """repair_batch over stripes that each have their own size, in one
+        launch (fec_repair_batch_ragged).
+
+        data, sizes, offsets, out and out_offsets as in decode_ragged: slot j
+        of stripe s is the sizes[s] bytes from data[offsets[s] + j *
+        sizes[s]], and row i of stripe s is written from out[out_offsets[s] +
+        i * sizes[s]]; the defaults are the packed layouts k * (cumsum(sizes)
+        - sizes) and t * (cumsum(sizes) - sizes).  blocknums and targets take
+        the two forms repair_batch accepts: [nstripes, k] with [nstripes, t],
+        or (patterns [P, k], pattern_of [nstripes]) with [P, t]; a target of
+        -1 means none.  Returns the output arena; with out given, the rows of
+        -1 targets keep their contents, without it they are unspecified.  With
+        descriptors on the device nothing synchronises with the host, and a
+        stripe whose descriptor does not fit, or whose device-side id is not
+        below P, is left unwritten; with descriptors on the CPU such a stripe
+        is an Error.  A decode with a pattern per stripe is targets =
+        0..k-1."""
+        import numpy as np
+        import torch
+
+        sizes = _ragged_words(sizes, "sizes")
+        ns = sizes.numel()
+        pats, tgts, ids_host, ids_dev = self._repair_patterns(ns, blocknums, targets)
+        t = tgts.shape[1]
+        if ids_dev is not None:
+            if not isinstance(data, torch.Tensor) or ids_dev.device != data.device:
+                raise Error("Precondition violation: device blocknums are required to be on the data's device")
+            ids = ids_dev.to(torch.int32).contiguous()  # non-negative ids: the bits of uint32
+            ids_ptr = ids.data_ptr()
+        else:
+            ids = np.ascontiguousarray(ids_host, dtype=np.uint32)
+            ids_ptr = ids.ctypes.data
+        pats = np.ascontiguousarray(pats, dtype=np.int64)
+        tgts = np.ascontiguousarray(tgts, dtype=np.int64)
+
+        code = _capi_code(self)
+
+        def call(src, src_bytes, sbs, soff, dst, dst_bytes, dbs, doff, szs, nums, nstripes, stream=0):
             # `ids` need only outlive the call: host ids are copied into the
             # library's staging, device ids are read by work of this stream
-            with _as_error():
-                _capi_code(self).repair_batch(ptr, sbs, sss, optr, obs, oss, np.ascontiguousarray(pats, dtype=np.int64),
-                                              np.ascontiguousarray(tgts, dtype=np.int64), ids_ptr, sz, ns,
-                                              stream=stream, flags=flags)
-        return out
+            code.repair_batch_ragged(src, src_bytes, sbs, soff, dst, dst_bytes, dbs, doff, szs, pats, tgts, ids_ptr,
+                                     nstripes, stream=stream)
+
+        return _ragged_call(self, call, data, sizes, offsets, out, out_offsets, None, t)[0]
 
     def repair_plan(self, patterns, targets):
         """A RepairPlan of P erasure patterns for repair_batch's work: patterns
@@ -990,6 +1050,30 @@ class Decoder(_fec.Decoder):
             with torch.cuda.device(data.device), _as_error():
                 _capi_code(self).locate_batch_ragged(data.data_ptr(), data.numel(), 0, offs.data_ptr(), szs.data_ptr(),
                                                      nums, ns, out.data_ptr(), stream=_stream_handle(data.device))
+        return out
+
+    def correct_ragged(self, data, sizes, blocknums, offsets=None):
+        """correct_batch over stripes that each have their own size: scrub,
+        locate and heal in place, in one call (fec_correct_batch_ragged).
+
+        Arguments as locate_ragged.  Returns the torch.int32 verdict tensor
+        [nstripes] locate_ragged would return for the data as it was on entry
+        (LOCATE_UNFIT included), and CORRECTS `data` IN PLACE: in a stripe
+        whose verdict is a slot h >= 0, the sizes[s] bytes of slot h are
+        rewritten from k other slots of that stripe, as correct_batch does.
+        Nothing else is written: no byte of a clean, LOCATE_MANY,
+        LOCATE_UNKNOWN, LOCATE_UNFIT or zero-size stripe, no other slot of a
+        corrected stripe, no byte past sizes[s] of slot h.  The work is
+        enqueued on the current stream."""
+        import torch
+
+        nums, ns, szs, offs = self._ragged_scrub_args(data, sizes, blocknums, offsets)
+        out = torch.empty((ns,), dtype=torch.int32, device=data.device)
+        if ns:
+            with torch.cuda.device(data.device), _as_error():
+                _capi_code(self).correct_batch_ragged(data.data_ptr(), data.numel(), 0, offs.data_ptr(),
+                                                      szs.data_ptr(), nums, ns, out.data_ptr(),
+                                                      stream=_stream_handle(data.device))
         return out
 
     def _ragged_scrub_args(self, data, sizes, blocknums, offsets):

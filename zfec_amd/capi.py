@@ -79,6 +79,9 @@ SYMBOLS = [
     ("fec_ragged_units", ctypes.c_int, [_P, _SZ, _P]),
     ("fec_verify_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
     ("fec_locate_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
+    ("fec_repair_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _UP, _SZ, _SZ, _P, _SZ,
+                                               _P, _U]),
+    ("fec_correct_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_LOCATE_NONE = 0xFFFFFFFC  # fec_locate2_batch: the second word of a verdict that is no pair
@@ -395,6 +398,35 @@ class Code(object):
         st = lib().fec_locate_batch_ragged(self.ptr, src, src_bytes, sbs, src_offsets_ptr or None, sizes_ptr or None,
                                            _nums(block_nums), len(block_nums), nstripes, culprit_ptr or None,
                                            stream or None, flags)
+        if st:
+            check(st)
+
+    def repair_batch_ragged(self, src, src_bytes, sbs, src_offsets_ptr, dst, dst_bytes, dbs, dst_offsets_ptr,
+                            sizes_ptr, present, targets, pattern_of_ptr, nstripes, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_repair_batch_ragged: the arena arguments of encode_batch_ragged
+        (three `_ptr` descriptor arrays of nstripes 8-byte words, all in host
+        or all in device memory) and the pattern arguments of repair_batch
+        (`present` [P, k], `targets` [P, t] with -1 for FEC_REPAIR_NONE,
+        `pattern_of_ptr` the address of nstripes uint32 ids in host or device
+        memory, or 0 with P = 1)."""
+        pres, npat, _ = _uint_table(present, self.k, "present is required to be [npatterns, k = %d]" % self.k)
+        tgts, ntp, nt = _uint_table(targets, None, "targets is required to be [npatterns, ntargets]")
+        if ntp != npat:
+            raise FecError("targets is required to hold one row per pattern: %d rows, %d patterns" % (ntp, npat))
+        st = lib().fec_repair_batch_ragged(self.ptr, src, src_bytes, sbs, src_offsets_ptr or None, dst, dst_bytes, dbs,
+                                           dst_offsets_ptr or None, sizes_ptr or None, pres[0], tgts[0], nt, npat,
+                                           pattern_of_ptr or None, nstripes, stream or None, flags)
+        if st:
+            check(st)
+
+    def correct_batch_ragged(self, blocks, nbytes, bs, offsets_ptr, sizes_ptr, block_nums, nstripes, culprit_ptr,
+                             stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_correct_batch_ragged: the arguments of locate_batch_ragged,
+        `blocks` writable: the verdicts go to `culprit_ptr` as there, and the
+        slot a verdict names is rewritten in place."""
+        st = lib().fec_correct_batch_ragged(self.ptr, blocks, nbytes, bs, offsets_ptr or None, sizes_ptr or None,
+                                            _nums(block_nums), len(block_nums), nstripes, culprit_ptr or None,
+                                            stream or None, flags)
         if st:
             check(st)
 

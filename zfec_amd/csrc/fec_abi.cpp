@@ -1440,9 +1440,11 @@ bool ragged_stripe_fits(const RaggedCall& c, unsigned k, unsigned r, const unsig
 }
 
 // The checks of a ragged call that follow its block numbers, in the header's
-// order: the stripe count, the memory kind of the three descriptor arrays
-// (*ddev: their device, -1 host memory), and with host arrays every stripe's fit.
-int check_ragged(const RaggedCall& c, unsigned k, unsigned r, int* ddev) {
+// order: the stripe count and the memory kind of the three descriptor arrays
+// (check_ragged_kinds; *ddev: their device, -1 host memory), then with host
+// arrays every stripe's fit (check_ragged_fit).  fec_repair_batch_ragged checks
+// its host-side ids between the two.
+int check_ragged_kinds(const RaggedCall& c, int* ddev) {
     if (uint64_t(c.nstripes) >= (1ull << 32))
         return set_status(FEC_EINVAL, "%s: %zu stripes: a call takes fewer than 2^32", c.fn, c.nstripes);
     int dv[3] = {-1, -1, -1};
@@ -1455,7 +1457,11 @@ int check_ragged(const RaggedCall& c, unsigned k, unsigned r, int* ddev) {
         return set_status(FEC_EINVAL, "%s: sizes, src_offsets and dst_offsets are of mixed memory kinds: all three "
                                       "in host memory, or all three in device memory on the blocks' device", c.fn);
     *ddev = dv[0];
-    if (*ddev < 0)
+    return FEC_OK;
+}
+
+int check_ragged_fit(const RaggedCall& c, unsigned k, unsigned r, int ddev) {
+    if (ddev < 0)
         for (size_t s = 0; s < c.nstripes; ++s) {
             const char* side = "";
             if (c.sizes[s] && !ragged_stripe_fits(c, k, r, c.sizes, c.soff, c.doff, s, &side)) {
@@ -1468,6 +1474,11 @@ int check_ragged(const RaggedCall& c, unsigned k, unsigned r, int* ddev) {
             }
         }
     return FEC_OK;
+}
+
+int check_ragged(const RaggedCall& c, unsigned k, unsigned r, int* ddev) {
+    if (check_ragged_kinds(c, ddev)) return t_status;
+    return check_ragged_fit(c, k, r, *ddev);
 }
 
 int run_ragged(const RaggedCall& c, const fec_t* code, const uint8_t* coef, unsigned r, int ddev) {
@@ -2413,6 +2424,8 @@ struct ScrubCall {
     unsigned* out;  // mismatch or culprit
     void* stream;
     unsigned flags;
+    bool heal = false;  // fec_correct_batch_ragged: src is the caller's writable blocks
+    const char* arena() const { return heal ? "blocks" : "src"; }
 };
 
 bool scrub_stripe_fits(const ScrubCall& c, const unsigned long long* sizes, const unsigned long long* soff, size_t s) {
@@ -2427,9 +2440,9 @@ int check_ragged_scrub(const fec_t* code, const ScrubCall& c, int* ddev) {
     const struct {
         const void* p;
         const char* name;
-    } args[] = {{c.src, "src"},
+    } args[] = {{c.src, c.arena()},
                 {c.sizes, "sizes"},
-                {c.soff, "src_offsets"},
+                {c.soff, c.heal ? "offsets" : "src_offsets"},
                 {c.nums, "block_nums"},
                 {c.out, c.locate ? "culprit" : "mismatch"}};
     for (const auto& a : args)
@@ -2446,16 +2459,18 @@ int check_ragged_scrub(const fec_t* code, const ScrubCall& c, int* ddev) {
         dv[1] = pointer_device(c.soff);
     }
     if (dv[0] != dv[1])
-        return set_status(FEC_EINVAL, "%s: sizes and src_offsets are of mixed memory kinds: both in host memory, or "
-                                      "both in device memory on the blocks' device", c.fn);
+        return set_status(FEC_EINVAL, c.heal ? "%s: sizes and offsets are of mixed memory kinds: both in host memory, "
+                                               "or both in device memory on the blocks' device"
+                                             : "%s: sizes and src_offsets are of mixed memory kinds: both in host "
+                                               "memory, or both in device memory on the blocks' device", c.fn);
     *ddev = dv[0];
     if (*ddev < 0)
         for (size_t s = 0; s < c.nstripes; ++s)
             if (c.sizes[s] && !scrub_stripe_fits(c, c.sizes, c.soff, s))
-                return set_status(FEC_EINVAL, "%s: stripe %zu does not fit src: offset %llu, %zu rows %llu apart, "
-                                              "size %llu, src_bytes %zu", c.fn, s, c.soff[s], c.nb,
+                return set_status(FEC_EINVAL, "%s: stripe %zu does not fit %s: offset %llu, %zu rows %llu apart, "
+                                              "size %llu, %s %zu", c.fn, s, c.arena(), c.soff[s], c.nb,
                                   static_cast<unsigned long long>(c.sbs ? c.sbs : c.sizes[s]), c.sizes[s],
-                                  c.src_bytes);
+                                  c.heal ? "bytes" : "src_bytes", c.src_bytes);
     return FEC_OK;
 }
 
@@ -2490,6 +2505,9 @@ int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int 
     int rc = verify_rows(code, c.nums, c.nb, P.data());
     const bool hyp = c.locate && cc >= 2;
     if (!rc && hyp) locate_rows(P.data(), k, cc, Q.data());
+    // with one check no verdict is a slot: nothing to heal, and the location is all there is
+    const bool heal = c.heal && hyp;
+    RaggedScrubStaged staged;
     const uint64_t* const sizes = reinterpret_cast<const uint64_t*>(c.sizes);
     const uint64_t* const soff = reinterpret_cast<const uint64_t*>(c.soff);
     const auto unfit = [&](unsigned checks, uint32_t* to) {
@@ -2516,6 +2534,7 @@ int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int 
         g.bits = bits;
         g.words = words;
         g.xbit = xbit;
+        g.keep = heal ? &staged : nullptr;
         ++t_launches;
         if ((e = launch_ragged_scrub(g, st)) != hipSuccess) rc = hip_fail(e, "launch_ragged_scrub");
     }
@@ -2526,6 +2545,26 @@ int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int 
             rc = hip_fail(e, "launch_locate_finish");
         if (!rc && ddev >= 0) rc = unfit(0, out);  // overwrites the verdict of what was not read
     }
+    if (!rc && heal && staged.slot) {
+        // row h of the nb x k correction matrix rebuilds slot h, over the verdict words in device
+        // memory and the descriptors the location staged (mem.z[0] is the caller's writable blocks)
+        thread_local std::vector<uint8_t> R;
+        R.resize(c.nb * k);
+        correct_rows(P.data(), k, cc, R.data());
+        RaggedCorrectSpec cs;
+        cs.k = k;
+        cs.nb = static_cast<uint32_t>(c.nb);
+        cs.rows = R.data();
+        cs.blocks = const_cast<uint8_t*>(mem.z[0]);
+        cs.bytes = c.src_bytes;
+        cs.bstride = c.sbs;
+        cs.nstripes = ns;
+        cs.verdict = out;
+        cs.staged = staged;
+        ++t_launches;
+        if ((e = launch_ragged_correct(cs, st)) != hipSuccess) rc = hip_fail(e, "launch_ragged_correct");
+    }
+    ragged_scrub_release(staged, st);
     if (!rc && rdev < 0 && (e = hipMemcpyAsync(c.out, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
         rc = hip_fail(e, "hipMemcpyAsync D2H (result words)");
     order.release();
@@ -2598,7 +2637,7 @@ int run_ragged_scrub_runs(const fec_t* code, const ScrubCall& c, int ddev, int r
         }
         const size_t bs = c.sbs ? c.sbs : sz;
         if (c.locate ? run_locate(code, c.src + soff[s0], bs, dsrc, c.nums, c.nb, sz, s1 - s0, c.out + s0, c.stream, jf,
-                                  c.fn)
+                                  c.fn, c.heal)
                      : run_verify(code, c.src + soff[s0], bs, dsrc, c.nums, c.nb, sz, s1 - s0, c.out + s0 * cw,
                                   c.stream, jf))
             return t_status;
@@ -2618,7 +2657,7 @@ int ragged_scrub(const fec_t* code, const ScrubCall& c) {
     const char* const out_name = c.locate ? "culprit" : "mismatch";
     const int rdev = pointer_device(c.out);
     // device memory on one device, or page-locked host memory (read in place)
-    const BatchBuf buf = {c.src, c.src_bytes, "src"};
+    const BatchBuf buf = {c.src, c.src_bytes, c.arena()};
     BatchMem mem;
     if (resolve_batch(mem, c.fn, &buf, 1, out_name, rdev, c.stream, c.flags, kCaptureRagged)) return t_status;
     if (ddev >= 0 && ddev != mem.dev)
@@ -2643,6 +2682,15 @@ FEC_API int fec_locate_batch_ragged(const fec_t* code, const gf* src, size_t src
                                     unsigned* culprit, void* stream, unsigned flags) {
     const ScrubCall c{"fec_locate_batch_ragged", true, src, src_bytes, src_block_stride, src_offsets, sizes,
                       block_nums, num_block_nums, nstripes, culprit, stream, flags};
+    return guarded([&] { return ragged_scrub(code, c); });
+}
+
+FEC_API int fec_correct_batch_ragged(const fec_t* code, gf* blocks, size_t bytes, size_t block_stride,
+                                     const unsigned long long* offsets, const unsigned long long* sizes,
+                                     const unsigned* block_nums, size_t num_block_nums, size_t nstripes,
+                                     unsigned* culprit, void* stream, unsigned flags) {
+    const ScrubCall c{"fec_correct_batch_ragged", true, blocks, bytes, block_stride, offsets, sizes,
+                      block_nums, num_block_nums, nstripes, culprit, stream, flags, true};
     return guarded([&] { return ragged_scrub(code, c); });
 }
 
@@ -2926,6 +2974,178 @@ FEC_API int fec_repair_batch(const fec_t* code, const gf* src, size_t src_block_
     return guarded([&] {
         return run_repair(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,
                           present, targets, ntargets, npatterns, pattern_of, idev, sz, nstripes, stream, flags);
+    });
+}
+
+// ---- ragged repair: a size and a pattern per stripe ------------------------------------------
+namespace {
+int run_repair_ragged(const RaggedCall& c, const fec_t* code, const unsigned* present, const unsigned* targets,
+                      size_t nt, size_t npatterns, const unsigned* pattern_of, int idev, int ddev) {
+    const unsigned k = code->k;
+    const size_t ns = c.nstripes;
+    // device memory on one device, or page-locked host memory (read and written in place)
+    const BatchBuf bufs[2] = {{c.src, c.src_bytes, "src"}, {c.dst, c.dst_bytes, "dst"}};
+    BatchMem mem;
+    if (resolve_batch(mem, c.fn, bufs, 2, "sizes", ddev, c.stream, c.flags, kCaptureRagged)) return t_status;
+    if (idev >= 0 && idev != mem.dev)
+        return set_status(FEC_EINVAL, "%s: pattern_of lives on device %d, the blocks on device %d", c.fn, idev,
+                          mem.dev);
+    const gf* const zsrc = mem.z[0];
+    gf* const zdst = const_cast<gf*>(mem.z[1]);
+    hipStream_t st = mem.st;
+    hipError_t e;
+    const unsigned r = static_cast<unsigned>(nt);
+    if (k <= kMixedMaxK) {
+        thread_local std::vector<uint8_t> rows;
+        thread_local std::vector<uint32_t> masks;
+        rows.resize(npatterns * nt * k);
+        masks.resize(npatterns);
+        for (size_t p = 0; p < npatterns; ++p)
+            if (repair_rows(code, present + p * k, targets + p * nt, nt, &rows[p * nt * k], &masks[p]))
+                return t_status;
+        RaggedRepairSpec g;
+        g.k = k;
+        g.t = r;
+        g.rows = rows.data();
+        g.masks = masks.data();
+        g.npatterns = static_cast<uint32_t>(npatterns);
+        g.ids_host = pattern_of && idev < 0 ? pattern_of : nullptr;
+        g.ids_dev = pattern_of && idev >= 0 ? pattern_of : nullptr;
+        g.in = zsrc;
+        g.out = zdst;
+        g.in_bytes = c.src_bytes;
+        g.out_bytes = c.dst_bytes;
+        g.in_bstride = c.sbs;
+        g.out_bstride = c.dbs;
+        g.sizes = reinterpret_cast<const uint64_t*>(c.sizes);
+        g.in_off = reinterpret_cast<const uint64_t*>(c.soff);
+        g.out_off = reinterpret_cast<const uint64_t*>(c.doff);
+        g.desc_host = ddev < 0;
+        g.nstripes = ns;
+        ++t_launches;
+        if ((e = launch_ragged_repair(g, st)) != hipSuccess) return hip_fail(e, "launch_ragged_repair");
+    } else {
+        // wider codes: runs of consecutive stripes of one size and one pattern id whose two
+        // offsets each advance by a constant, each run one shared-matrix application of that
+        // pattern's live rows.  Device-side arrays come to the host first (a stream sync).
+        const unsigned long long *sizes = c.sizes, *soff = c.soff, *doff = c.doff;
+        const unsigned* ids = pattern_of;
+        thread_local std::vector<unsigned long long> hd;
+        thread_local std::vector<unsigned> hids;
+        bool synced = true;
+        if (ddev >= 0) {
+            hd.resize(3 * ns);
+            const unsigned long long* from[3] = {c.sizes, c.soff, c.doff};
+            for (int i = 0; i < 3; ++i)
+                if ((e = hipMemcpyAsync(&hd[i * ns], from[i], ns * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                        st)) != hipSuccess)
+                    return hip_fail(e, "hipMemcpyAsync D2H (descriptor arrays)");
+            sizes = hd.data();
+            soff = sizes + ns;
+            doff = soff + ns;
+            synced = false;
+        }
+        if (pattern_of && idev >= 0) {
+            hids.resize(ns);
+            if ((e = hipMemcpyAsync(hids.data(), pattern_of, ns * sizeof(unsigned), hipMemcpyDeviceToHost, st)) !=
+                hipSuccess)
+                return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
+            ids = hids.data();
+            synced = false;
+        }
+        if (!synced && (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+        const auto id_of = [&](size_t s) { return ids ? ids[s] : 0u; };
+        const auto live = [&](size_t s) {
+            return sizes[s] && id_of(s) < npatterns && ragged_stripe_fits(c, k, r, sizes, soff, doff, s);
+        };
+        typedef std::pair<std::vector<uint8_t>, uint32_t> RowsAndMask;
+        std::unordered_map<unsigned, RowsAndMask> cache;
+        for (size_t s0 = 0; s0 < ns;) {
+            if (!live(s0)) {  // empty, or (device-side arrays) unfit or a bad id: neither read nor written
+                ++s0;
+                continue;
+            }
+            const size_t sz = sizes[s0];
+            const unsigned id = id_of(s0);
+            const auto same = [&](size_t s) { return sizes[s] == sz && id_of(s) == id && live(s); };
+            size_t s1 = s0 + 1, dsrc = 0, ddst = 0;
+            if (s1 < ns && soff[s1] > soff[s0] && doff[s1] > doff[s0] && same(s1)) {
+                dsrc = soff[s1] - soff[s0];
+                ddst = doff[s1] - doff[s0];
+                ++s1;
+                while (s1 < ns && soff[s1] > soff[s1 - 1] && soff[s1] - soff[s1 - 1] == dsrc &&
+                       doff[s1] > doff[s1 - 1] && doff[s1] - doff[s1 - 1] == ddst && same(s1))
+                    ++s1;
+            }
+            const auto ins = cache.try_emplace(id);
+            RowsAndMask& pr = ins.first->second;
+            if (ins.second) {
+                pr.first.resize(nt * k);
+                if (repair_rows(code, present + size_t(id) * k, targets + size_t(id) * nt, nt, pr.first.data(),
+                                &pr.second))
+                    return t_status;
+            }
+            if (repair_shared(pr.first.data(), pr.second, k, nt, zsrc + soff[s0], c.sbs ? c.sbs : sz, dsrc,
+                              zdst + doff[s0], c.dbs ? c.dbs : sz, ddst, sz, s1 - s0, st))
+                return t_status;
+            s0 = s1;
+        }
+    }
+    if (!(c.flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_repair_batch_ragged(const fec_t* code, const gf* src, size_t src_bytes, size_t src_block_stride,
+                                    const unsigned long long* src_offsets, gf* dst, size_t dst_bytes,
+                                    size_t dst_block_stride, const unsigned long long* dst_offsets,
+                                    const unsigned long long* sizes, const unsigned* present,
+                                    const unsigned* targets, size_t ntargets, size_t npatterns,
+                                    const unsigned* pattern_of, size_t nstripes, void* stream, unsigned flags) {
+    const RaggedCall c{"fec_repair_batch_ragged", src,         src_bytes, src_block_stride, src_offsets, dst,
+                       dst_bytes,                 dst_block_stride, dst_offsets, sizes,     nstripes,    stream,
+                       flags};
+    // fec_repair_batch's checks of the code and the pattern arguments, in its order
+    const auto pattern_args = [&]() -> int {
+        if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+        if (!src || !dst) return set_status(FEC_EINVAL, "NULL buffer");
+        if (!present) return set_status(FEC_EINVAL, "present is NULL");
+        if (!targets) return set_status(FEC_EINVAL, "targets is NULL");
+        if (ntargets == 0 || ntargets > kRepairMaxRows)
+            return set_status(FEC_EINVAL, "ntargets is %zu: a call takes between 1 and %u targets per stripe",
+                              ntargets, unsigned(kRepairMaxRows));
+        if (npatterns == 0 && nstripes > 0)
+            return set_status(FEC_EINVAL, "npatterns is 0: stripe 0 of %zu has no pattern", nstripes);
+        if (npatterns > kMixedMaxPatterns)
+            return set_status(FEC_EINVAL, "%zu patterns: a call takes at most %u", npatterns,
+                              unsigned(kMixedMaxPatterns));
+        if (!pattern_of && npatterns != 1)
+            return set_status(FEC_EINVAL, "pattern_of is NULL with %zu patterns: without ids every stripe uses "
+                                          "pattern 0, so npatterns must be 1", npatterns);
+        return check_repair_patterns(code, present, targets, ntargets, npatterns);
+    };
+    if (pattern_args()) {
+        const std::string msg = t_msg;
+        return set_status(t_status, "%s: %s", c.fn, msg.c_str());
+    }
+    for (const auto& a : {std::make_pair(static_cast<const void*>(sizes), "sizes"),
+                          std::make_pair(static_cast<const void*>(src_offsets), "src_offsets"),
+                          std::make_pair(static_cast<const void*>(dst_offsets), "dst_offsets")})
+        if (!a.first) return set_status(FEC_EINVAL, "%s: %s is NULL", c.fn, a.second);
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        int ddev = -1;
+        if (check_ragged_kinds(c, &ddev)) return t_status;
+        const int idev = gpu_available() && pattern_of ? pointer_device(pattern_of) : -1;
+        if (pattern_of && idev < 0)
+            for (size_t s = 0; s < nstripes; ++s)
+                if (pattern_of[s] >= npatterns)
+                    return set_status(FEC_EINVAL, "%s: stripe %zu: pattern id %u out of range (npatterns = %zu)",
+                                      c.fn, s, pattern_of[s], npatterns);
+        if (check_ragged_fit(c, code->k, static_cast<unsigned>(ntargets), ddev)) return t_status;
+        if (!gpu_available()) return no_gpu();
+        return run_repair_ragged(c, code, present, targets, ntargets, npatterns, pattern_of, idev, ddev);
     });
 }
 

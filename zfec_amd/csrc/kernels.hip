@@ -49,6 +49,12 @@
 //   matrepair_mixed<K, R> matapply_mixed with R rows per pattern instead of K, each
 //                       row stored only where its pattern's live-row mask says
 //                       so (fec_repair_batch).
+//   matrepair_ragged<K, R>, matcorrect_ragged<K>
+//                       matapply_ragged's walk around matrepair_mixed's per-stripe
+//                       record (a size AND a pattern per stripe) and around
+//                       matcorrect_reg's unit, the stripe's verdict read with its
+//                       descriptor (fec_repair_batch_ragged /
+//                       fec_correct_batch_ragged).
 //   matapply_lds        any k <= 32, r <= 48 (longer codes are split by the
 //                       caller): each workgroup expands its coefficients into
 //                       LDS tables from a compile-time bank of all 256 values;
@@ -2089,6 +2095,306 @@ __global__ __launch_bounds__(kBlock) void rows_correct(const CorrectJob job) {
         if (w >= job.wps) {
             w -= job.wps;
             ++s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// matrepair_ragged<K, R>: a batched repair whose stripes each have their own
+// size AND their own pattern (fec_repair_batch_ragged), k <= 4 and up to 8
+// output rows per launch.  Two kernels joined.
+//
+// The walk is matapply_ragged's: 1 KiB units, T split over the launched waves
+// by the shard_range rule, one binary search over ustart per wave, the
+// stripe's size and two offsets by scalar loads through constant-address-space
+// pointers with the next stripe's requested early, zero-size stripes passed
+// over, the fit test on both arenas (over ALL the call's rows, stored or not),
+// 64-bit addresses, ragged_span's overlapped last chunk and the byte tail.
+//
+// The per-stripe matrix is matrepair_mixed's: the stripe's pattern id is read
+// with its descriptor and formed through readfirstlane, so the record address
+// and the live-row mask are wave-uniform; each live row's tables come by scalar
+// loads where they are used (the empty asm on the record pointer keeps at most
+// two rows' tables in SGPRs), and a row whose mask bit is clear is a scalar
+// branch around load, arithmetic and store.  The record layout is
+// repair_fill_records', unchanged.  An id >= npatterns, a stripe that does not
+// fit, or one none of whose rows in this launch is live is neither read nor
+// written.
+//
+// A wave's range crosses stripes: id, record pointer and mask are formed anew
+// at every stripe boundary, inside the stripe's own scope -- nothing carries
+// from one stripe to the next.  Stores are store16_pol<0> and store_tail,
+// plain vector stores.  Records, ids and descriptors are written before the
+// launch (a copy, ragged_scan or the caller's earlier work in the stream),
+// never by this kernel, so the scalar reads are coherent.
+// ---------------------------------------------------------------------------
+struct alignas(16) RaggedRepairJob {
+    uint64_t in_bstride, out_bstride;  // 0: the stripe's own size (packed objects)
+    uint64_t in_bytes, out_bytes;      // extents of the two arenas
+    uint32_t nstripes;
+    uint32_t rows_all;  // targets per stripe of the whole call (the fit test)
+    uint32_t row0;      // this launch takes rows row0 .. row0 + R: its first mask bit
+    uint32_t npatterns;
+    uint32_t rec_dwords;  // dwords per pattern record
+    uint32_t tab_off;     // dword offset in a record of this launch's first row
+    uint32_t mask_off;    // dword offset in a record of the live-row mask
+    uint32_t pad_;
+    const uint64_t* ustart;  // nstripes + 1
+    const uint64_t* sizes;
+    const uint64_t* in_off;
+    const uint64_t* out_off;
+    const uint32_t* records;  // npatterns x rec_dwords
+    const uint32_t* ids;      // nstripes pattern ids
+    const uint8_t* in;
+    uint8_t* out;
+};
+
+struct RepairStripe {
+    uint64_t u0, u1;  // its units: [u0, u1)
+    uint64_t sz, ioff, ooff;
+    uint32_t id;
+};
+
+__device__ __forceinline__ RepairStripe repair_stripe(const RaggedRepairJob& job, uint32_t s) {
+    const CU64 us = (CU64)job.ustart;
+    return RepairStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.in_off)[s], ((CU64)job.out_off)[s],
+                        ((CU32)job.ids)[s]};
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matrepair_ragged(const RaggedRepairJob job) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t G = gridDim.x * (kBlock / 64);
+    const CU64 us = (CU64)job.ustart;
+    const uint32_t ns = job.nstripes;
+    const uint64_t total = us[ns];
+    // (a launch with a wave per unit or more needs no division)
+    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
+    uint64_t u = uniform64(g * q + (g < e ? g : e));
+    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
+    if (u >= end) return;
+    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (us[mid] <= u)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
+    RepairStripe cur = repair_stripe(job, s);
+    for (;;) {
+        RepairStripe nxt = cur;
+        if (s + 1 < ns) nxt = repair_stripe(job, s + 1);
+        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+        const uint64_t sz = cur.sz;
+        const uint64_t ib = job.in_bstride ? job.in_bstride : sz, ob = job.out_bstride ? job.out_bstride : sz;
+        const uint32_t id = __builtin_amdgcn_readfirstlane(cur.id);
+        // the launch's record geometry is read from the argument segment where a stripe needs
+        // it, not kept in SGPRs across the walk
+        const KPtr<RaggedRepairJob> kj = kernarg_job<RaggedRepairJob>();
+        if (u < stop && id < kj->npatterns && ragged_fits(cur.ioff, ib, K, sz, job.in_bytes) &&
+            ragged_fits(cur.ooff, ob, job.rows_all, sz, job.out_bytes)) {
+            // this stripe's record, mask and table pointer: formed here, dead at the closing brace
+            const CU32 rp = (CU32)kj->records + size_t(id) * kj->rec_dwords;
+            const uint32_t row0 = kj->row0;
+            const uint32_t smask = (__builtin_amdgcn_readfirstlane(rp[kj->mask_off]) >> row0) & ((1u << R) - 1u);
+            if (smask != 0u) {  // wave-uniform: a stripe with no live row here is not read
+                CU32 tp = rp + kj->tab_off;
+                const uint8_t* const in0 = job.in + cur.ioff;
+                uint8_t* const out0 = job.out + cur.ooff + row0 * ob;
+                const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
+                for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
+                    // opaque per unit: the R row tests stay bit tests of one SGPR here; hoisted
+                    // out of the unit loop each would live in an SGPR pair of its own
+                    uint32_t mask = smask;
+                    asm volatile("" : "+s"(mask));
+                    const uint64_t c = w * 64u + lane;
+                    const bool live = c < cps;
+                    const Span sp = ragged_span(c, sz, nfull);
+                    u32x4 x[K];
+#pragma unroll
+                    for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+                    if (live) {
+                        // the slot address advances per lane (next_row): the multiples j * ib as
+                        // wave-uniform values would live across the unit loop (<4,2> and up re-read
+                        // one from a VGPR lane per unit)
+                        const uint8_t* row = in0 + sp.off;
+                        if (sp.full) {
+#pragma unroll
+                            for (int j = 0; j < K; ++j, row = next_row(row, ib)) x[j] = load16(row);
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < K; ++j, row = next_row(row, ib)) x[j] = load_tail(row, sp.nb);
+                        }
+                    }
+                    Sel sel[4][K];
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        sel[0][j] = selectors(x[j].x);
+                        sel[1][j] = selectors(x[j].y);
+                        sel[2][j] = selectors(x[j].z);
+                        sel[3][j] = selectors(x[j].w);
+                    }
+                    // the row address advances per lane, as matapply_ragged's does
+                    uint8_t* orow = out0 + sp.off;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        if ((mask >> r) & 1u) {  // wave-uniform: a scalar branch
+                            asm volatile("" : "+s"(tp));
+                            Tab t[K];
+#pragma unroll
+                            for (int j = 0; j < K; ++j) {
+                                const uint32_t i = (r * K + j) * 5;
+                                t[j] = Tab{tp[i], tp[i + 1], tp[i + 2], tp[i + 3], tp[i + 4]};
+                            }
+                            const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]),
+                                          gf_dot<K>(t, sel[3])};
+                            if (live) {
+                                if (sp.full)
+                                    store16_pol<0>(orow, y);
+                                else
+                                    store_tail(orow, y, sp.nb);
+                            }
+                        }
+                        orow += ob;
+                    }
+                }
+            }
+        }
+        u = stop;
+        if (u >= end || s + 1 >= ns) break;
+        ++s;
+        cur = nxt;
+        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
+            ++s;
+            cur = repair_stripe(job, s);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// matcorrect_ragged<K>: in-place correction of a batch whose stripes each have
+// their own size (fec_correct_batch_ragged), k = K <= 4, over the verdict words
+// locate_finish and ragged_unfit wrote earlier in the stream -- never this
+// kernel, so the scalar reads of them are coherent.  The walk is
+// matapply_ragged's, over the ustart the location staged; the stripe's verdict
+// h is read with its descriptor by a scalar load.  Unless h names a slot AND
+// the stripe passes this kernel's own fit test over all nb slots (it does not
+// rely on the UNFIT verdict), a scalar branch goes around the whole stripe: a
+// clean stripe costs scalar loads and no vector memory instruction.
+//
+// For a slot verdict the body is matcorrect_reg's: source l is slot
+// (l == h ? K : l), record h of the fec_correct_rows tables comes by scalar
+// loads, one store per lane (byte by byte below a chunk, so no byte past
+// sizes[s] of slot h is written: in a packed object that byte is slot h + 1's
+// or the next stripe's).  The target is never among its sources.  Hence a
+// stripe split between two waves, and the overlapped last chunk's two lanes,
+// write identical bytes and read none that are written: no order between
+// them is needed.
+// ---------------------------------------------------------------------------
+struct alignas(16) RaggedCorrectJob {
+    uint64_t bstride;  // 0: the stripe's own size (packed objects)
+    uint64_t bytes;    // extent of the arena
+    uint32_t nstripes;
+    uint32_t nb;  // slots per stripe
+    const uint64_t* ustart;  // nstripes + 1
+    const uint64_t* sizes;
+    const uint64_t* off;
+    const uint32_t* tabs;     // nb records of K * 5 dwords
+    const uint32_t* verdict;  // nstripes verdict words
+    uint8_t* blocks;
+};
+
+struct CorrectStripe {
+    uint64_t u0, u1;  // its units: [u0, u1)
+    uint64_t sz, off;
+    uint32_t h;
+};
+
+__device__ __forceinline__ CorrectStripe correct_stripe(const RaggedCorrectJob& job, uint32_t s) {
+    const CU64 us = (CU64)job.ustart;
+    return CorrectStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.off)[s], ((CU32)job.verdict)[s]};
+}
+
+template <int K>
+__global__ __launch_bounds__(kBlock) void matcorrect_ragged(const RaggedCorrectJob job) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t G = gridDim.x * (kBlock / 64);
+    const CU64 us = (CU64)job.ustart;
+    const uint32_t ns = job.nstripes;
+    const uint64_t total = us[ns];
+    // (a launch with a wave per unit or more needs no division)
+    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
+    uint64_t u = uniform64(g * q + (g < e ? g : e));
+    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
+    if (u >= end) return;
+    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (us[mid] <= u)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
+    CorrectStripe cur = correct_stripe(job, s);
+    for (;;) {
+        CorrectStripe nxt = cur;
+        if (s + 1 < ns) nxt = correct_stripe(job, s + 1);
+        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+        const uint64_t sz = cur.sz;
+        const uint64_t B = job.bstride ? job.bstride : sz;
+        const uint32_t h = __builtin_amdgcn_readfirstlane(cur.h);
+        // wave-uniform: a scalar branch, not taken on clean data
+        if (h < job.nb && u < stop && ragged_fits(cur.off, B, job.nb, sz, job.bytes)) {
+            // the tables' base is read from the argument segment here, where a dirty stripe needs it
+            uint8_t* const base = job.blocks + cur.off;
+            CU32 tp = (CU32)kernarg_job<RaggedCorrectJob>()->tabs + size_t(h) * (K * 5);
+            const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
+            for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
+                const uint64_t c = w * 64u + lane;
+                const bool live = c < cps;
+                const Span sp = ragged_span(c, sz, nfull);
+                u32x4 x[K];
+#pragma unroll
+                for (int l = 0; l < K; ++l) {
+                    const uint32_t slot =
+                        static_cast<uint32_t>(l) == h ? static_cast<uint32_t>(K) : static_cast<uint32_t>(l);
+                    x[l] = load_unit(base + slot * B + sp.off, live, sp);
+                }
+                asm volatile("" : "+s"(tp));  // the tables are read per unit, not held across the walk
+                Tab t[K];
+#pragma unroll
+                for (int l = 0; l < K; ++l)
+                    t[l] = Tab{tp[l * 5], tp[l * 5 + 1], tp[l * 5 + 2], tp[l * 5 + 3], tp[l * 5 + 4]};
+                Sel sel[4][K];
+#pragma unroll
+                for (int l = 0; l < K; ++l) {
+                    sel[0][l] = selectors(x[l].x);
+                    sel[1][l] = selectors(x[l].y);
+                    sel[2][l] = selectors(x[l].z);
+                    sel[3][l] = selectors(x[l].w);
+                }
+                const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]), gf_dot<K>(t, sel[3])};
+                if (live) {
+                    uint8_t* const out = base + h * B + sp.off;
+                    if (sp.full)
+                        store16_pol<0>(out, y);
+                    else
+                        store_tail(out, y, sp.nb);
+                }
+            }
+        }
+        u = stop;
+        if (u >= end || s + 1 >= ns) break;
+        ++s;
+        cur = nxt;
+        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
+            ++s;
+            cur = correct_stripe(job, s);
         }
     }
 }
@@ -5396,6 +5702,130 @@ hipError_t launch_ragged_scrub_all(const RaggedScrubSpec& p, hipStream_t stream)
         e = p.Q ? g_ragged_locate_launch(p.k, rg)(p, d, g0, grid, stream)
                 : g_ragged_verify_launch(p.k, rg)(p, d, g0, grid, stream);
     }
+    if (p.keep && e == hipSuccess) {
+        // a correction follows over the same descriptors: it releases the slot (ragged_scrub_release)
+        *p.keep = RaggedScrubStaged{up.slot, d.ustart, d.sizes, d.off, units};
+        return e;
+    }
+    up.done(stream);
+    return e;
+}
+
+// ---- matrepair_ragged dispatch ----------------------------------------------------------
+// The six arrays of a ragged repair in device memory.
+struct RepairDev {
+    const uint64_t *ustart, *sizes, *in_off, *out_off;
+    const uint32_t *records, *ids;
+};
+
+const KrNames g_ragged_repair_names("matrepair_ragged");
+
+// Rows [g0, g0 + R) of every stripe.
+struct RaggedRepairKr {
+    template <int K, int R>
+    static hipError_t launch(const RaggedRepairSpec& p, const RepairDev& d, uint32_t g0, uint32_t grid,
+                             hipStream_t stream) {
+        RaggedRepairJob job;
+        job.in_bstride = p.in_bstride;
+        job.out_bstride = p.out_bstride;
+        job.in_bytes = p.in_bytes;
+        job.out_bytes = p.out_bytes;
+        job.nstripes = static_cast<uint32_t>(p.nstripes);
+        job.rows_all = p.t;
+        job.row0 = g0;
+        job.npatterns = p.npatterns;
+        job.rec_dwords = repair_rec_dwords(K, p.t);
+        job.tab_off = g0 * K * 5;
+        job.mask_off = p.t * K * 5;
+        job.pad_ = 0;
+        job.ustart = d.ustart;
+        job.sizes = d.sizes;
+        job.in_off = d.in_off;
+        job.out_off = d.out_off;
+        job.records = d.records;
+        job.ids = d.ids;
+        job.in = p.in;
+        job.out = p.out;
+        const hipError_t e =
+            launch_job(reinterpret_cast<const void*>(matrepair_ragged<K, R>), grid, kBlock, 0, stream, job);
+        if (e == hipSuccess) t_last_kernel = g_ragged_repair_names.name[K][R];
+        return e;
+    }
+};
+constexpr KrTable<RaggedRepairKr> g_ragged_repair_launch;
+
+// One MixedRing slot per call: [records | ids (host-side or none given) |
+// ustart | sizes | in_off | out_off] by one copy with host-side descriptors;
+// with device-side ones [records | ids] by one copy and ragged_scan's ustart
+// behind them in the slot's device half (launch_ragged_all).  The grid rule is
+// matapply_ragged's, ceil(10 / (k + r)) units per wave, r the most live rows
+// any pattern has within the launch's row group; a row group no pattern uses
+// is skipped.
+hipError_t launch_ragged_repair_all(const RaggedRepairSpec& p, hipStream_t stream) {
+    const uint64_t ns = p.nstripes;
+    const uint32_t k = p.k, t = p.t;
+    const uint32_t any = repair_any(p.masks, p.npatterns, t);
+    if (!any) return hipSuccess;  // nothing to store: no upload, no launch
+    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
+    const size_t tab_bytes = (size_t(p.npatterns) * repair_rec_dwords(k, t) * 4 + 255) / 256 * 256;
+    const bool stage_ids = !p.ids_dev;  // host-side ids, or none: every stripe pattern 0
+    const size_t ids_bytes = stage_ids ? (size_t(ns) * 4 + 255) / 256 * 256 : 0;
+    const size_t head = tab_bytes + ids_bytes;
+    StagedUpload up;
+    RepairDev d;
+    hipError_t e;
+    uint64_t units;  // of the whole call, or (device arrays) a bound on them
+    const auto fill_head = [&] {
+        repair_fill_records(reinterpret_cast<uint32_t*>(up.host()), p.rows, p.masks, p.npatterns, k, t);
+        if (!stage_ids) return;
+        if (p.ids_host)
+            std::memcpy(up.host() + tab_bytes, p.ids_host, size_t(ns) * 4);
+        else
+            std::memset(up.host() + tab_bytes, 0, size_t(ns) * 4);
+    };
+    if (p.desc_host) {
+        const size_t bytes = head + (4 * ns + 1) * sizeof(uint64_t);
+        if ((e = up.acquire(bytes)) != hipSuccess) return e;
+        uint64_t* h = reinterpret_cast<uint64_t*>(up.host() + head);
+        const uint64_t total = ragged_units(p.sizes, ns, h);
+        if (!total) return hipSuccess;  // every stripe is empty: nothing copied, nothing launched
+        fill_head();
+        std::memcpy(h + ns + 1, p.sizes, ns * sizeof(uint64_t));
+        std::memcpy(h + 2 * ns + 1, p.in_off, ns * sizeof(uint64_t));
+        std::memcpy(h + 3 * ns + 1, p.out_off, ns * sizeof(uint64_t));
+        if ((e = up.copy(bytes, stream)) != hipSuccess) return e;
+        const uint64_t* dv = reinterpret_cast<const uint64_t*>(up.dev() + head);
+        d = RepairDev{dv, dv + ns + 1, dv + 2 * ns + 1, dv + 3 * ns + 1, nullptr, nullptr};
+        units = total;
+    } else {
+        // an estimate sizes the grid (launch_ragged_all): blocks do not overlap
+        const uint64_t in_units = p.in_bytes / (p.in_bstride ? 1 : k) / kRaggedUnit;
+        const uint64_t out_units = p.out_bytes / (p.out_bstride ? 1 : t) / kRaggedUnit;
+        units = std::max<uint64_t>(1, std::min(in_units, out_units));
+        const uint64_t ntiles = (ns + kScanTile - 1) / kScanTile;
+        if ((e = up.acquire(head + (ns + 1 + ntiles) * sizeof(uint64_t))) != hipSuccess) return e;
+        fill_head();
+        if ((e = up.copy(head, stream)) != hipSuccess) return e;
+        uint64_t* dv = reinterpret_cast<uint64_t*>(up.slot->dev + head);
+        e = launch_ragged_scan(p.sizes, ns, p.in_bytes < p.out_bytes ? p.in_bytes : p.out_bytes, dv, dv + ns + 1,
+                               stream);
+        if (e != hipSuccess) {
+            up.done(stream);
+            return e;
+        }
+        d = RepairDev{dv, p.sizes, p.in_off, p.out_off, nullptr, nullptr};
+    }
+    d.records = reinterpret_cast<const uint32_t*>(up.dev());
+    d.ids = stage_ids ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : p.ids_dev;
+    for (uint32_t g0 = 0; g0 < t && e == hipSuccess; g0 += kRegR) {
+        const uint32_t rg = std::min<uint32_t>(kRegR, t - g0);
+        uint32_t rmax = 0;  // the most live rows any pattern has in this group
+        for (size_t q = 0; q < p.npatterns; ++q)
+            rmax = std::max<uint32_t>(rmax, __builtin_popcount((p.masks[q] >> g0) & ((1u << rg) - 1u)));
+        if (!rmax) continue;  // rows no pattern stores
+        const uint64_t per_wg = ragged_units_per_wave(k, rmax) * (kBlock / 64), need = (units + per_wg - 1) / per_wg;
+        e = g_ragged_repair_launch(k, rg)(p, d, g0, static_cast<uint32_t>(need < cap ? need : cap), stream);
+    }
     up.done(stream);
     return e;
 }
@@ -5968,6 +6398,65 @@ hipError_t launch_ragged_unfit(const uint64_t* sizes, const uint64_t* off, uint6
     job.c = c;
     const uint32_t grid = static_cast<uint32_t>((nstripes + kBlock - 1) / kBlock);
     return launch_job(reinterpret_cast<const void*>(ragged_unfit), grid, kBlock, 0, stream, job);
+}
+
+hipError_t launch_ragged_repair(const RaggedRepairSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (p.k < 1 || p.k > static_cast<uint32_t>(kRegK) || p.t < 1 || p.t > kRepairMaxRows || p.npatterns < 1 ||
+        p.npatterns > kMixedMaxPatterns || !p.rows || !p.masks || (p.ids_host && p.ids_dev) ||
+        (!p.ids_host && !p.ids_dev && p.npatterns != 1) || !p.in || !p.out || !p.sizes || !p.in_off || !p.out_off ||
+        p.nstripes == 0 || p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    return launch_ragged_repair_all(p, stream);
+}
+
+void ragged_scrub_release(const RaggedScrubStaged& t, hipStream_t stream) {
+    if (t.slot) StagedUpload{static_cast<Slot*>(t.slot)}.done(stream);
+}
+
+// ---- matcorrect_ragged dispatch ---------------------------------------------------------
+hipError_t launch_ragged_correct(const RaggedCorrectSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (p.k < 1 || p.k > static_cast<uint32_t>(kRegK) || p.nb <= p.k || p.nb > 256 || !p.rows || !p.verdict ||
+        !p.blocks || !p.staged.ustart || !p.staged.sizes || !p.staged.off || p.nstripes == 0 ||
+        p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    static const char* const kNames[kRegK + 1] = {"", "matcorrect_ragged<1>", "matcorrect_ragged<2>",
+                                                  "matcorrect_ragged<3>", "matcorrect_ragged<4>"};
+    static const void* const kFns[kRegK + 1] = {nullptr, reinterpret_cast<const void*>(matcorrect_ragged<1>),
+                                                reinterpret_cast<const void*>(matcorrect_ragged<2>),
+                                                reinterpret_cast<const void*>(matcorrect_ragged<3>),
+                                                reinterpret_cast<const void*>(matcorrect_ragged<4>)};
+    StagedUpload up;
+    hipError_t e = upload_tabs(up, p.rows, size_t(p.nb) * p.k, stream);
+    if (e != hipSuccess) return e;
+    RaggedCorrectJob job;
+    job.bstride = p.bstride;
+    job.bytes = p.bytes;
+    job.nstripes = static_cast<uint32_t>(p.nstripes);
+    job.nb = p.nb;
+    job.ustart = p.staged.ustart;
+    job.sizes = p.staged.sizes;
+    job.off = p.staged.off;
+    job.tabs = reinterpret_cast<const uint32_t*>(up.dev());
+    job.verdict = p.verdict;
+    job.blocks = p.blocks;
+    // Not matapply_ragged's rule: a unit of a clean stripe moves no bytes, so a wave that owns few
+    // units only pays for its search over ustart.  On 10^6 clean stripes of 4 KiB the call took 1.12 x
+    // fec_correct_batch with 3 units per wave and 1.01 x with 48 (a ZFEC_HIP_GRID_CAP sweep that
+    // slowed the location too), with every stripe corrupt 1.09 x and 1.05 x.
+    constexpr uint64_t kCorrectUnitsPerWave = 48;
+    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
+    const uint64_t per_wg = kCorrectUnitsPerWave * (kBlock / 64);
+    const uint64_t need = (std::max<uint64_t>(1, p.staged.units) + per_wg - 1) / per_wg;
+    e = launch_job(kFns[p.k], static_cast<uint32_t>(need < cap ? need : cap), kBlock, 0, stream, job);
+    up.done(stream);
+    if (e == hipSuccess) t_last_kernel = kNames[p.k];
+    return e;
 }
 
 int generic_mode() {

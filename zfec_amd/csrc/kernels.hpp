@@ -379,6 +379,17 @@ hipError_t launch_ragged(const RaggedSpec& g, hipStream_t stream);
 // check bits of its ceil(c / 32) words at out + s * words, or with c == 0 the
 // verdict FEC_LOCATE_UNFIT at out + s.  Plain stores; it stages nothing and
 // leaves matapply_last_kernel() as it was.
+//
+// keep (may be null): where a correction follows the location, the staged
+// descriptors stay valid past the call -- ustart, sizes and offsets in device
+// memory, and the units that sized the grid -- until ragged_scrub_release,
+// which records the slot's event after the last launch that reads them.  It is
+// left with a null slot where nothing was launched (every stripe empty).
+struct RaggedScrubStaged {
+    void* slot = nullptr;
+    const uint64_t *ustart = nullptr, *sizes = nullptr, *off = nullptr;
+    uint64_t units = 0;
+};
 struct RaggedScrubSpec {
     uint32_t k, c;
     const uint8_t* P;    // c x k coefficients, row-major (host memory)
@@ -390,10 +401,63 @@ struct RaggedScrubSpec {
     uint64_t nstripes;
     uint32_t* bits;
     uint32_t words, xbit;
+    RaggedScrubStaged* keep = nullptr;
 };
 hipError_t launch_ragged_scrub(const RaggedScrubSpec& p, hipStream_t stream);
 hipError_t launch_ragged_unfit(const uint64_t* sizes, const uint64_t* off, uint64_t nstripes, uint32_t slots,
                                uint64_t bstride, uint64_t bytes, uint32_t c, uint32_t* out, hipStream_t stream);
+void ragged_scrub_release(const RaggedScrubStaged& t, hipStream_t stream);
+
+// The in-place correction of such a batch (matcorrect_ragged<K>, k <= 4;
+// fec_correct_batch_ragged) over the verdict words launch_locate_finish and
+// launch_ragged_unfit wrote, in device memory, and the descriptors a location
+// with `keep` staged: a stripe whose verdict h is below nb, and which fits the
+// arena by the kernel's own test over all nb slots, has the sizes[s] bytes of
+// slot h rewritten as row h of `rows` (nb x k, host memory) applied to slots
+// 0..k-1, slot k taking slot h's place when h < k.  Every other stripe costs
+// scalar loads and is neither read nor written.  The tables go through a
+// staging slot of their own (hipErrorNotSupported under capture).  The caller
+// releases `staged` afterwards.
+struct RaggedCorrectSpec {
+    uint32_t k, nb;
+    const uint8_t* rows;  // nb x k coefficients (host memory)
+    uint8_t* blocks;      // the arena, a kernel-visible address
+    uint64_t bytes, bstride;
+    uint64_t nstripes;
+    const uint32_t* verdict;  // nstripes words, device memory
+    RaggedScrubStaged staged;
+};
+hipError_t launch_ragged_correct(const RaggedCorrectSpec& p, hipStream_t stream);
+
+// A batched repair whose stripes each have their own size and their own
+// pattern (matrepair_ragged<K, R>, k <= 4; fec_repair_batch_ragged): the
+// arenas, descriptors, fit rule and units of launch_ragged, the patterns of
+// launch_repair.  Stripe s uses pattern ids[s]; with neither ids_host nor
+// ids_dev (npatterns == 1) every stripe uses pattern 0.  Row i of a stripe is
+// stored at out + out_off[s] + i * B' only where bit i of its pattern's mask
+// is set; the fit test covers all t rows.  A stripe that does not fit, or
+// whose id is >= npatterns, is neither read nor written.  More than 8 targets
+// run as row groups of 8 over one staging; a group no pattern uses is skipped,
+// and a call no pattern of which has a live row launches nothing.  One staging
+// slot holds records, host-side ids and host-side descriptors (one copy), or
+// records, host-side ids and ragged_scan's ustart; hipErrorNotSupported under
+// capture, hipErrorInvalidValue for other shapes (k > 4: the caller cuts runs).
+struct RaggedRepairSpec {
+    uint32_t k, t;
+    const uint8_t* rows;     // npatterns x t x k coefficients (host memory)
+    const uint32_t* masks;   // npatterns live-row masks (host memory)
+    uint32_t npatterns;
+    const uint32_t* ids_host;  // nstripes ids in host memory, or
+    const uint32_t* ids_dev;   // in device memory, or neither
+    const uint8_t* in;         // the two arenas, kernel-visible addresses
+    uint8_t* out;
+    uint64_t in_bytes, out_bytes;
+    uint64_t in_bstride, out_bstride;
+    const uint64_t *sizes, *in_off, *out_off;  // nstripes each
+    bool desc_host;
+    uint64_t nstripes;
+};
+hipError_t launch_ragged_repair(const RaggedRepairSpec& p, hipStream_t stream);
 
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
