@@ -69,33 +69,25 @@ asan: build/address/driver
 tsan: build/thread/driver
 	TSAN_OPTIONS="halt_on_error=0 second_deadlock_stack=1" ./build/thread/driver
 
-# The validation path of the ragged scrub calls (fec_verify_batch_ragged,
-# fec_locate_batch_ragged) under AddressSanitizer and UndefinedBehaviorSanitizer:
-# a stand-alone program, tests/c/ragged_scrub_validate.cpp, over the same host
-# objects; no GPU needed.
-SCRUBSAN := $(filter-out tests/c/sanitize_driver.cpp,$(SANSRC)) tests/c/ragged_scrub_validate.cpp
+# The validation paths of the ragged scrub calls (fec_verify_batch_ragged,
+# fec_locate_batch_ragged) and of fec_repair_batch_ragged and
+# fec_correct_batch_ragged under AddressSanitizer and
+# UndefinedBehaviorSanitizer: stand-alone programs,
+# tests/c/ragged_scrub_validate.cpp and tests/c/ragged_repair_validate.cpp, each
+# over the same host objects; no GPU needed.
+VALSRC := $(filter-out tests/c/sanitize_driver.cpp,$(SANSRC))
 
-build/scrub/validate: $(SCRUBSAN) $(SRC)/*.hpp include/zfec_hip.h
-	mkdir -p build/scrub
-	set -e; for f in $(SCRUBSAN); do \
-	  $(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=address,undefined -c $$f -o build/scrub/$$(basename $$f).o; done
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -fno-gpu-sanitize -o $@ build/scrub/*.o -ldl -lpthread
+build/scrub/validate build/repair/validate: build/%/validate: $(VALSRC) tests/c/ragged_%_validate.cpp $(SRC)/*.hpp \
+                                            include/zfec_hip.h
+	mkdir -p build/$*
+	set -e; for f in $(VALSRC) tests/c/ragged_$*_validate.cpp; do \
+	  $(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=address,undefined -c $$f -o build/$*/$$(basename $$f).o; done
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -fno-gpu-sanitize -o $@ build/$*/*.o -ldl -lpthread
 
 asan-scrub: build/scrub/validate
-	ASAN_OPTIONS=detect_leaks=0 ./build/scrub/validate
-
-# The same for the validation path of fec_repair_batch_ragged and
-# fec_correct_batch_ragged: tests/c/ragged_repair_validate.cpp.
-REPAIRSAN := $(filter-out tests/c/sanitize_driver.cpp,$(SANSRC)) tests/c/ragged_repair_validate.cpp
-
-build/repair/validate: $(REPAIRSAN) $(SRC)/*.hpp include/zfec_hip.h
-	mkdir -p build/repair
-	set -e; for f in $(REPAIRSAN); do \
-	  $(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=address,undefined -c $$f -o build/repair/$$(basename $$f).o; done
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -fno-gpu-sanitize -o $@ build/repair/*.o -ldl -lpthread
-
 asan-repair: build/repair/validate
-	ASAN_OPTIONS=detect_leaks=0 ./build/repair/validate
+asan-scrub asan-repair:
+	ASAN_OPTIONS=detect_leaks=0 ./$<
 
 # The no-GPU Python tests of the C-ABI (tests/test_cpu_surface.py: validation,
 # JIT registry from threads) against an AddressSanitizer build of the library,

@@ -1423,62 +1423,145 @@ int ragged_null(const RaggedCall& c, const void* nums, const char* nums_name) {
     return FEC_OK;
 }
 
-// Whether stripe s fits both arenas (kernels.hpp ragged_fits); *side: the one it does not.
-bool ragged_stripe_fits(const RaggedCall& c, unsigned k, unsigned r, const unsigned long long* sizes,
-                        const unsigned long long* soff, const unsigned long long* doff, size_t s,
-                        const char** side = nullptr) {
-    const uint64_t sz = sizes[s];
-    if (!ragged_fits(soff[s], c.sbs ? c.sbs : sz, k, sz, c.src_bytes)) {
-        if (side) *side = "src";
-        return false;
-    }
-    if (!ragged_fits(doff[s], c.dbs ? c.dbs : sz, r, sz, c.dst_bytes)) {
-        if (side) *side = "dst";
-        return false;
-    }
+// The descriptors of a ragged call, over one arena (the scrub calls) or two:
+// the arrays where the host reads them -- the caller's own, or fetch_desc's
+// copies -- and each arena as the messages name it.
+struct RaggedArena {
+    const char *name, *off_name, *bytes_name;
+    size_t bytes, bstride, rows;  // rows: blocks per stripe on this side
+};
+struct RaggedArgs {
+    const char* fn;
+    const char* mixed_kinds;  // the message for descriptor arrays of mixed memory kinds (one %s: fn)
+    int na;                   // arenas: 1 or 2
+    RaggedArena a[2];
+    size_t nstripes;
+    const unsigned long long* sizes;
+    const unsigned long long* off[2];
+    const unsigned* ids = nullptr;  // the repair's pattern ids, where given
+};
+
+RaggedArgs ragged_args(const RaggedCall& c, unsigned k, unsigned r) {
+    return RaggedArgs{c.fn,
+                      "%s: sizes, src_offsets and dst_offsets are of mixed memory kinds: all three in host memory, or "
+                      "all three in device memory on the blocks' device",
+                      2, {{"src", "src_offsets", "src_bytes", c.src_bytes, c.sbs, k},
+                                {"dst", "dst_offsets", "dst_bytes", c.dst_bytes, c.dbs, r}},
+                      c.nstripes, c.sizes, {c.soff, c.doff}};
+}
+
+// Whether stripe s fits every arena (kernels.hpp ragged_fits); *which: the first it does not.
+bool ragged_stripe_fits(const RaggedArgs& d, size_t s, int* which = nullptr) {
+    const uint64_t sz = d.sizes[s];
+    for (int i = 0; i < d.na; ++i)
+        if (!ragged_fits(d.off[i][s], d.a[i].bstride ? d.a[i].bstride : sz, static_cast<uint32_t>(d.a[i].rows), sz,
+                         d.a[i].bytes)) {
+            if (which) *which = i;
+            return false;
+        }
     return true;
 }
 
 // The checks of a ragged call that follow its block numbers, in the header's
-// order: the stripe count and the memory kind of the three descriptor arrays
+// order: the stripe count and the memory kind of the descriptor arrays
 // (check_ragged_kinds; *ddev: their device, -1 host memory), then with host
 // arrays every stripe's fit (check_ragged_fit).  fec_repair_batch_ragged checks
 // its host-side ids between the two.
-int check_ragged_kinds(const RaggedCall& c, int* ddev) {
-    if (uint64_t(c.nstripes) >= (1ull << 32))
-        return set_status(FEC_EINVAL, "%s: %zu stripes: a call takes fewer than 2^32", c.fn, c.nstripes);
+int check_ragged_kinds(const RaggedArgs& d, int* ddev) {
+    if (uint64_t(d.nstripes) >= (1ull << 32))
+        return set_status(FEC_EINVAL, "%s: %zu stripes: a call takes fewer than 2^32", d.fn, d.nstripes);
     int dv[3] = {-1, -1, -1};
-    if (gpu_available()) {
-        dv[0] = pointer_device(c.sizes);
-        dv[1] = pointer_device(c.soff);
-        dv[2] = pointer_device(c.doff);
+    if (gpu_available() && d.nstripes) {
+        dv[0] = pointer_device(d.sizes);
+        for (int i = 0; i < d.na; ++i) dv[1 + i] = pointer_device(d.off[i]);
     }
-    if (dv[0] != dv[1] || dv[0] != dv[2])
-        return set_status(FEC_EINVAL, "%s: sizes, src_offsets and dst_offsets are of mixed memory kinds: all three "
-                                      "in host memory, or all three in device memory on the blocks' device", c.fn);
+    if (dv[0] != dv[1] || (d.na == 2 && dv[0] != dv[2])) return set_status(FEC_EINVAL, d.mixed_kinds, d.fn);
     *ddev = dv[0];
     return FEC_OK;
 }
 
-int check_ragged_fit(const RaggedCall& c, unsigned k, unsigned r, int ddev) {
+int check_ragged_fit(const RaggedArgs& d, int ddev) {
     if (ddev < 0)
-        for (size_t s = 0; s < c.nstripes; ++s) {
-            const char* side = "";
-            if (c.sizes[s] && !ragged_stripe_fits(c, k, r, c.sizes, c.soff, c.doff, s, &side)) {
-                const bool in = side[0] == 's';
-                return set_status(FEC_EINVAL, "%s: stripe %zu does not fit %s: offset %llu, %u rows %llu apart, size "
-                                              "%llu, %s_bytes %zu", c.fn, s, side, in ? c.soff[s] : c.doff[s],
-                                  in ? k : r, static_cast<unsigned long long>(in ? (c.sbs ? c.sbs : c.sizes[s])
-                                                                                 : (c.dbs ? c.dbs : c.sizes[s])),
-                                  c.sizes[s], side, in ? c.src_bytes : c.dst_bytes);
+        for (size_t s = 0; s < d.nstripes; ++s) {
+            int i = 0;
+            if (d.sizes[s] && !ragged_stripe_fits(d, s, &i)) {
+                const RaggedArena& a = d.a[i];
+                return set_status(FEC_EINVAL, "%s: stripe %zu does not fit %s: offset %llu, %zu rows %llu apart, size "
+                                              "%llu, %s %zu", d.fn, s, a.name, d.off[i][s], a.rows,
+                                  static_cast<unsigned long long>(a.bstride ? a.bstride : d.sizes[s]), d.sizes[s],
+                                  a.bytes_name, a.bytes);
             }
         }
     return FEC_OK;
 }
 
-int check_ragged(const RaggedCall& c, unsigned k, unsigned r, int* ddev) {
-    if (check_ragged_kinds(c, ddev)) return t_status;
-    return check_ragged_fit(c, k, r, *ddev);
+int check_ragged(const RaggedArgs& d, int* ddev) {
+    if (check_ragged_kinds(d, ddev)) return t_status;
+    return check_ragged_fit(d, *ddev);
+}
+
+// Descriptor arrays in device memory (ddev >= 0), and pattern ids there (idev
+// >= 0), brought to the host for the calls that cut runs: copies on `st` into
+// the thread's buffers and one synchronise; d then reads the copies.
+int fetch_desc(RaggedArgs& d, int ddev, int idev, hipStream_t st) {
+    thread_local std::vector<unsigned long long> hd;
+    thread_local std::vector<unsigned> hids;
+    const size_t ns = d.nstripes;
+    hipError_t e;
+    if (ddev >= 0) {
+        hd.resize((1 + d.na) * ns);
+        const unsigned long long* from[3] = {d.sizes, d.off[0], d.off[1]};
+        for (int i = 0; i < 1 + d.na; ++i)
+            if ((e = hipMemcpyAsync(&hd[i * ns], from[i], ns * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                    st)) != hipSuccess)
+                return hip_fail(e, "hipMemcpyAsync D2H (descriptor arrays)");
+        d.sizes = hd.data();
+        for (int i = 0; i < d.na; ++i) d.off[i] = d.sizes + (1 + i) * ns;
+    }
+    if (d.ids && idev >= 0) {
+        hids.resize(ns);
+        if ((e = hipMemcpyAsync(hids.data(), d.ids, ns * sizeof(unsigned), hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
+        d.ids = hids.data();
+    }
+    if ((ddev >= 0 || (d.ids && idev >= 0)) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return FEC_OK;
+}
+
+// Maximal runs [s0, s1) of consecutive stripes that are live(s), have one size,
+// are same(s0, s) and whose offsets each advance by a constant: each one
+// uniform batched call.  run(s0, s1, step) with the offset steps (0 for a run
+// of one); a stripe that is not live is passed over.
+template <class Live, class Same, class Run>
+int for_each_ragged_run(const RaggedArgs& d, Live live, Same same, Run run) {
+    const size_t ns = d.nstripes;
+    for (size_t s0 = 0; s0 < ns;) {
+        if (!live(s0)) {
+            ++s0;
+            continue;
+        }
+        size_t s1 = s0 + 1, step[2] = {0, 0};
+        // stripe s follows s - 1 at a rising offset in every arena, and belongs to the run of s0
+        const auto joins = [&](size_t s) {
+            for (int i = 0; i < d.na; ++i)
+                if (d.off[i][s] <= d.off[i][s - 1]) return false;
+            return d.sizes[s] == d.sizes[s0] && same(s0, s) && live(s);
+        };
+        const auto in_step = [&](size_t s) {
+            for (int i = 0; i < d.na; ++i)
+                if (d.off[i][s] - d.off[i][s - 1] != step[i]) return false;
+            return true;
+        };
+        if (s1 < ns && joins(s1)) {
+            for (int i = 0; i < d.na; ++i) step[i] = d.off[i][s1] - d.off[i][s0];
+            ++s1;
+            while (s1 < ns && joins(s1) && in_step(s1)) ++s1;
+        }
+        if (run(s0, s1, step)) return t_status;
+        s0 = s1;
+    }
+    return FEC_OK;
 }
 
 int run_ragged(const RaggedCall& c, const fec_t* code, const uint8_t* coef, unsigned r, int ddev) {
@@ -1511,42 +1594,18 @@ int run_ragged(const RaggedCall& c, const fec_t* code, const uint8_t* coef, unsi
     } else {
         // wider codes: runs of consecutive stripes of one size whose two offsets
         // each advance by a constant, each run one shared-matrix batched launch
-        const unsigned long long *sizes = c.sizes, *soff = c.soff, *doff = c.doff;
-        thread_local std::vector<unsigned long long> hd;
-        if (ddev >= 0) {
-            hd.resize(3 * ns);
-            const unsigned long long* from[3] = {c.sizes, c.soff, c.doff};
-            for (int i = 0; i < 3; ++i)
-                if ((e = hipMemcpyAsync(&hd[i * ns], from[i], ns * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                        st)) != hipSuccess)
-                    return hip_fail(e, "hipMemcpyAsync D2H (descriptor arrays)");
-            if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-            sizes = hd.data();
-            soff = sizes + ns;
-            doff = soff + ns;
-        }
-        const auto live = [&](size_t s) { return sizes[s] && ragged_stripe_fits(c, k, r, sizes, soff, doff, s); };
+        RaggedArgs d = ragged_args(c, k, r);
+        if (fetch_desc(d, ddev, -1, st)) return t_status;
         const unsigned jf = (c.flags & FEC_FLAG_LIBRARY_STREAM) | FEC_FLAG_ASYNC;
-        for (size_t s0 = 0; s0 < ns;) {
-            if (!live(s0)) {  // empty, or (device-side arrays) it does not fit: neither read nor written
-                ++s0;
-                continue;
-            }
-            const size_t sz = sizes[s0];
-            size_t s1 = s0 + 1, dsrc = 0, ddst = 0;
-            if (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s0] && doff[s1] > doff[s0] && live(s1)) {
-                dsrc = soff[s1] - soff[s0];
-                ddst = doff[s1] - doff[s0];
-                ++s1;
-                while (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s1 - 1] && soff[s1] - soff[s1 - 1] == dsrc &&
-                       doff[s1] > doff[s1 - 1] && doff[s1] - doff[s1 - 1] == ddst && live(s1))
-                    ++s1;
-            }
-            if (run_batch(code, coef, r, c.src + soff[s0], c.sbs ? c.sbs : sz, dsrc, c.dst + doff[s0],
-                          c.dbs ? c.dbs : sz, ddst, sz, s1 - s0, c.stream, jf))
-                return t_status;
-            s0 = s1;
-        }
+        // not live: empty, or (device-side arrays) it does not fit: neither read nor written
+        if (for_each_ragged_run(
+                d, [&](size_t s) { return d.sizes[s] && ragged_stripe_fits(d, s); }, [](size_t, size_t) { return true; },
+                [&](size_t s0, size_t s1, const size_t* step) {
+                    const size_t sz = d.sizes[s0];
+                    return run_batch(code, coef, r, c.src + d.off[0][s0], c.sbs ? c.sbs : sz, step[0],
+                                     c.dst + d.off[1][s0], c.dbs ? c.dbs : sz, step[1], sz, s1 - s0, c.stream, jf);
+                }))
+            return t_status;
     }
     if (!(c.flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "hipStreamSynchronize");
@@ -1582,7 +1641,7 @@ FEC_API int fec_encode_batch_ragged(const fec_t* code, const gf* src, size_t src
     return guarded([&] {
         const unsigned r = static_cast<unsigned>(num_block_nums);
         int ddev = -1;
-        if (check_ragged(c, code->k, r, &ddev)) return t_status;
+        if (check_ragged(ragged_args(c, code->k, r), &ddev)) return t_status;
         if (!gpu_available()) return no_gpu();
         return run_ragged(c, code, encode_rows(code, block_nums, num_block_nums), r, ddev);
     });
@@ -1607,7 +1666,7 @@ FEC_API int fec_decode_batch_ragged(const fec_t* code, const gf* src, size_t src
         }
         if (nstripes == 0) return set_status(FEC_OK);
         int ddev = -1;
-        if (check_ragged(c, code->k, r, &ddev)) return t_status;
+        if (check_ragged(ragged_args(c, code->k, r), &ddev)) return t_status;
         if (r == 0) return set_status(FEC_OK);  // no primary is missing: nothing to recover
         if (!gpu_available()) return no_gpu();
         return run_ragged(c, code, rows.data(), r, ddev);
@@ -2428,9 +2487,15 @@ struct ScrubCall {
     const char* arena() const { return heal ? "blocks" : "src"; }
 };
 
-bool scrub_stripe_fits(const ScrubCall& c, const unsigned long long* sizes, const unsigned long long* soff, size_t s) {
-    const uint64_t sz = sizes[s];
-    return ragged_fits(soff[s], c.sbs ? c.sbs : sz, static_cast<uint32_t>(c.nb), sz, c.src_bytes);
+RaggedArgs ragged_args(const ScrubCall& c) {
+    return RaggedArgs{c.fn,
+                      c.heal ? "%s: sizes and offsets are of mixed memory kinds: both in host memory, or both in device "
+                               "memory on the blocks' device"
+                             : "%s: sizes and src_offsets are of mixed memory kinds: both in host memory, or both in "
+                               "device memory on the blocks' device",
+                      1, {{c.arena(), c.heal ? "offsets" : "src_offsets", c.heal ? "bytes" : "src_bytes",
+                                 c.src_bytes, c.sbs, c.nb}, {}},
+                      c.nstripes, c.sizes, {c.soff, nullptr}};
 }
 
 // Every check of a ragged scrub call that needs no GPU, in the header's order.
@@ -2442,7 +2507,7 @@ int check_ragged_scrub(const fec_t* code, const ScrubCall& c, int* ddev) {
         const char* name;
     } args[] = {{c.src, c.arena()},
                 {c.sizes, "sizes"},
-                {c.soff, c.heal ? "offsets" : "src_offsets"},
+                {c.soff, ragged_args(c).a[0].off_name},
                 {c.nums, "block_nums"},
                 {c.out, c.locate ? "culprit" : "mismatch"}};
     for (const auto& a : args)
@@ -2451,27 +2516,7 @@ int check_ragged_scrub(const fec_t* code, const ScrubCall& c, int* ddev) {
         const std::string msg = t_msg;  // fec_verify_batch's checks, named as this call's
         return set_status(t_status, "%s: %s", c.fn, msg.c_str());
     }
-    if (uint64_t(c.nstripes) >= (1ull << 32))
-        return set_status(FEC_EINVAL, "%s: %zu stripes: a call takes fewer than 2^32", c.fn, c.nstripes);
-    int dv[2] = {-1, -1};
-    if (gpu_available() && c.nstripes) {
-        dv[0] = pointer_device(c.sizes);
-        dv[1] = pointer_device(c.soff);
-    }
-    if (dv[0] != dv[1])
-        return set_status(FEC_EINVAL, c.heal ? "%s: sizes and offsets are of mixed memory kinds: both in host memory, "
-                                               "or both in device memory on the blocks' device"
-                                             : "%s: sizes and src_offsets are of mixed memory kinds: both in host "
-                                               "memory, or both in device memory on the blocks' device", c.fn);
-    *ddev = dv[0];
-    if (*ddev < 0)
-        for (size_t s = 0; s < c.nstripes; ++s)
-            if (c.sizes[s] && !scrub_stripe_fits(c, c.sizes, c.soff, s))
-                return set_status(FEC_EINVAL, "%s: stripe %zu does not fit %s: offset %llu, %zu rows %llu apart, "
-                                              "size %llu, %s %zu", c.fn, s, c.arena(), c.soff[s], c.nb,
-                                  static_cast<unsigned long long>(c.sbs ? c.sbs : c.sizes[s]), c.sizes[s],
-                                  c.heal ? "bytes" : "src_bytes", c.src_bytes);
-    return FEC_OK;
+    return check_ragged(ragged_args(c), ddev);
 }
 
 // k <= 4 (a location: c <= 8): matverify_ragged / matlocate_ragged.  The
@@ -2583,20 +2628,10 @@ int run_ragged_scrub_runs(const fec_t* code, const ScrubCall& c, int ddev, int r
     const size_t ns = c.nstripes, W = c.locate ? 1 : cw;
     hipStream_t st = mem.st;
     hipError_t e;
-    const unsigned long long *sizes = c.sizes, *soff = c.soff;
-    thread_local std::vector<unsigned long long> hd;
-    if (ddev >= 0) {
-        hd.resize(2 * ns);
-        const unsigned long long* from[2] = {c.sizes, c.soff};
-        for (int i = 0; i < 2; ++i)
-            if ((e = hipMemcpyAsync(&hd[i * ns], from[i], ns * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                    st)) != hipSuccess)
-                return hip_fail(e, "hipMemcpyAsync D2H (descriptor arrays)");
-        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-        sizes = hd.data();
-        soff = sizes + ns;
-    }
-    const auto live = [&](size_t s) { return sizes[s] && scrub_stripe_fits(c, sizes, soff, s); };
+    RaggedArgs d = ragged_args(c);
+    if (fetch_desc(d, ddev, -1, st)) return t_status;
+    // not live: empty, or (device-side arrays) it does not fit: not read
+    const auto live = [&](size_t s) { return d.sizes[s] && ragged_stripe_fits(d, s); };
     // every word cleared (a location: CLEAN), then the marks of what will not be read
     const size_t out_bytes = ns * W * sizeof(uint32_t);
     const int fill = c.locate ? 0xFF : 0;
@@ -2613,7 +2648,7 @@ int run_ragged_scrub_runs(const fec_t* code, const ScrubCall& c, int ddev, int r
     } else {
         std::memset(c.out, fill, out_bytes);
         for (size_t s = 0; s < ns; ++s) {
-            if (!sizes[s] || live(s)) continue;
+            if (!d.sizes[s] || live(s)) continue;
             if (c.locate)
                 c.out[s] = FEC_LOCATE_UNFIT;
             else
@@ -2622,27 +2657,16 @@ int run_ragged_scrub_runs(const fec_t* code, const ScrubCall& c, int ddev, int r
         }
     }
     const unsigned jf = (c.flags & FEC_FLAG_LIBRARY_STREAM) | FEC_FLAG_ASYNC;
-    for (size_t s0 = 0; s0 < ns;) {
-        if (!live(s0)) {  // empty, or (device-side arrays) it does not fit: not read
-            ++s0;
-            continue;
-        }
-        const size_t sz = sizes[s0];
-        size_t s1 = s0 + 1, dsrc = 0;
-        if (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s0] && live(s1)) {
-            dsrc = soff[s1] - soff[s0];
-            ++s1;
-            while (s1 < ns && sizes[s1] == sz && soff[s1] > soff[s1 - 1] && soff[s1] - soff[s1 - 1] == dsrc && live(s1))
-                ++s1;
-        }
-        const size_t bs = c.sbs ? c.sbs : sz;
-        if (c.locate ? run_locate(code, c.src + soff[s0], bs, dsrc, c.nums, c.nb, sz, s1 - s0, c.out + s0, c.stream, jf,
-                                  c.fn, c.heal)
-                     : run_verify(code, c.src + soff[s0], bs, dsrc, c.nums, c.nb, sz, s1 - s0, c.out + s0 * cw,
-                                  c.stream, jf))
-            return t_status;
-        s0 = s1;
-    }
+    if (for_each_ragged_run(
+            d, live, [](size_t, size_t) { return true; }, [&](size_t s0, size_t s1, const size_t* step) {
+                const size_t sz = d.sizes[s0], bs = c.sbs ? c.sbs : sz;
+                const gf* const src = c.src + d.off[0][s0];
+                return c.locate ? run_locate(code, src, bs, step[0], c.nums, c.nb, sz, s1 - s0, c.out + s0, c.stream,
+                                             jf, c.fn, c.heal)
+                                : run_verify(code, src, bs, step[0], c.nums, c.nb, sz, s1 - s0, c.out + s0 * cw,
+                                             c.stream, jf);
+            }))
+        return t_status;
     if (!(c.flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "hipStreamSynchronize");
     return set_status(FEC_OK);
@@ -3028,68 +3052,31 @@ int run_repair_ragged(const RaggedCall& c, const fec_t* code, const unsigned* pr
         // wider codes: runs of consecutive stripes of one size and one pattern id whose two
         // offsets each advance by a constant, each run one shared-matrix application of that
         // pattern's live rows.  Device-side arrays come to the host first (a stream sync).
-        const unsigned long long *sizes = c.sizes, *soff = c.soff, *doff = c.doff;
-        const unsigned* ids = pattern_of;
-        thread_local std::vector<unsigned long long> hd;
-        thread_local std::vector<unsigned> hids;
-        bool synced = true;
-        if (ddev >= 0) {
-            hd.resize(3 * ns);
-            const unsigned long long* from[3] = {c.sizes, c.soff, c.doff};
-            for (int i = 0; i < 3; ++i)
-                if ((e = hipMemcpyAsync(&hd[i * ns], from[i], ns * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                        st)) != hipSuccess)
-                    return hip_fail(e, "hipMemcpyAsync D2H (descriptor arrays)");
-            sizes = hd.data();
-            soff = sizes + ns;
-            doff = soff + ns;
-            synced = false;
-        }
-        if (pattern_of && idev >= 0) {
-            hids.resize(ns);
-            if ((e = hipMemcpyAsync(hids.data(), pattern_of, ns * sizeof(unsigned), hipMemcpyDeviceToHost, st)) !=
-                hipSuccess)
-                return hip_fail(e, "hipMemcpyAsync D2H (pattern_of)");
-            ids = hids.data();
-            synced = false;
-        }
-        if (!synced && (e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-        const auto id_of = [&](size_t s) { return ids ? ids[s] : 0u; };
-        const auto live = [&](size_t s) {
-            return sizes[s] && id_of(s) < npatterns && ragged_stripe_fits(c, k, r, sizes, soff, doff, s);
-        };
+        RaggedArgs d = ragged_args(c, k, r);
+        d.ids = pattern_of;
+        if (fetch_desc(d, ddev, idev, st)) return t_status;
+        const auto id_of = [&](size_t s) { return d.ids ? d.ids[s] : 0u; };
         typedef std::pair<std::vector<uint8_t>, uint32_t> RowsAndMask;
         std::unordered_map<unsigned, RowsAndMask> cache;
-        for (size_t s0 = 0; s0 < ns;) {
-            if (!live(s0)) {  // empty, or (device-side arrays) unfit or a bad id: neither read nor written
-                ++s0;
-                continue;
-            }
-            const size_t sz = sizes[s0];
-            const unsigned id = id_of(s0);
-            const auto same = [&](size_t s) { return sizes[s] == sz && id_of(s) == id && live(s); };
-            size_t s1 = s0 + 1, dsrc = 0, ddst = 0;
-            if (s1 < ns && soff[s1] > soff[s0] && doff[s1] > doff[s0] && same(s1)) {
-                dsrc = soff[s1] - soff[s0];
-                ddst = doff[s1] - doff[s0];
-                ++s1;
-                while (s1 < ns && soff[s1] > soff[s1 - 1] && soff[s1] - soff[s1 - 1] == dsrc &&
-                       doff[s1] > doff[s1 - 1] && doff[s1] - doff[s1 - 1] == ddst && same(s1))
-                    ++s1;
-            }
-            const auto ins = cache.try_emplace(id);
-            RowsAndMask& pr = ins.first->second;
-            if (ins.second) {
-                pr.first.resize(nt * k);
-                if (repair_rows(code, present + size_t(id) * k, targets + size_t(id) * nt, nt, pr.first.data(),
-                                &pr.second))
-                    return t_status;
-            }
-            if (repair_shared(pr.first.data(), pr.second, k, nt, zsrc + soff[s0], c.sbs ? c.sbs : sz, dsrc,
-                              zdst + doff[s0], c.dbs ? c.dbs : sz, ddst, sz, s1 - s0, st))
-                return t_status;
-            s0 = s1;
-        }
+        // not live: empty, or (device-side arrays) unfit or a bad id: neither read nor written
+        if (for_each_ragged_run(
+                d, [&](size_t s) { return d.sizes[s] && id_of(s) < npatterns && ragged_stripe_fits(d, s); },
+                [&](size_t s0, size_t s) { return id_of(s) == id_of(s0); },
+                [&](size_t s0, size_t s1, const size_t* step) {
+                    const size_t sz = d.sizes[s0];
+                    const unsigned id = id_of(s0);
+                    const auto ins = cache.try_emplace(id);
+                    RowsAndMask& pr = ins.first->second;
+                    if (ins.second) {
+                        pr.first.resize(nt * k);
+                        if (repair_rows(code, present + size_t(id) * k, targets + size_t(id) * nt, nt, pr.first.data(),
+                                        &pr.second))
+                            return t_status;
+                    }
+                    return repair_shared(pr.first.data(), pr.second, k, nt, zsrc + d.off[0][s0], c.sbs ? c.sbs : sz,
+                                         step[0], zdst + d.off[1][s0], c.dbs ? c.dbs : sz, step[1], sz, s1 - s0, st);
+                }))
+            return t_status;
     }
     if (!(c.flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
         return hip_fail(e, "hipStreamSynchronize");
@@ -3136,14 +3123,15 @@ FEC_API int fec_repair_batch_ragged(const fec_t* code, const gf* src, size_t src
     if (nstripes == 0) return set_status(FEC_OK);
     return guarded([&] {
         int ddev = -1;
-        if (check_ragged_kinds(c, &ddev)) return t_status;
+        const RaggedArgs d = ragged_args(c, code->k, static_cast<unsigned>(ntargets));
+        if (check_ragged_kinds(d, &ddev)) return t_status;
         const int idev = gpu_available() && pattern_of ? pointer_device(pattern_of) : -1;
         if (pattern_of && idev < 0)
             for (size_t s = 0; s < nstripes; ++s)
                 if (pattern_of[s] >= npatterns)
                     return set_status(FEC_EINVAL, "%s: stripe %zu: pattern id %u out of range (npatterns = %zu)",
                                       c.fn, s, pattern_of[s], npatterns);
-        if (check_ragged_fit(c, code->k, static_cast<unsigned>(ntargets), ddev)) return t_status;
+        if (check_ragged_fit(d, ddev)) return t_status;
         if (!gpu_available()) return no_gpu();
         return run_repair_ragged(c, code, present, targets, ntargets, npatterns, pattern_of, idev, ddev);
     });

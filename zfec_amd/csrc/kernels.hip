@@ -22,10 +22,12 @@
 //   matapply_rows<K, R> the same arithmetic, one wave per stripe of short blocks.
 //   matapply_mixed<K>   the same arithmetic, K outputs, each stripe's tables picked
 //                       by its pattern id from a device-side table (scalar loads).
-//   matapply_ragged<K, R> the same arithmetic, every stripe its own size: a wave walks
-//                       a short range of 1 KiB units, finds its stripe by a search
-//                       over their prefix sum (ragged_scan writes it for device-side
-//                       sizes) and reads sizes and offsets by scalar loads
+//   ragged_walk         not a kernel: the walk of the five ragged families below,
+//                       every stripe its own size.  A wave walks a short range of
+//                       1 KiB units, finds its stripe by a search over their prefix
+//                       sum (ragged_scan writes it for device-side sizes) and reads
+//                       each stripe's descriptor by scalar loads.
+//   matapply_ragged<K, R> matapply_reg's arithmetic per unit of the walk
 //                       (fec_encode_batch_ragged / fec_decode_batch_ragged).
 //   matverify_reg<K, R> the same arithmetic, nothing stored: the R rows are compared
 //                       with the stored check blocks and only mismatch bits are
@@ -37,7 +39,7 @@
 //                       same past k = 4 or 8 checks, locate_finish turns each
 //                       stripe's bits into its verdict.
 //   matverify_ragged<K, R>, matlocate_ragged<K, R>
-//                       those two units inside matapply_ragged's walk: the bits of
+//                       those two units inside ragged_walk: the bits of
 //                       a stripe are gathered per wave and OR-ed out once, and
 //                       ragged_unfit marks the stripes a device-side descriptor
 //                       put outside the arena (fec_verify_batch_ragged /
@@ -50,11 +52,10 @@
 //                       row stored only where its pattern's live-row mask says
 //                       so (fec_repair_batch).
 //   matrepair_ragged<K, R>, matcorrect_ragged<K>
-//                       matapply_ragged's walk around matrepair_mixed's per-stripe
-//                       record (a size AND a pattern per stripe) and around
-//                       matcorrect_reg's unit, the stripe's verdict read with its
-//                       descriptor (fec_repair_batch_ragged /
-//                       fec_correct_batch_ragged).
+//                       ragged_walk around matrepair_mixed's per-stripe record (a
+//                       size AND a pattern per stripe) and around matcorrect_reg's
+//                       unit, the stripe's verdict read with its descriptor
+//                       (fec_repair_batch_ragged / fec_correct_batch_ragged).
 //   matapply_lds        any k <= 32, r <= 48 (longer codes are split by the
 //                       caller): each workgroup expands its coefficients into
 //                       LDS tables from a compile-time bank of all 256 values;
@@ -855,24 +856,9 @@ __global__ __launch_bounds__(kBlock) void matapply_mixed(const MixedJob<K> job) 
 // matapply_ragged<K, R>: a batch whose stripes each have their own size
 // (fec_encode_batch_ragged / fec_decode_batch_ragged), k <= 4, up to 8 rows
 // per launch, one matrix for all stripes (its tables in the argument block, as
-// RegJob).  A unit is one wave step of one stripe -- 64 lanes x 16 bytes of
-// every block -- so stripe s has ceil(sizes[s] / 1024) units and ustart is
-// their exclusive prefix sum, ustart[nstripes] the total T.
-//
-// The launch has G waves; wave g owns the contiguous units [g*q + min(g, e),
-// ...) with q = T / G, e = T % G (the shard_range rule).  It finds its first
-// stripe by one binary search over ustart (the last s with ustart[s] <= first,
-// which skips zero-size stripes) and walks forward: per stripe it reads the
-// size and the two offsets once, tests that the stripe fits both arenas
-// (ragged_fits; a stripe that does not is neither read nor written), and makes
-// the stripe's wave steps, unit w covering chunks w*64 + lane with
-// chunk_span's overlapped last chunk.  The next stripe's descriptor is
-// requested before the current stripe's units are computed.  Everything about
-// a stripe is the same in every lane: it is formed through readfirstlane and
-// read through constant-address-space pointers (scalar loads), as in
-// matapply_mixed.  ustart, sizes and offsets are written before the launch (a
-// copy, ragged_scan or the caller's earlier work in the stream), never by this
-// kernel.  All byte addresses are 64-bit.
+// RegJob), inside ragged_walk (below).  Per stripe the body tests that it fits
+// both arenas (ragged_fits; a stripe that does not is neither read nor
+// written) and makes the stripe's wave steps: K rows loaded, R rows stored.
 // ---------------------------------------------------------------------------
 template <int K, int R>
 struct alignas(16) RaggedJob {
@@ -899,15 +885,96 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
     return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
-struct RaggedStripe {
-    uint64_t u0, u1;  // its units: [u0, u1)
-    uint64_t sz, ioff, ooff;
+// ---------------------------------------------------------------------------
+// ragged_walk: the walk every ragged kernel makes.  A unit is one wave step of
+// one stripe -- 64 lanes x 16 bytes of every block -- so stripe s has
+// ceil(sizes[s] / 1024) units and ustart is their exclusive prefix sum,
+// ustart[ns] the total T.
+//
+// The launch has G waves; wave g owns the contiguous units [g*q + min(g, e),
+// ...) with q = T / G, e = T % G (the shard_range rule).  It finds its first
+// stripe by one binary search over ustart (the last s with ustart[s] <= first,
+// which skips zero-size stripes) and walks forward, calling
+// body(stripe, s, u, stop) once per stripe with the wave's units [u, stop) of
+// it (none, u == stop, where the range ends on the stripe's first unit).  The
+// next stripe's descriptor is requested before the body runs.  Everything
+// about a stripe is the same in every lane: it is formed through readfirstlane
+// and read through constant-address-space pointers (scalar loads), as in
+// matapply_mixed.  The descriptor arrays are written before the launch (a
+// copy, ragged_scan or the caller's earlier work in the stream), never by the
+// kernel that walks them.  All byte addresses are 64-bit.
+//
+// RaggedDesc names the arrays: ustart, sizes, NOFF offset arrays and, with
+// WORD, one 32-bit word per stripe (a pattern id, a verdict); RaggedStripe is
+// one stripe's entry of each.
+// ---------------------------------------------------------------------------
+template <int NOFF, bool WORD>
+struct RaggedDesc {
+    uint32_t ns;
+    const uint64_t* ustart;  // ns + 1
+    const uint64_t* sizes;
+    const uint64_t* off[NOFF];
+    const uint32_t* word;
 };
 
-template <class J>
-__device__ __forceinline__ RaggedStripe ragged_stripe(const J& job, uint32_t s) {
-    const CU64 us = (CU64)job.ustart;
-    return RaggedStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.in_off)[s], ((CU64)job.out_off)[s]};
+template <int NOFF, bool WORD>
+struct RaggedStripe {
+    uint64_t u0, u1;  // its units: [u0, u1)
+    uint64_t sz, off[NOFF];
+    uint32_t word;
+};
+
+template <int NOFF, bool WORD>
+__device__ __forceinline__ RaggedStripe<NOFF, WORD> ragged_stripe(const RaggedDesc<NOFF, WORD>& d, uint32_t s) {
+    const CU64 us = (CU64)d.ustart;
+    RaggedStripe<NOFF, WORD> t;
+    t.u0 = us[s];
+    t.u1 = us[s + 1];
+    t.sz = ((CU64)d.sizes)[s];
+#pragma unroll
+    for (int i = 0; i < NOFF; ++i) t.off[i] = ((CU64)d.off[i])[s];
+    t.word = 0;
+    if constexpr (WORD) t.word = ((CU32)d.word)[s];
+    return t;
+}
+
+template <int NOFF, bool WORD, class Body>
+__device__ __forceinline__ void ragged_walk(const RaggedDesc<NOFF, WORD>& d, Body&& body) {
+    using Stripe = RaggedStripe<NOFF, WORD>;
+    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t G = gridDim.x * (kBlock / 64);
+    const CU64 us = (CU64)d.ustart;
+    const uint32_t ns = d.ns;
+    const uint64_t total = us[ns];
+    // (a launch with a wave per unit or more needs no division)
+    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
+    uint64_t u = uniform64(g * q + (g < e ? g : e));
+    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
+    if (u >= end) return;
+    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (us[mid] <= u)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
+    Stripe cur = ragged_stripe(d, s);
+    for (;;) {
+        Stripe nxt = cur;
+        if (s + 1 < ns) nxt = ragged_stripe(d, s + 1);
+        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+        body(cur, s, u, stop);
+        u = stop;
+        if (u >= end || s + 1 >= ns) break;
+        ++s;
+        cur = nxt;
+        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
+            ++s;
+            cur = ragged_stripe(d, s);
+        }
+    }
 }
 
 // chunk_span<kChunk, true> with a 64-bit chunk number (a stripe is not bounded
@@ -917,6 +984,36 @@ __device__ __forceinline__ Span ragged_span(uint64_t c, uint64_t sz, uint64_t nf
     if (c < nfull) return Span{off, true, kChunk};
     if (sz >= kChunk) return Span{sz - kChunk, true, kChunk};
     return Span{off, false, static_cast<uint32_t>(sz - off)};
+}
+
+// This lane's chunk of unit w of a stripe of sz bytes: chunk w*64 + lane with
+// ragged_span's overlapped last chunk; *live: the stripe has that chunk.
+__device__ __forceinline__ Span ragged_unit(uint64_t w, uint32_t lane, uint64_t sz, bool* live) {
+    const uint64_t c = w * 64u + lane;
+    *live = c < (sz + kChunk - 1) / kChunk;
+    return ragged_span(c, sz, sz / kChunk);
+}
+
+// The lane's address of the next row.  The empty asm keeps it a per-lane
+// 64-bit add: left to itself the compiler may form multiples j * B as
+// wave-uniform values that live across the unit loop, in SGPRs the walk does
+// not have (matlocate_ragged<4,8> spilled two without it).
+__device__ __forceinline__ const uint8_t* next_row(const uint8_t* row, uint64_t B) {
+    row += B;
+    asm volatile("" : "+v"(row));
+    return row;
+}
+
+// The selectors of the four dwords of each of K inputs.
+template <int K>
+__device__ __forceinline__ void ragged_sel(Sel (&sel)[4][K], const u32x4 (&x)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        sel[0][j] = selectors(x[j].x);
+        sel[1][j] = selectors(x[j].y);
+        sel[2][j] = selectors(x[j].z);
+        sel[3][j] = selectors(x[j].w);
+    }
 }
 
 template <int K, int R>
@@ -937,41 +1034,19 @@ __global__ __launch_bounds__(kBlock) void matapply_ragged(const RaggedJob<K, R> 
             }
     }
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t G = gridDim.x * (kBlock / 64);
-    const CU64 us = (CU64)job.ustart;
-    const uint32_t ns = job.nstripes;
-    const uint64_t total = us[ns];
-    // (a launch with a wave per unit or more needs no division)
-    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
-    uint64_t u = uniform64(g * q + (g < e ? g : e));
-    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
-    if (u >= end) return;
-    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (us[mid] <= u)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
-    RaggedStripe cur = ragged_stripe(job, s);
-    for (;;) {
-        RaggedStripe nxt = cur;
-        if (s + 1 < ns) nxt = ragged_stripe(job, s + 1);
-        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+    const RaggedDesc<2, false> desc{job.nstripes, job.ustart, job.sizes, {job.in_off, job.out_off}, nullptr};
+    ragged_walk(desc, [&](const RaggedStripe<2, false>& cur, uint32_t, uint64_t u, uint64_t stop) {
         const uint64_t sz = cur.sz;
         const uint64_t ib = job.in_bstride ? job.in_bstride : sz, ob = job.out_bstride ? job.out_bstride : sz;
-        if (u < stop && ragged_fits(cur.ioff, ib, K, sz, job.in_bytes) &&
-            ragged_fits(cur.ooff, ob, job.rows_all, sz, job.out_bytes)) {
-            const uint8_t* const in0 = job.in + cur.ioff;
-            uint8_t* const out0 = job.out + cur.ooff + job.row0 * ob;
-            const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
+        if (u < stop && ragged_fits(cur.off[0], ib, K, sz, job.in_bytes) &&
+            ragged_fits(cur.off[1], ob, job.rows_all, sz, job.out_bytes)) {
+            // the arenas' bases are read from the argument segment per stripe: held across the
+            // walk in four SGPRs they spill inside the shared walk (<2,1>: 8 where its own had 6)
+            const uint8_t* const in0 = kernarg_job<J>()->in + cur.off[0];
+            uint8_t* const out0 = kernarg_job<J>()->out + cur.off[1] + job.row0 * ob;
             for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
-                const uint64_t c = w * 64u + lane;
-                const bool live = c < cps;
-                const Span sp = ragged_span(c, sz, nfull);
+                bool live;
+                const Span sp = ragged_unit(w, lane, sz, &live);
                 u32x4 x[K];
 #pragma unroll
                 for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
@@ -985,13 +1060,7 @@ __global__ __launch_bounds__(kBlock) void matapply_ragged(const RaggedJob<K, R> 
                     }
                 }
                 Sel sel[4][K];
-#pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    sel[0][j] = selectors(x[j].x);
-                    sel[1][j] = selectors(x[j].y);
-                    sel[2][j] = selectors(x[j].z);
-                    sel[3][j] = selectors(x[j].w);
-                }
+                ragged_sel<K>(sel, x);
                 // the row address advances per lane: R wave-uniform row bases would
                 // live across the unit loop in SGPRs the walk has no room for
                 uint8_t* orow = out0 + sp.off;
@@ -1021,15 +1090,7 @@ __global__ __launch_bounds__(kBlock) void matapply_ragged(const RaggedJob<K, R> 
                 }
             }
         }
-        u = stop;
-        if (u >= end || s + 1 >= ns) break;
-        ++s;
-        cur = nxt;
-        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
-            ++s;
-            cur = ragged_stripe(job, s);
-        }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1717,14 +1778,10 @@ __global__ __launch_bounds__(kBlock) void locate_finish(const FinishJob job) {
 // matverify_ragged<K, R> / matlocate_ragged<K, R>: the scrub of a batch whose
 // stripes each have their own size (fec_verify_batch_ragged /
 // fec_locate_batch_ragged), k <= 4 and up to 8 checks per launch.  One body,
-// LOC choosing the family: the walk of matapply_ragged (1 KiB units, the
-// shard_range split of T over the launched waves, one binary search over
-// ustart, the stripe's size and offset by scalar loads with the next stripe's
-// requested early, the fit test, 64-bit addresses, ragged_span's overlapped
-// last chunk, the tail zero-filled on both sides) around the unit of
-// matverify_reg / matlocate_reg (the syndromes in registers; with LOC the k
-// hypotheses against the Q tables, read through the kernel-argument pointer
-// under the wave-uniform mask != 0 branch only).
+// LOC choosing the family: ragged_walk around the unit of matverify_reg /
+// matlocate_reg (the syndromes in registers, the tail zero-filled on both
+// sides; with LOC the k hypotheses against the Q tables, read through the
+// kernel-argument pointer under the wave-uniform mask != 0 branch only).
 //
 // There is ONE base pointer: slot j of a stripe is base + off + j * B, so the
 // first check slot of a launch (K + bit0) is a number, not a pointer array.
@@ -1758,27 +1815,6 @@ struct alignas(16) RaggedScrubJob {
     uint32_t qtab[LOC ? K * (R - 1) * 5 : 1];      // Q[r][j], r = 1..R-1, at ((r-1)*K + j)*5
 };
 
-struct ScrubStripe {
-    uint64_t u0, u1;  // its units: [u0, u1)
-    uint64_t sz, off;
-};
-
-template <class J>
-__device__ __forceinline__ ScrubStripe scrub_stripe(const J& job, uint32_t s) {
-    const CU64 us = (CU64)job.ustart;
-    return ScrubStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.off)[s]};
-}
-
-// The lane's address of the next slot.  The empty asm keeps it a per-lane
-// 64-bit add: left to itself the compiler may form multiples j * B as
-// wave-uniform values that live across the unit loop, in SGPRs the walk does
-// not have (matlocate_ragged<4,8> spilled two without it).
-__device__ __forceinline__ const uint8_t* next_row(const uint8_t* row, uint64_t B) {
-    row += B;
-    asm volatile("" : "+v"(row));
-    return row;
-}
-
 template <int K, int R, bool LOC>
 __device__ __forceinline__ void scrub_ragged_body(const RaggedScrubJob<K, R, LOC>& job) {
     using J = RaggedScrubJob<K, R, LOC>;
@@ -1797,41 +1833,18 @@ __device__ __forceinline__ void scrub_ragged_body(const RaggedScrubJob<K, R, LOC
             }
     }
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t G = gridDim.x * (kBlock / 64);
-    const CU64 us = (CU64)job.ustart;
-    const uint32_t ns = job.nstripes;
-    const uint64_t total = us[ns];
-    // (a launch with a wave per unit or more needs no division)
-    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
-    uint64_t u = uniform64(g * q + (g < e ? g : e));
-    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
-    if (u >= end) return;
-    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (us[mid] <= u)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
-    ScrubStripe cur = scrub_stripe(job, s);
-    for (;;) {
-        ScrubStripe nxt = cur;
-        if (s + 1 < ns) nxt = scrub_stripe(job, s + 1);
-        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+    const RaggedDesc<1, false> desc{job.nstripes, job.ustart, job.sizes, {job.off}, nullptr};
+    ragged_walk(desc, [&](const RaggedStripe<1, false>& cur, uint32_t s, uint64_t u, uint64_t stop) {
         const uint64_t sz = cur.sz;
         const uint64_t B = job.bstride ? job.bstride : sz;
         uint32_t smask = 0, sexcl = 0;  // this wave's bits of stripe s
-        if (u < stop && ragged_fits(cur.off, B, job.slots, sz, job.bytes)) {
-            const uint8_t* const in0 = job.src + cur.off;
+        if (u < stop && ragged_fits(cur.off[0], B, job.slots, sz, job.bytes)) {
+            const uint8_t* const in0 = job.src + cur.off[0];
             const uint64_t coff = job.chk0 * B;
-            const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
             for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
-                const uint64_t c = w * 64u + lane;
-                const bool live = c < cps;
-                const Span sp = ragged_span(c, sz, nfull);
+                bool live;
+                const Span sp = ragged_unit(w, lane, sz, &live);
+                // the K basis rows, then the R stored check rows from slot chk0 on
                 u32x4 x[K], y[R];
 #pragma unroll
                 for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
@@ -1854,12 +1867,18 @@ __device__ __forceinline__ void scrub_ragged_body(const RaggedScrubJob<K, R, LOC
                     }
                 }
                 Sel sel[4][K];
+                if constexpr (LOC) {
+                    ragged_sel<K>(sel, x);
+                } else {
+                    // written out: through ragged_sel matverify_ragged<4,3> and <4,7> take two VGPRs
+                    // more and lose a wave per SIMD
 #pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    sel[0][j] = selectors(x[j].x);
-                    sel[1][j] = selectors(x[j].y);
-                    sel[2][j] = selectors(x[j].z);
-                    sel[3][j] = selectors(x[j].w);
+                    for (int j = 0; j < K; ++j) {
+                        sel[0][j] = selectors(x[j].x);
+                        sel[1][j] = selectors(x[j].y);
+                        sel[2][j] = selectors(x[j].z);
+                        sel[3][j] = selectors(x[j].w);
+                    }
                 }
                 uint32_t mask = 0;
 #pragma unroll
@@ -1917,15 +1936,7 @@ __device__ __forceinline__ void scrub_ragged_body(const RaggedScrubJob<K, R, LOC
             if (smask != 0u) mismatch_or(base, job.bit0, smask);
             if (LOC && sexcl != 0u) mismatch_or(base, job.xbit, sexcl);
         }
-        u = stop;
-        if (u >= end || s + 1 >= ns) break;
-        ++s;
-        cur = nxt;
-        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
-            ++s;
-            cur = scrub_stripe(job, s);
-        }
-    }
+    });
 }
 
 template <int K, int R>
@@ -2102,14 +2113,9 @@ __global__ __launch_bounds__(kBlock) void rows_correct(const CorrectJob job) {
 // ---------------------------------------------------------------------------
 // matrepair_ragged<K, R>: a batched repair whose stripes each have their own
 // size AND their own pattern (fec_repair_batch_ragged), k <= 4 and up to 8
-// output rows per launch.  Two kernels joined.
-//
-// The walk is matapply_ragged's: 1 KiB units, T split over the launched waves
-// by the shard_range rule, one binary search over ustart per wave, the
-// stripe's size and two offsets by scalar loads through constant-address-space
-// pointers with the next stripe's requested early, zero-size stripes passed
-// over, the fit test on both arenas (over ALL the call's rows, stored or not),
-// 64-bit addresses, ragged_span's overlapped last chunk and the byte tail.
+// output rows per launch: ragged_walk, the stripe's pattern id its extra word,
+// with matapply_ragged's fit test on both arenas (over ALL the call's rows,
+// stored or not).
 //
 // The per-stripe matrix is matrepair_mixed's: the stripe's pattern id is read
 // with its descriptor and formed through readfirstlane, so the record address
@@ -2149,77 +2155,43 @@ struct alignas(16) RaggedRepairJob {
     uint8_t* out;
 };
 
-struct RepairStripe {
-    uint64_t u0, u1;  // its units: [u0, u1)
-    uint64_t sz, ioff, ooff;
-    uint32_t id;
-};
-
-__device__ __forceinline__ RepairStripe repair_stripe(const RaggedRepairJob& job, uint32_t s) {
-    const CU64 us = (CU64)job.ustart;
-    return RepairStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.in_off)[s], ((CU64)job.out_off)[s],
-                        ((CU32)job.ids)[s]};
-}
-
 template <int K, int R>
 __global__ __launch_bounds__(kBlock) void matrepair_ragged(const RaggedRepairJob job) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t G = gridDim.x * (kBlock / 64);
-    const CU64 us = (CU64)job.ustart;
-    const uint32_t ns = job.nstripes;
-    const uint64_t total = us[ns];
-    // (a launch with a wave per unit or more needs no division)
-    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
-    uint64_t u = uniform64(g * q + (g < e ? g : e));
-    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
-    if (u >= end) return;
-    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (us[mid] <= u)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
-    RepairStripe cur = repair_stripe(job, s);
-    for (;;) {
-        RepairStripe nxt = cur;
-        if (s + 1 < ns) nxt = repair_stripe(job, s + 1);
-        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+    const RaggedDesc<2, true> desc{job.nstripes, job.ustart, job.sizes, {job.in_off, job.out_off}, job.ids};
+    ragged_walk(desc, [&](const RaggedStripe<2, true>& cur, uint32_t, uint64_t u, uint64_t stop) {
         const uint64_t sz = cur.sz;
         const uint64_t ib = job.in_bstride ? job.in_bstride : sz, ob = job.out_bstride ? job.out_bstride : sz;
-        const uint32_t id = __builtin_amdgcn_readfirstlane(cur.id);
+        const uint32_t id = __builtin_amdgcn_readfirstlane(cur.word);
         // the launch's record geometry is read from the argument segment where a stripe needs
         // it, not kept in SGPRs across the walk
         const KPtr<RaggedRepairJob> kj = kernarg_job<RaggedRepairJob>();
-        if (u < stop && id < kj->npatterns && ragged_fits(cur.ioff, ib, K, sz, job.in_bytes) &&
-            ragged_fits(cur.ooff, ob, job.rows_all, sz, job.out_bytes)) {
+        if (u < stop && id < kj->npatterns && ragged_fits(cur.off[0], ib, K, sz, job.in_bytes) &&
+            ragged_fits(cur.off[1], ob, job.rows_all, sz, job.out_bytes)) {
             // this stripe's record, mask and table pointer: formed here, dead at the closing brace
             const CU32 rp = (CU32)kj->records + size_t(id) * kj->rec_dwords;
             const uint32_t row0 = kj->row0;
             const uint32_t smask = (__builtin_amdgcn_readfirstlane(rp[kj->mask_off]) >> row0) & ((1u << R) - 1u);
             if (smask != 0u) {  // wave-uniform: a stripe with no live row here is not read
                 CU32 tp = rp + kj->tab_off;
-                const uint8_t* const in0 = job.in + cur.ioff;
-                uint8_t* const out0 = job.out + cur.ooff + row0 * ob;
-                const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
+                // and the arenas' bases, as matapply_ragged's (<4,2> and up: 8 spills where their own
+                // walk had 6)
+                const uint8_t* const in0 = kj->in + cur.off[0];
+                uint8_t* const out0 = kj->out + cur.off[1] + row0 * ob;
                 for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
                     // opaque per unit: the R row tests stay bit tests of one SGPR here; hoisted
                     // out of the unit loop each would live in an SGPR pair of its own
                     uint32_t mask = smask;
                     asm volatile("" : "+s"(mask));
-                    const uint64_t c = w * 64u + lane;
-                    const bool live = c < cps;
-                    const Span sp = ragged_span(c, sz, nfull);
+                    bool live;
+                    const Span sp = ragged_unit(w, lane, sz, &live);
+                    // the slot address advances per lane (next_row): the multiples j * ib as
+                    // wave-uniform values would live across the unit loop (<4,2> and up re-read
+                    // one from a VGPR lane per unit)
                     u32x4 x[K];
 #pragma unroll
                     for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
                     if (live) {
-                        // the slot address advances per lane (next_row): the multiples j * ib as
-                        // wave-uniform values would live across the unit loop (<4,2> and up re-read
-                        // one from a VGPR lane per unit)
                         const uint8_t* row = in0 + sp.off;
                         if (sp.full) {
 #pragma unroll
@@ -2230,13 +2202,7 @@ __global__ __launch_bounds__(kBlock) void matrepair_ragged(const RaggedRepairJob
                         }
                     }
                     Sel sel[4][K];
-#pragma unroll
-                    for (int j = 0; j < K; ++j) {
-                        sel[0][j] = selectors(x[j].x);
-                        sel[1][j] = selectors(x[j].y);
-                        sel[2][j] = selectors(x[j].z);
-                        sel[3][j] = selectors(x[j].w);
-                    }
+                    ragged_sel<K>(sel, x);
                     // the row address advances per lane, as matapply_ragged's does
                     uint8_t* orow = out0 + sp.off;
 #pragma unroll
@@ -2263,24 +2229,16 @@ __global__ __launch_bounds__(kBlock) void matrepair_ragged(const RaggedRepairJob
                 }
             }
         }
-        u = stop;
-        if (u >= end || s + 1 >= ns) break;
-        ++s;
-        cur = nxt;
-        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
-            ++s;
-            cur = repair_stripe(job, s);
-        }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
 // matcorrect_ragged<K>: in-place correction of a batch whose stripes each have
 // their own size (fec_correct_batch_ragged), k = K <= 4, over the verdict words
 // locate_finish and ragged_unfit wrote earlier in the stream -- never this
-// kernel, so the scalar reads of them are coherent.  The walk is
-// matapply_ragged's, over the ustart the location staged; the stripe's verdict
-// h is read with its descriptor by a scalar load.  Unless h names a slot AND
+// kernel, so the scalar reads of them are coherent.  ragged_walk over the
+// ustart the location staged; the stripe's verdict h is its extra word, read
+// with its descriptor by a scalar load.  Unless h names a slot AND
 // the stripe passes this kernel's own fit test over all nb slots (it does not
 // rely on the UNFIT verdict), a scalar branch goes around the whole stripe: a
 // clean stripe costs scalar loads and no vector memory instruction.
@@ -2307,57 +2265,22 @@ struct alignas(16) RaggedCorrectJob {
     uint8_t* blocks;
 };
 
-struct CorrectStripe {
-    uint64_t u0, u1;  // its units: [u0, u1)
-    uint64_t sz, off;
-    uint32_t h;
-};
-
-__device__ __forceinline__ CorrectStripe correct_stripe(const RaggedCorrectJob& job, uint32_t s) {
-    const CU64 us = (CU64)job.ustart;
-    return CorrectStripe{us[s], us[s + 1], ((CU64)job.sizes)[s], ((CU64)job.off)[s], ((CU32)job.verdict)[s]};
-}
-
 template <int K>
 __global__ __launch_bounds__(kBlock) void matcorrect_ragged(const RaggedCorrectJob job) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t g = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t G = gridDim.x * (kBlock / 64);
-    const CU64 us = (CU64)job.ustart;
-    const uint32_t ns = job.nstripes;
-    const uint64_t total = us[ns];
-    // (a launch with a wave per unit or more needs no division)
-    const uint64_t q = total <= G ? (total == G ? 1u : 0u) : total / G, e = total - q * G;
-    uint64_t u = uniform64(g * q + (g < e ? g : e));
-    const uint64_t end = uniform64(g * q + (g < e ? g : e) + q + (g < e ? 1u : 0u));
-    if (u >= end) return;
-    uint32_t lo = 0, hi = ns;  // ustart[lo] <= u < ustart[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (us[mid] <= u)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    uint32_t s = __builtin_amdgcn_readfirstlane(lo);
-    CorrectStripe cur = correct_stripe(job, s);
-    for (;;) {
-        CorrectStripe nxt = cur;
-        if (s + 1 < ns) nxt = correct_stripe(job, s + 1);
-        const uint64_t stop = cur.u1 < end ? cur.u1 : end;
+    const RaggedDesc<1, true> desc{job.nstripes, job.ustart, job.sizes, {job.off}, job.verdict};
+    ragged_walk(desc, [&](const RaggedStripe<1, true>& cur, uint32_t, uint64_t u, uint64_t stop) {
         const uint64_t sz = cur.sz;
         const uint64_t B = job.bstride ? job.bstride : sz;
-        const uint32_t h = __builtin_amdgcn_readfirstlane(cur.h);
+        const uint32_t h = __builtin_amdgcn_readfirstlane(cur.word);
         // wave-uniform: a scalar branch, not taken on clean data
-        if (h < job.nb && u < stop && ragged_fits(cur.off, B, job.nb, sz, job.bytes)) {
+        if (h < job.nb && u < stop && ragged_fits(cur.off[0], B, job.nb, sz, job.bytes)) {
             // the tables' base is read from the argument segment here, where a dirty stripe needs it
-            uint8_t* const base = job.blocks + cur.off;
+            uint8_t* const base = job.blocks + cur.off[0];
             CU32 tp = (CU32)kernarg_job<RaggedCorrectJob>()->tabs + size_t(h) * (K * 5);
-            const uint64_t nfull = sz / kChunk, cps = (sz + kChunk - 1) / kChunk;
             for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
-                const uint64_t c = w * 64u + lane;
-                const bool live = c < cps;
-                const Span sp = ragged_span(c, sz, nfull);
+                bool live;
+                const Span sp = ragged_unit(w, lane, sz, &live);
                 u32x4 x[K];
 #pragma unroll
                 for (int l = 0; l < K; ++l) {
@@ -2371,13 +2294,7 @@ __global__ __launch_bounds__(kBlock) void matcorrect_ragged(const RaggedCorrectJ
                 for (int l = 0; l < K; ++l)
                     t[l] = Tab{tp[l * 5], tp[l * 5 + 1], tp[l * 5 + 2], tp[l * 5 + 3], tp[l * 5 + 4]};
                 Sel sel[4][K];
-#pragma unroll
-                for (int l = 0; l < K; ++l) {
-                    sel[0][l] = selectors(x[l].x);
-                    sel[1][l] = selectors(x[l].y);
-                    sel[2][l] = selectors(x[l].z);
-                    sel[3][l] = selectors(x[l].w);
-                }
+                ragged_sel<K>(sel, x);
                 const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]), gf_dot<K>(t, sel[3])};
                 if (live) {
                     uint8_t* const out = base + h * B + sp.off;
@@ -2388,15 +2305,7 @@ __global__ __launch_bounds__(kBlock) void matcorrect_ragged(const RaggedCorrectJ
                 }
             }
         }
-        u = stop;
-        if (u >= end || s + 1 >= ns) break;
-        ++s;
-        cur = nxt;
-        while (cur.u1 == cur.u0 && s + 1 < ns) {  // zero-size stripes
-            ++s;
-            cur = correct_stripe(job, s);
-        }
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -5497,9 +5406,18 @@ constexpr uint64_t kRaggedGridPerCu = kGridPerCu;
 constexpr uint32_t kRaggedWaveKiB = 10;
 constexpr uint64_t ragged_units_per_wave(uint32_t k, uint32_t r) { return (kRaggedWaveKiB + k + r - 1) / (k + r); }
 
-// The four descriptor arrays in device memory.
+// grid = min(ceil(units / (per_wave * waves per workgroup)), cap)
+uint32_t ragged_grid(uint64_t units, uint64_t per_wave) {
+    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
+    const uint64_t per_wg = per_wave * (kBlock / 64), need = (units + per_wg - 1) / per_wg;
+    return static_cast<uint32_t>(need < cap ? need : cap);
+}
+
+// What a ragged call staged, in device memory: the descriptor arrays (one or
+// two offset arrays) and the call's own head bytes (a repair's records and ids).
 struct RaggedDev {
-    const uint64_t *ustart, *sizes, *in_off, *out_off;
+    const uint64_t *ustart, *sizes, *off[2];
+    const uint8_t* head;
 };
 
 const KrNames g_ragged_names("matapply_ragged");
@@ -5520,8 +5438,8 @@ struct RaggedKr {
         job.pad_ = 0;
         job.ustart = d.ustart;
         job.sizes = d.sizes;
-        job.in_off = d.in_off;
-        job.out_off = d.out_off;
+        job.in_off = d.off[0];
+        job.out_off = d.off[1];
         job.in = p.in;
         job.out = p.out;
         for (int i = 0; i < R * K; ++i) host_tab(&job.tab[i * 5], p.coef[size_t(g0) * K + i]);
@@ -5552,68 +5470,96 @@ hipError_t launch_ragged_scan(const uint64_t* sizes, uint64_t n, uint64_t maxsz,
     return e;
 }
 
-hipError_t launch_ragged_all(const RaggedSpec& p, hipStream_t stream) {
-    const uint64_t ns = p.nstripes;
-    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
+// The descriptor staging of a ragged call through one MixedRing slot, after
+// `head` bytes of the call's own (fill_head(host address) writes them; a
+// multiple of 256).  Host-side arrays: [head | ustart | sizes | off...] by one
+// copy.  Device-side arrays: the head by one copy, ragged_scan's ustart (sizes
+// past scan_maxsz counting no units) and its tile sums behind it in the slot's
+// device half, sizes and offsets where the caller has them.  `units`
+// afterwards: the call's total, 0 when every stripe is empty (nothing was
+// copied: the caller returns, nothing to launch); with device-side arrays
+// `estimate`, which only sizes the grid.  On success with units != 0 the
+// caller launches what reads `d` and the head at up.dev(), then up.done() --
+// also after a failed launch; after an error here there is nothing to undo.
+//
+// The estimate: blocks do not overlap, so the sizes sum to at most an arena
+// over its rows (ragged_units_bound).  The rounding of each stripe's last unit
+// is left out: a total above the estimate lengthens the ranges a little, one
+// below it leaves waves with less than their share (or nothing: they exit),
+// which is what a narrow shape cannot afford (ragged_units_per_wave).
+uint64_t ragged_units_bound(uint64_t bytes, uint64_t bstride, uint32_t rows) {
+    return bytes / (bstride ? 1 : rows) / kRaggedUnit;
+}
+
+struct RaggedStage {
     StagedUpload up;
-    RaggedDev d;
-    hipError_t e;
-    uint64_t units;  // of the whole call, or (device arrays) a bound on them
-    if (p.desc_host) {
-        // [ustart | sizes | in_off | out_off] by one copy
-        const size_t bytes = (4 * ns + 1) * sizeof(uint64_t);
-        if ((e = up.acquire(bytes)) != hipSuccess) return e;
-        uint64_t* h = reinterpret_cast<uint64_t*>(up.host());
-        const uint64_t total = ragged_units(p.sizes, ns, h);
-        if (!total) return hipSuccess;  // every stripe is empty: nothing copied, nothing launched
-        std::memcpy(h + ns + 1, p.sizes, ns * sizeof(uint64_t));
-        std::memcpy(h + 2 * ns + 1, p.in_off, ns * sizeof(uint64_t));
-        std::memcpy(h + 3 * ns + 1, p.out_off, ns * sizeof(uint64_t));
-        if ((e = up.copy(bytes, stream)) != hipSuccess) return e;
-        const uint64_t* dv = reinterpret_cast<const uint64_t*>(up.dev());
-        d = RaggedDev{dv, dv + ns + 1, dv + 2 * ns + 1, dv + 3 * ns + 1};
-        units = total;
-    } else {
-        // the total is not known here; it only sizes the grid, so an estimate
-        // serves: blocks do not overlap, so the sizes sum to at most either arena
-        // over its rows.  The rounding of each stripe's last unit is left out: a
-        // total above the estimate lengthens the ranges a little, one below it
-        // leaves waves with less than their share (or nothing: they exit), which
-        // is what a narrow shape cannot afford (ragged_units_per_wave).
-        const uint64_t in_units = p.in_bytes / (p.in_bstride ? 1 : p.k) / kRaggedUnit;
-        const uint64_t out_units = p.out_bytes / (p.out_bstride ? 1 : p.r) / kRaggedUnit;
-        units = std::max<uint64_t>(1, std::min(in_units, out_units));
+    RaggedDev d{};
+    uint64_t units = 0;
+
+    template <class Fill>
+    hipError_t stage(const uint64_t* sizes, std::initializer_list<const uint64_t*> offs, uint64_t ns, bool desc_host,
+                     uint64_t scan_maxsz, uint64_t estimate, size_t head, Fill fill_head, hipStream_t stream) {
         const uint64_t ntiles = (ns + kScanTile - 1) / kScanTile;
-        if ((e = up.acquire((ns + 1 + ntiles) * sizeof(uint64_t))) != hipSuccess) return e;
-        uint64_t* dv = reinterpret_cast<uint64_t*>(up.slot->dev);
-        e = launch_ragged_scan(p.sizes, ns, p.in_bytes < p.out_bytes ? p.in_bytes : p.out_bytes, dv, dv + ns + 1,
-                               stream);
-        if (e != hipSuccess) {
+        const size_t bytes = head + ((desc_host ? (1 + offs.size()) * ns : ntiles) + ns + 1) * sizeof(uint64_t);
+        hipError_t e = up.acquire(bytes);
+        if (e != hipSuccess) return e;
+        d.head = up.dev();
+        if (desc_host) {
+            uint64_t* const h = reinterpret_cast<uint64_t*>(up.host() + head);
+            if (!(units = ragged_units(sizes, ns, h))) return hipSuccess;
+            fill_head(up.host());
+            const uint64_t* const dv = reinterpret_cast<const uint64_t*>(up.dev() + head);
+            size_t at = ns + 1;
+            std::memcpy(h + at, sizes, ns * sizeof(uint64_t));
+            d.ustart = dv;
+            d.sizes = dv + at;
+            int i = 0;
+            for (const uint64_t* o : offs) {
+                at += ns;
+                std::memcpy(h + at, o, ns * sizeof(uint64_t));
+                d.off[i++] = dv + at;
+            }
+            return up.copy(bytes, stream);
+        }
+        units = std::max<uint64_t>(1, estimate);
+        if (head) {
+            fill_head(up.host());
+            if ((e = up.copy(head, stream)) != hipSuccess) return e;
+        }
+        uint64_t* const dv = reinterpret_cast<uint64_t*>(up.slot->dev + head);
+        if ((e = launch_ragged_scan(sizes, ns, scan_maxsz, dv, dv + ns + 1, stream)) != hipSuccess) {
             up.done(stream);
             return e;
         }
-        d = RaggedDev{dv, p.sizes, p.in_off, p.out_off};
+        d.ustart = dv;
+        d.sizes = sizes;
+        int i = 0;
+        for (const uint64_t* o : offs) d.off[i++] = o;
+        return hipSuccess;
     }
+};
+
+hipError_t launch_ragged_all(const RaggedSpec& p, hipStream_t stream) {
+    RaggedStage st;
+    hipError_t e = st.stage(p.sizes, {p.in_off, p.out_off}, p.nstripes, p.desc_host, std::min(p.in_bytes, p.out_bytes),
+                            std::min(ragged_units_bound(p.in_bytes, p.in_bstride, p.k),
+                                     ragged_units_bound(p.out_bytes, p.out_bstride, p.r)),
+                            0, [](uint8_t*) {}, stream);
+    if (e != hipSuccess || !st.units) return e;
     for (uint32_t g0 = 0; g0 < p.r && e == hipSuccess; g0 += kRegR) {
         const uint32_t rg = std::min<uint32_t>(kRegR, p.r - g0);
-        const uint64_t per_wg = ragged_units_per_wave(p.k, rg) * (kBlock / 64), need = (units + per_wg - 1) / per_wg;
-        e = g_ragged_launch(p.k, rg)(p, d, g0, static_cast<uint32_t>(need < cap ? need : cap), stream);
+        e = g_ragged_launch(p.k, rg)(p, st.d, g0, ragged_grid(st.units, ragged_units_per_wave(p.k, rg)), stream);
     }
-    up.done(stream);
+    st.up.done(stream);
     return e;
 }
 
 // ---- matverify_ragged / matlocate_ragged dispatch -------------------------------------
-// The three descriptor arrays of a ragged scrub in device memory.
-struct ScrubDev {
-    const uint64_t *ustart, *sizes, *off;
-};
-
 const KrNames g_ragged_verify_names("matverify_ragged");
 const KrNames g_ragged_locate_names("matlocate_ragged");
 
 template <int K, int R, bool LOC>
-hipError_t launch_ragged_scrub_kr(const RaggedScrubSpec& p, const ScrubDev& d, uint32_t g0, uint32_t grid,
+hipError_t launch_ragged_scrub_kr(const RaggedScrubSpec& p, const RaggedDev& d, uint32_t g0, uint32_t grid,
                                   hipStream_t stream) {
     RaggedScrubJob<K, R, LOC> job;
     job.bstride = p.bstride;
@@ -5626,7 +5572,7 @@ hipError_t launch_ragged_scrub_kr(const RaggedScrubSpec& p, const ScrubDev& d, u
     job.xbit = p.xbit;
     job.ustart = d.ustart;
     job.sizes = d.sizes;
-    job.off = d.off;
+    job.off = d.off[0];
     job.src = p.src;
     job.bits = p.bits;
     for (int i = 0; i < R * K; ++i) host_tab(&job.tab[i * 5], p.P[size_t(g0) * K + i]);
@@ -5645,14 +5591,14 @@ hipError_t launch_ragged_scrub_kr(const RaggedScrubSpec& p, const ScrubDev& d, u
 
 struct RaggedVerifyKr {
     template <int K, int R>
-    static hipError_t launch(const RaggedScrubSpec& p, const ScrubDev& d, uint32_t g0, uint32_t grid,
+    static hipError_t launch(const RaggedScrubSpec& p, const RaggedDev& d, uint32_t g0, uint32_t grid,
                              hipStream_t stream) {
         return launch_ragged_scrub_kr<K, R, false>(p, d, g0, grid, stream);
     }
 };
 struct RaggedLocateKr {
     template <int K, int R>
-    static hipError_t launch(const RaggedScrubSpec& p, const ScrubDev& d, uint32_t g0, uint32_t grid,
+    static hipError_t launch(const RaggedScrubSpec& p, const RaggedDev& d, uint32_t g0, uint32_t grid,
                              hipStream_t stream) {
         return launch_ragged_scrub_kr<K, R, true>(p, d, g0, grid, stream);
     }
@@ -5664,66 +5610,38 @@ constexpr KrTable<RaggedLocateKr, 2> g_ragged_locate_launch;
 // the launch's checks: measured there for stored rows at k + r = 10 and 5, not
 // for this read-only traffic.
 hipError_t launch_ragged_scrub_all(const RaggedScrubSpec& p, hipStream_t stream) {
-    const uint64_t ns = p.nstripes;
-    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
-    StagedUpload up;
-    ScrubDev d;
-    hipError_t e;
-    uint64_t units;  // of the whole call, or (device arrays) a bound on them
-    if (p.desc_host) {
-        // [ustart | sizes | offsets] by one copy
-        const size_t bytes = (3 * ns + 1) * sizeof(uint64_t);
-        if ((e = up.acquire(bytes)) != hipSuccess) return e;
-        uint64_t* h = reinterpret_cast<uint64_t*>(up.host());
-        const uint64_t total = ragged_units(p.sizes, ns, h);
-        if (!total) return hipSuccess;  // every stripe is empty: nothing copied, nothing launched
-        std::memcpy(h + ns + 1, p.sizes, ns * sizeof(uint64_t));
-        std::memcpy(h + 2 * ns + 1, p.off, ns * sizeof(uint64_t));
-        if ((e = up.copy(bytes, stream)) != hipSuccess) return e;
-        const uint64_t* dv = reinterpret_cast<const uint64_t*>(up.dev());
-        d = ScrubDev{dv, dv + ns + 1, dv + 2 * ns + 1};
-        units = total;
-    } else {
-        // an estimate sizes the grid (launch_ragged_all): blocks do not overlap
-        units = std::max<uint64_t>(1, p.bytes / (p.bstride ? 1 : p.k + p.c) / kRaggedUnit);
-        const uint64_t ntiles = (ns + kScanTile - 1) / kScanTile;
-        if ((e = up.acquire((ns + 1 + ntiles) * sizeof(uint64_t))) != hipSuccess) return e;
-        uint64_t* dv = reinterpret_cast<uint64_t*>(up.slot->dev);
-        if ((e = launch_ragged_scan(p.sizes, ns, p.bytes, dv, dv + ns + 1, stream)) != hipSuccess) {
-            up.done(stream);
-            return e;
-        }
-        d = ScrubDev{dv, p.sizes, p.off};
-    }
+    RaggedStage st;
+    hipError_t e = st.stage(p.sizes, {p.off}, p.nstripes, p.desc_host, p.bytes,
+                            ragged_units_bound(p.bytes, p.bstride, p.k + p.c), 0, [](uint8_t*) {}, stream);
+    if (e != hipSuccess || !st.units) return e;
     for (uint32_t g0 = 0; g0 < p.c && e == hipSuccess; g0 += kRegR) {
         const uint32_t rg = std::min<uint32_t>(kRegR, p.c - g0);
-        const uint64_t per_wg = ragged_units_per_wave(p.k, rg) * (kBlock / 64), need = (units + per_wg - 1) / per_wg;
-        const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
-        e = p.Q ? g_ragged_locate_launch(p.k, rg)(p, d, g0, grid, stream)
-                : g_ragged_verify_launch(p.k, rg)(p, d, g0, grid, stream);
+        const uint32_t grid = ragged_grid(st.units, ragged_units_per_wave(p.k, rg));
+        e = p.Q ? g_ragged_locate_launch(p.k, rg)(p, st.d, g0, grid, stream)
+                : g_ragged_verify_launch(p.k, rg)(p, st.d, g0, grid, stream);
     }
     if (p.keep && e == hipSuccess) {
         // a correction follows over the same descriptors: it releases the slot (ragged_scrub_release)
-        *p.keep = RaggedScrubStaged{up.slot, d.ustart, d.sizes, d.off, units};
+        *p.keep = RaggedScrubStaged{st.up.slot, st.d.ustart, st.d.sizes, st.d.off[0], st.units};
         return e;
     }
-    up.done(stream);
+    st.up.done(stream);
     return e;
 }
 
 // ---- matrepair_ragged dispatch ----------------------------------------------------------
-// The six arrays of a ragged repair in device memory.
-struct RepairDev {
-    const uint64_t *ustart, *sizes, *in_off, *out_off;
-    const uint32_t *records, *ids;
-};
-
 const KrNames g_ragged_repair_names("matrepair_ragged");
+
+// The staged head of a ragged repair: the records, then the ids the call staged
+// (host-side ones, or none given: every stripe pattern 0), each padded to 256 bytes.
+size_t ragged_repair_tab_bytes(const RaggedRepairSpec& p) {
+    return (size_t(p.npatterns) * repair_rec_dwords(p.k, p.t) * 4 + 255) / 256 * 256;
+}
 
 // Rows [g0, g0 + R) of every stripe.
 struct RaggedRepairKr {
     template <int K, int R>
-    static hipError_t launch(const RaggedRepairSpec& p, const RepairDev& d, uint32_t g0, uint32_t grid,
+    static hipError_t launch(const RaggedRepairSpec& p, const RaggedDev& d, uint32_t g0, uint32_t grid,
                              hipStream_t stream) {
         RaggedRepairJob job;
         job.in_bstride = p.in_bstride;
@@ -5740,10 +5658,10 @@ struct RaggedRepairKr {
         job.pad_ = 0;
         job.ustart = d.ustart;
         job.sizes = d.sizes;
-        job.in_off = d.in_off;
-        job.out_off = d.out_off;
-        job.records = d.records;
-        job.ids = d.ids;
+        job.in_off = d.off[0];
+        job.out_off = d.off[1];
+        job.records = reinterpret_cast<const uint32_t*>(d.head);
+        job.ids = p.ids_dev ? p.ids_dev : reinterpret_cast<const uint32_t*>(d.head + ragged_repair_tab_bytes(p));
         job.in = p.in;
         job.out = p.out;
         const hipError_t e =
@@ -5754,10 +5672,7 @@ struct RaggedRepairKr {
 };
 constexpr KrTable<RaggedRepairKr> g_ragged_repair_launch;
 
-// One MixedRing slot per call: [records | ids (host-side or none given) |
-// ustart | sizes | in_off | out_off] by one copy with host-side descriptors;
-// with device-side ones [records | ids] by one copy and ragged_scan's ustart
-// behind them in the slot's device half (launch_ragged_all).  The grid rule is
+// RaggedStage with a head of [records | ids (host-side or none given)].  The grid rule is
 // matapply_ragged's, ceil(10 / (k + r)) units per wave, r the most live rows
 // any pattern has within the launch's row group; a row group no pattern uses
 // is skipped.
@@ -5766,67 +5681,32 @@ hipError_t launch_ragged_repair_all(const RaggedRepairSpec& p, hipStream_t strea
     const uint32_t k = p.k, t = p.t;
     const uint32_t any = repair_any(p.masks, p.npatterns, t);
     if (!any) return hipSuccess;  // nothing to store: no upload, no launch
-    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
-    const size_t tab_bytes = (size_t(p.npatterns) * repair_rec_dwords(k, t) * 4 + 255) / 256 * 256;
+    const size_t tab_bytes = ragged_repair_tab_bytes(p);
     const bool stage_ids = !p.ids_dev;  // host-side ids, or none: every stripe pattern 0
     const size_t ids_bytes = stage_ids ? (size_t(ns) * 4 + 255) / 256 * 256 : 0;
-    const size_t head = tab_bytes + ids_bytes;
-    StagedUpload up;
-    RepairDev d;
-    hipError_t e;
-    uint64_t units;  // of the whole call, or (device arrays) a bound on them
-    const auto fill_head = [&] {
-        repair_fill_records(reinterpret_cast<uint32_t*>(up.host()), p.rows, p.masks, p.npatterns, k, t);
+    const auto fill_head = [&](uint8_t* host) {
+        repair_fill_records(reinterpret_cast<uint32_t*>(host), p.rows, p.masks, p.npatterns, k, t);
         if (!stage_ids) return;
         if (p.ids_host)
-            std::memcpy(up.host() + tab_bytes, p.ids_host, size_t(ns) * 4);
+            std::memcpy(host + tab_bytes, p.ids_host, size_t(ns) * 4);
         else
-            std::memset(up.host() + tab_bytes, 0, size_t(ns) * 4);
+            std::memset(host + tab_bytes, 0, size_t(ns) * 4);
     };
-    if (p.desc_host) {
-        const size_t bytes = head + (4 * ns + 1) * sizeof(uint64_t);
-        if ((e = up.acquire(bytes)) != hipSuccess) return e;
-        uint64_t* h = reinterpret_cast<uint64_t*>(up.host() + head);
-        const uint64_t total = ragged_units(p.sizes, ns, h);
-        if (!total) return hipSuccess;  // every stripe is empty: nothing copied, nothing launched
-        fill_head();
-        std::memcpy(h + ns + 1, p.sizes, ns * sizeof(uint64_t));
-        std::memcpy(h + 2 * ns + 1, p.in_off, ns * sizeof(uint64_t));
-        std::memcpy(h + 3 * ns + 1, p.out_off, ns * sizeof(uint64_t));
-        if ((e = up.copy(bytes, stream)) != hipSuccess) return e;
-        const uint64_t* dv = reinterpret_cast<const uint64_t*>(up.dev() + head);
-        d = RepairDev{dv, dv + ns + 1, dv + 2 * ns + 1, dv + 3 * ns + 1, nullptr, nullptr};
-        units = total;
-    } else {
-        // an estimate sizes the grid (launch_ragged_all): blocks do not overlap
-        const uint64_t in_units = p.in_bytes / (p.in_bstride ? 1 : k) / kRaggedUnit;
-        const uint64_t out_units = p.out_bytes / (p.out_bstride ? 1 : t) / kRaggedUnit;
-        units = std::max<uint64_t>(1, std::min(in_units, out_units));
-        const uint64_t ntiles = (ns + kScanTile - 1) / kScanTile;
-        if ((e = up.acquire(head + (ns + 1 + ntiles) * sizeof(uint64_t))) != hipSuccess) return e;
-        fill_head();
-        if ((e = up.copy(head, stream)) != hipSuccess) return e;
-        uint64_t* dv = reinterpret_cast<uint64_t*>(up.slot->dev + head);
-        e = launch_ragged_scan(p.sizes, ns, p.in_bytes < p.out_bytes ? p.in_bytes : p.out_bytes, dv, dv + ns + 1,
-                               stream);
-        if (e != hipSuccess) {
-            up.done(stream);
-            return e;
-        }
-        d = RepairDev{dv, p.sizes, p.in_off, p.out_off, nullptr, nullptr};
-    }
-    d.records = reinterpret_cast<const uint32_t*>(up.dev());
-    d.ids = stage_ids ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : p.ids_dev;
+    RaggedStage st;
+    hipError_t e = st.stage(p.sizes, {p.in_off, p.out_off}, ns, p.desc_host, std::min(p.in_bytes, p.out_bytes),
+                            std::min(ragged_units_bound(p.in_bytes, p.in_bstride, k),
+                                     ragged_units_bound(p.out_bytes, p.out_bstride, t)),
+                            tab_bytes + ids_bytes, fill_head, stream);
+    if (e != hipSuccess || !st.units) return e;
     for (uint32_t g0 = 0; g0 < t && e == hipSuccess; g0 += kRegR) {
         const uint32_t rg = std::min<uint32_t>(kRegR, t - g0);
         uint32_t rmax = 0;  // the most live rows any pattern has in this group
         for (size_t q = 0; q < p.npatterns; ++q)
             rmax = std::max<uint32_t>(rmax, __builtin_popcount((p.masks[q] >> g0) & ((1u << rg) - 1u)));
         if (!rmax) continue;  // rows no pattern stores
-        const uint64_t per_wg = ragged_units_per_wave(k, rmax) * (kBlock / 64), need = (units + per_wg - 1) / per_wg;
-        e = g_ragged_repair_launch(k, rg)(p, d, g0, static_cast<uint32_t>(need < cap ? need : cap), stream);
+        e = g_ragged_repair_launch(k, rg)(p, st.d, g0, ragged_grid(st.units, ragged_units_per_wave(k, rmax)), stream);
     }
-    up.done(stream);
+    st.up.done(stream);
     return e;
 }
 
@@ -6450,10 +6330,8 @@ hipError_t launch_ragged_correct(const RaggedCorrectSpec& p, hipStream_t stream)
     // fec_correct_batch with 3 units per wave and 1.01 x with 48 (a ZFEC_HIP_GRID_CAP sweep that
     // slowed the location too), with every stripe corrupt 1.09 x and 1.05 x.
     constexpr uint64_t kCorrectUnitsPerWave = 48;
-    const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * kRaggedGridPerCu);
-    const uint64_t per_wg = kCorrectUnitsPerWave * (kBlock / 64);
-    const uint64_t need = (std::max<uint64_t>(1, p.staged.units) + per_wg - 1) / per_wg;
-    e = launch_job(kFns[p.k], static_cast<uint32_t>(need < cap ? need : cap), kBlock, 0, stream, job);
+    e = launch_job(kFns[p.k], ragged_grid(std::max<uint64_t>(1, p.staged.units), kCorrectUnitsPerWave), kBlock, 0,
+                   stream, job);
     up.done(stream);
     if (e == hipSuccess) t_last_kernel = kNames[p.k];
     return e;
