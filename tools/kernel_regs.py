@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
-"""The register table of the ragged kernels from the amdhsa.kernels metadata
-of a device-only assembly of kernels.hip (the Makefile's HIPFLAGS plus
---cuda-device-only -S): for every kernel whose name contains "ragged" its
-vgpr_count, sgpr_count, private_segment_fixed_size (scratch), sgpr_spill_count
-and vgpr_spill_count.  Metadata only; no instruction is read.
+"""The register table of kernels.hip's kernels from the amdhsa.kernels metadata
+of a device-only assembly (the Makefile's HIPFLAGS plus --cuda-device-only
+-S): per kernel its vgpr_count, sgpr_count, private_segment_fixed_size
+(scratch), sgpr_spill_count and vgpr_spill_count.  Metadata only; no
+instruction is read.
 
-With two files it also checks the second against the first, per kernel: no
-scratch, no VGPR spill, no fewer waves per SIMD (512 / (8 * ceil(vgpr / 8))),
-no more SGPR spills; the exit status says whether all hold.
+--match REGEX (default "ragged") names the kernels a change is about; the table
+holds those.  With two files the second is checked against the first:
 
-    python tools/ragged_regs.py parent.s [this.s] [--out profiles/ragged_walk_regs.json]
+  * a matched kernel: no scratch, no VGPR spill, no fewer waves per SIMD
+    (512 / (8 * ceil(vgpr / 8))), no more SGPR spills;
+  * every other kernel: all five numbers unchanged.
+
+The exit status says whether all hold.
+
+    python tools/kernel_regs.py parent.s [this.s] [--match REGEX] [--out profiles/NAME.json]
 """
 import argparse
 import json
@@ -21,7 +26,7 @@ KEYS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "sgpr_spill_co
 
 
 def table(path):
-    """kernel name (template arguments as numbers) -> the five numbers."""
+    """kernel name (template arguments as numbers) -> the five numbers, for every kernel."""
     recs, cur = [], None
     with open(path) as f:
         for line in f:
@@ -34,7 +39,7 @@ def table(path):
                 recs.append(cur)
             elif cur is not None and key in KEYS:
                 cur[key] = int(val)
-    recs = [r for r in recs if "ragged" in r["name"] and all(k in r for k in KEYS)]
+    recs = [r for r in recs if all(k in r for k in KEYS)]
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in recs), capture_output=True, text=True,
                            check=True).stdout.splitlines()
     out = {}
@@ -53,15 +58,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
     ap.add_argument("this", nargs="?")
+    ap.add_argument("--match", default="ragged", help="regex (re.search) of the kernels the change is about")
     ap.add_argument("--out")
     args = ap.parse_args()
-    parent = table(args.parent)
-    res = {"columns": list(KEYS), "parent": parent}
+    hit = re.compile(args.match).search
+    every = table(args.parent)
+    parent = {n: v for n, v in every.items() if hit(n)}
+    res = {"columns": list(KEYS), "match": args.match, "parent": parent}
     bad = 0
     if args.this:
-        this = res["this"] = table(args.this)
-        if sorted(this) != sorted(parent):
-            print("kernel lists differ:", sorted(set(this) ^ set(parent)))
+        every_this = table(args.this)
+        this = res["this"] = {n: v for n, v in every_this.items() if hit(n)}
+        if sorted(every_this) != sorted(every):
+            print("kernel lists differ:", sorted(set(every_this) ^ set(every)))
             bad += 1
         for n in sorted(set(this) & set(parent)):
             p, t = parent[n], this[n]
@@ -69,8 +78,14 @@ def main():
             bad += broke
             if p != t:
                 print("%-28s %s -> %s%s" % (n, p, t, "  BROKEN" if broke else ""))
-        print("%d kernels, %d changed, %d break a condition" %
+        print("%d kernels match, %d changed, %d break a condition" %
               (len(this), sum(parent.get(n) != this[n] for n in this), bad))
+        moved = sorted(n for n in set(every) & set(every_this) if not hit(n) and every[n] != every_this[n])
+        for n in moved:
+            print("%-28s %s -> %s  OUTSIDE THE MATCH" % (n, every[n], every_this[n]))
+        print("%d other kernels, %d moved" % (len(every_this) - len(this), len(moved)))
+        bad += len(moved)
+        res["others"] = {"kernels": len(every_this) - len(this), "moved": moved}
     else:
         for n in sorted(parent):
             print("%-28s %s" % (n, parent[n]))

@@ -308,6 +308,123 @@ __device__ __forceinline__ KPtr<J> kernarg_job() {
     return kj;
 }
 
+// The job where its pointers and tables are read: AL (argument loads) reads
+// them in place through kernarg_job, each where it is used; otherwise through
+// the argument the compiler loaded in the prologue.
+template <bool AL, class J>
+__device__ __forceinline__ auto job_at(const J& job) {
+    if constexpr (AL)
+        return kernarg_job<J>();
+    else
+        return &job;
+}
+
+// ---- the dense batch walk --------------------------------------------------------
+// A batch of nstripes stripes of sz bytes each.  A wave's 64 units lie in ONE
+// stripe: a stripe gets wps = ceil(cps / 64) waves, the last one partly
+// masked, so the stripe number is wave-uniform.  The grid strides over
+// (stripe, wave) pairs; fill_walk (below) fills these fields.
+struct Walk {
+    uint64_t sz;
+    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
+    uint32_t wps;            // waves per stripe
+    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    uint32_t pad_;
+};
+
+// This wave's index in a grid of workgroups of WG lanes.
+template <uint32_t WG = kBlock>
+__device__ __forceinline__ uint32_t grid_wave() {
+    if constexpr (WG == 64u)
+        return blockIdx.x;
+    else
+        return blockIdx.x * (WG / 64u) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+}
+
+// The (stripe, wave) pairs of one wave, without a division per step:
+//   for (WaveWalk it(job.walk, grid_wave()); it.s < n; it.next(job.walk))
+// n is the stripe count, or the length of a list whose entries name the
+// stripes (pairs_locate, pairs_correct): then s counts entries.
+struct WaveWalk {
+    uint32_t s, w;
+    __device__ __forceinline__ WaveWalk(const Walk& k, uint32_t gw) : s(gw / k.wps), w(gw - s * k.wps) {}
+    __device__ __forceinline__ void next(const Walk& k) {
+        w += k.gs_w;
+        s += k.gs_s;
+        if (w >= k.wps) {
+            w -= k.wps;
+            ++s;
+        }
+    }
+};
+
+// This lane's chunk of wave w of a stripe: chunk w*64 + lane with chunk_span's
+// overlapped last chunk; *live: the stripe has that chunk.
+__device__ __forceinline__ Span wave_unit(const Walk& k, uint32_t w, uint32_t lane, bool* live) {
+    const uint32_t c = w * 64u + lane;
+    *live = c < k.cps;
+    return chunk_span<kChunk, true>(c, k.sz, static_cast<uint32_t>(k.sz / kChunk));
+}
+
+// ---- one unit: loads, selectors, tables, store (dense and ragged walks alike) ----
+// A dead lane loads zeros, a byte tail is zero-filled.
+__device__ __forceinline__ u32x4 load_unit(const uint8_t* p, bool live, const Span& sp) {
+    if (!live) return u32x4{0u, 0u, 0u, 0u};
+    return sp.full ? load16(p) : load_tail(p, sp.nb);
+}
+
+// N rows at once, so that all N loads are issued before any of them is used.
+template <int N>
+__device__ __forceinline__ void load_units(u32x4 (&x)[N], const uint8_t* const (&p)[N], uint64_t off, bool live,
+                                           const Span& sp) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
+    if (live) {
+        if (sp.full) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) x[j] = load16(p[j] + off);
+        } else {
+#pragma unroll
+            for (int j = 0; j < N; ++j) x[j] = load_tail(p[j] + off, sp.nb);
+        }
+    }
+}
+
+// A streaming store; no byte past the block's end is written.
+__device__ __forceinline__ void store_unit(uint8_t* p, u32x4 y, bool live, const Span& sp) {
+    if (live) {
+        if (sp.full)
+            store16_pol<0>(p, y);
+        else
+            store_tail(p, y, sp.nb);
+    }
+}
+
+// The selectors of the four dwords of each of K inputs.
+template <int K>
+__device__ __forceinline__ void unit_sel(Sel (&sel)[4][K], const u32x4 (&x)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        sel[0][j] = selectors(x[j].x);
+        sel[1][j] = selectors(x[j].y);
+        sel[2][j] = selectors(x[j].z);
+        sel[3][j] = selectors(x[j].w);
+    }
+}
+
+// One coefficient's table from its five dwords, in the argument block or in
+// device memory read through a constant-address-space pointer (scalar loads).
+typedef const __attribute__((address_space(4))) uint32_t* CU32;
+__device__ __forceinline__ Tab tab_at(const uint32_t* p) { return Tab{p[0], p[1], p[2], p[3], p[4]}; }
+__device__ __forceinline__ Tab tab_at(CU32 p) { return Tab{p[0], p[1], p[2], p[3], p[4]}; }
+
+// The K tables of one matrix row, laid out one after the other from p on.
+template <int K, class P>
+__device__ __forceinline__ void row_tabs(Tab (&t)[K], P p) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) t[j] = tab_at(p + j * 5);
+}
+
 // ---------------------------------------------------------------------------
 // matapply_reg<K, R>: compile-time k and r.  The kernel argument block holds
 // the K + R block pointers and the K*R coefficients' tables (5 dwords each):
@@ -773,10 +890,8 @@ constexpr uint32_t mixed_tab_dwords() {
 
 template <int K>
 struct alignas(16) MixedJob {
-    uint64_t sz, in_sstride, out_sstride;
-    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
-    uint32_t wps;            // waves per stripe
-    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    Walk walk;
+    uint64_t in_sstride, out_sstride;
     uint32_t npatterns;
     const uint32_t* tables;  // npatterns x mixed_tab_dwords<K>()
     const uint32_t* ids;     // nstripes pattern ids
@@ -784,70 +899,32 @@ struct alignas(16) MixedJob {
     uint8_t* out[K];
 };
 
-typedef const __attribute__((address_space(4))) uint32_t* CU32;
-
 template <int K>
 __global__ __launch_bounds__(kBlock) void matapply_mixed(const MixedJob<K> job) {
     constexpr uint32_t TD = mixed_tab_dwords<K>();
     constexpr bool AL = reg_argload(K, K);  // K = 4: each row's tables are read where they are used
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
     const CU32 ids = (CU32)job.ids;
-    while (s < job.nstripes) {
-        const uint32_t c = w * 64u + lane;
-        const bool live = c < job.cps;
-        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        const uint32_t s = it.s;
+        bool live;
+        const Span sp = wave_unit(job.walk, it.w, lane, &live);
         u32x4 x[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
-        if (live) {
-            const uint64_t ib = s * job.in_sstride + sp.off;
-            if (sp.full) {
-#pragma unroll
-                for (int j = 0; j < K; ++j) x[j] = load16(job.in[j] + ib);
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) x[j] = load_tail(job.in[j] + ib, sp.nb);
-            }
-        }
+        load_units<K>(x, job.in, s * job.in_sstride + sp.off, live, sp);
         const uint32_t id = __builtin_amdgcn_readfirstlane(ids[s]);
         if (id < job.npatterns) {
             CU32 tp = (CU32)job.tables + size_t(id) * TD;
             Sel sel[4][K];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                sel[0][j] = selectors(x[j].x);
-                sel[1][j] = selectors(x[j].y);
-                sel[2][j] = selectors(x[j].z);
-                sel[3][j] = selectors(x[j].w);
-            }
+            unit_sel<K>(sel, x);
             const uint64_t ob = s * job.out_sstride + sp.off;
 #pragma unroll
             for (int r = 0; r < K; ++r) {
                 if constexpr (AL) asm volatile("" : "+s"(tp));
                 Tab t[K];
-#pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    const uint32_t i = (r * K + j) * 5;
-                    t[j] = Tab{tp[i], tp[i + 1], tp[i + 2], tp[i + 3], tp[i + 4]};
-                }
+                row_tabs<K>(t, tp + r * K * 5);
                 const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]), gf_dot<K>(t, sel[3])};
-                if (live) {
-                    if (sp.full)
-                        store16_pol<0>(job.out[r] + ob, y);
-                    else
-                        store_tail(job.out[r] + ob, y, sp.nb);
-                }
+                store_unit(job.out[r] + ob, y, live, sp);
             }
-        }
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
         }
     }
 }
@@ -1004,18 +1081,6 @@ __device__ __forceinline__ const uint8_t* next_row(const uint8_t* row, uint64_t 
     return row;
 }
 
-// The selectors of the four dwords of each of K inputs.
-template <int K>
-__device__ __forceinline__ void ragged_sel(Sel (&sel)[4][K], const u32x4 (&x)[K]) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        sel[0][j] = selectors(x[j].x);
-        sel[1][j] = selectors(x[j].y);
-        sel[2][j] = selectors(x[j].z);
-        sel[3][j] = selectors(x[j].w);
-    }
-}
-
 template <int K, int R>
 __global__ __launch_bounds__(kBlock) void matapply_ragged(const RaggedJob<K, R> job) {
     using J = RaggedJob<K, R>;
@@ -1060,7 +1125,7 @@ __global__ __launch_bounds__(kBlock) void matapply_ragged(const RaggedJob<K, R> 
                     }
                 }
                 Sel sel[4][K];
-                ragged_sel<K>(sel, x);
+                unit_sel<K>(sel, x);
                 // the row address advances per lane: R wave-uniform row bases would
                 // live across the unit loop in SGPRs the walk has no room for
                 uint8_t* orow = out0 + sp.off;
@@ -1179,30 +1244,43 @@ __global__ __launch_bounds__(kBlock) void ragged_scan(const ScanJob job) {
 // to 8 check rows per launch.  The R rows matapply_reg<K, R> would store are
 // computed in registers from the K basis blocks and compared with the R
 // stored check blocks: the launch reads K + R rows and writes nothing unless a
-// row differs.  matapply_mixed's walk: a wave's 64 units lie in one stripe, so
-// the stripe number is wave-uniform.  Per unit all K + R loads are issued
-// before any arithmetic; per row the four words of computed ^ stored are
-// OR-ed, one ballot turns "any lane differs" into one bit of a wave-uniform
-// mask, and if the mask is nonzero ONE lane issues one relaxed device-scope
-// fetch_or per touched word of the stripe's mismatch words.  Dead lanes (past
-// the stripe's last chunk) hold zeros on both sides; the byte tail is
-// zero-filled on both sides by load_tail; the overlapped last chunk of
+// row differs.  WaveWalk: the stripe number is wave-uniform.  Per unit all
+// K + R loads are issued before any arithmetic; per row computed ^ stored, the
+// row's syndrome (four words), replaces the stored row in its registers, its
+// words are OR-ed, one ballot turns "any lane differs" into one bit of a
+// wave-uniform mask, and if the mask is nonzero ONE lane issues one relaxed
+// device-scope fetch_or per touched word of the stripe's mismatch words.  Dead
+// lanes (past the stripe's last chunk) hold zeros on both sides; the byte tail
+// is zero-filled on both sides by load_tail; the overlapped last chunk of
 // chunk_span compares some bytes twice, which is harmless.  OR is
 // order-independent, so the result is deterministic.
+//
+// matlocate_reg<K, R>: single-block error location (fec_locate_batch), k <= 4
+// and 2 <= R <= 8 checks, all in one launch (bit0 = 0).  The same body
+// (scrub_body, LOC choosing the family) down to the mask.  Only under a scalar
+// branch on mask != 0 the K hypotheses "only basis slot j is corrupt" are
+// tested: the syndromes of such an error satisfy s_r = Q[r][j] . s_0 (Q[r][j] =
+// P[r][j] / P[0][j]) at every byte, so a lane where some s_r ^ Q[r][j] . s_0 is
+// nonzero refutes j, and one ballot per j gives the wave's excluded bits.  A
+// wave whose syndromes are all zero refutes nothing, so skipping it loses
+// nothing.  The Q tables sit behind the verify tables in the argument block
+// and are read through the kernel-argument pointer inside the branch only: the
+// clean path carries no SGPRs for them, performs no store and no atomic.  One
+// lane then ORs mismatch bits (from bit 0) and excluded bits (from bit xbit)
+// into the stripe's working words.
 // ---------------------------------------------------------------------------
-template <int K, int R>
-struct alignas(16) VerifyJob {
-    uint64_t sz, sstride;
-    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
-    uint32_t wps;            // waves per stripe
-    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
-    uint32_t words;          // mismatch words per stripe
-    uint32_t bit0;           // bit index of this launch's first check row
-    uint32_t pad_;
-    uint32_t* mismatch;
+template <int K, int R, bool LOC>
+struct alignas(16) ScrubJob {
+    Walk walk;
+    uint64_t sstride;
+    uint32_t words;  // mismatch (verify) or working (locate) words per stripe
+    uint32_t bit0;   // bit index of this launch's first check row
+    uint32_t xbit;   // bit index of basis slot 0's excluded bit (locate)
+    uint32_t* bits;
     const uint8_t* in[K];
     const uint8_t* chk[R];
-    uint32_t tab[K * R * 5];  // the RegJob layout: row i, input j at (i*K + j)*5
+    uint32_t tab[K * R * 5];                   // the RegJob layout: row i, input j at (i*K + j)*5
+    uint32_t qtab[LOC ? K * (R - 1) * 5 : 1];  // Q[r][j], r = 1..R-1, at ((r-1)*K + j)*5
 };
 
 // ORs `bits` (bit 0 = bit index `bit` of the stripe's words) into the words at
@@ -1215,41 +1293,41 @@ __device__ __forceinline__ void mismatch_or(uint32_t* base, uint32_t bit, uint32
     if (hi) (void)__hip_atomic_fetch_or(wp + 1, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int K, int R>
-__global__ __launch_bounds__(kBlock) void matverify_reg(const VerifyJob<K, R> job) {
-    constexpr bool AL = reg_argload(K, R);  // each row's tables are read where they are used
+// <1,8> and <3,3> sit at the SGPR limit as matverify_reg shapes (106 and 105)
+// and would spill with the dirty branch's registers on top: they too read
+// tables and pointers where they are used.  So does <1,7> (100 SGPRs): with
+// its tables held it takes 72 VGPRs through scrub_body, a wave per SIMD fewer.
+constexpr bool locate_argload(int K, int R) {
+    return reg_argload(K, R) || K * R * 5 + 2 * (K + R) >= 56 || (K == 1 && R == 7);
+}
+
+template <int K, int R, bool LOC>
+__device__ __forceinline__ void scrub_body(const ScrubJob<K, R, LOC>& job) {
+    using J = ScrubJob<K, R, LOC>;
+    // each row's tables are read where they are used; the block pointers too,
+    // so they do not sit in SGPRs next to the tables (<4,8> spilled otherwise)
+    constexpr bool AL = LOC ? locate_argload(K, R) : reg_argload(K, R);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
-    while (s < job.nstripes) {
-        const uint32_t c = w * 64u + lane;
-        const bool live = c < job.cps;
-        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        bool live;
+        const Span sp = wave_unit(job.walk, it.w, lane, &live);
+        // K + R loads under ONE test of live and sp.full, written out: through
+        // load_units (one call per array, or one over K + R pointers) a third of
+        // the forms take more VGPRs and some lose a wave per SIMD
         u32x4 x[K], y[R];
 #pragma unroll
         for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
         for (int r = 0; r < R; ++r) y[r] = u32x4{0u, 0u, 0u, 0u};
         if (live) {
-            const uint64_t ib = s * job.sstride + sp.off;
-            // AL: the block pointers too are read where they are used, so they
-            // do not sit in SGPRs next to the tables (<4,8> spilled otherwise)
+            const uint64_t ib = it.s * job.sstride + sp.off;
+            const auto kj = job_at<AL>(job);
             const uint8_t* in[K];
             const uint8_t* chk[R];
-            if constexpr (AL) {
-                const KPtr<VerifyJob<K, R>> kj = kernarg_job<VerifyJob<K, R>>();
 #pragma unroll
-                for (int j = 0; j < K; ++j) in[j] = kj->in[j];
+            for (int j = 0; j < K; ++j) in[j] = kj->in[j];
 #pragma unroll
-                for (int r = 0; r < R; ++r) chk[r] = kj->chk[r];
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) in[j] = job.in[j];
-#pragma unroll
-                for (int r = 0; r < R; ++r) chk[r] = job.chk[r];
-            }
+            for (int r = 0; r < R; ++r) chk[r] = kj->chk[r];
             if (sp.full) {
 #pragma unroll
                 for (int j = 0; j < K; ++j) x[j] = load16(in[j] + ib);
@@ -1263,50 +1341,65 @@ __global__ __launch_bounds__(kBlock) void matverify_reg(const VerifyJob<K, R> jo
             }
         }
         Sel sel[4][K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            sel[0][j] = selectors(x[j].x);
-            sel[1][j] = selectors(x[j].y);
-            sel[2][j] = selectors(x[j].z);
-            sel[3][j] = selectors(x[j].w);
-        }
+        unit_sel<K>(sel, x);
         uint32_t mask = 0;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             Tab t[K];
-            if constexpr (AL) {
-                const KPtr<VerifyJob<K, R>> kj = kernarg_job<VerifyJob<K, R>>();
-#pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    const uint32_t i = (r * K + j) * 5;
-                    t[j] = Tab{kj->tab[i], kj->tab[i + 1], kj->tab[i + 2], kj->tab[i + 3], kj->tab[i + 4]};
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    const uint32_t* p = &job.tab[(r * K + j) * 5];
-                    t[j] = Tab{p[0], p[1], p[2], p[3], p[4]};
-                }
-            }
-            const uint32_t d = (gf_dot<K>(t, sel[0]) ^ y[r].x) | (gf_dot<K>(t, sel[1]) ^ y[r].y) |
-                               (gf_dot<K>(t, sel[2]) ^ y[r].z) | (gf_dot<K>(t, sel[3]) ^ y[r].w);
+            auto kj = job_at<AL>(job);
+            // as scrub_ragged_body: the pointer is formed after the previous row's
+            // ballot, so at most two rows' tables are in SGPRs at a time
+            // (matlocate_reg<4,6> and <4,7> spilled 7 and 36 SGPRs without it)
+            if constexpr (AL && LOC) asm volatile("" : "+s"(kj) : "s"(mask));
+            row_tabs<K>(t, kj->tab + r * K * 5);
+            // the syndrome of row r replaces the stored row
+            y[r].x ^= gf_dot<K>(t, sel[0]);
+            y[r].y ^= gf_dot<K>(t, sel[1]);
+            y[r].z ^= gf_dot<K>(t, sel[2]);
+            y[r].w ^= gf_dot<K>(t, sel[3]);
+            const uint32_t d = y[r].x | y[r].y | y[r].z | y[r].w;
             if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << r;
         }
-        if (mask != 0u && lane == 0u) mismatch_or(job.mismatch + size_t(s) * job.words, job.bit0, mask);
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
+        if (mask != 0u) {  // wave-uniform: a scalar branch, not taken on clean data
+            uint32_t excl = 0;
+            if constexpr (LOC) {
+                const Sel z[4][1] = {{selectors(y[0].x)}, {selectors(y[0].y)}, {selectors(y[0].z)}, {selectors(y[0].w)}};
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    uint32_t d = 0;
+#pragma unroll
+                    for (int r = 1; r < R; ++r) {
+                        const Tab q[1] = {tab_at(kernarg_job<J>()->qtab + ((r - 1) * K + j) * 5)};
+                        d |= (y[r].x ^ gf_dot<1>(q, z[0])) | (y[r].y ^ gf_dot<1>(q, z[1])) |
+                             (y[r].z ^ gf_dot<1>(q, z[2])) | (y[r].w ^ gf_dot<1>(q, z[3]));
+                    }
+                    if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) excl |= 1u << j;
+                }
+            }
+            if (lane == 0u) {
+                uint32_t* const base = job.bits + size_t(it.s) * job.words;
+                mismatch_or(base, LOC ? 0u : job.bit0, mask);
+                if (LOC && excl != 0u) mismatch_or(base, job.xbit, excl);
+            }
         }
     }
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matverify_reg(const ScrubJob<K, R, false> job) {
+    scrub_body<K, R, false>(job);
+}
+
+template <int K, int R>
+__global__ __launch_bounds__(kBlock) void matlocate_reg(const ScrubJob<K, R, true> job) {
+    scrub_body<K, R, true>(job);
 }
 
 // ---------------------------------------------------------------------------
 // matrepair_mixed<K, R>: a batched repair whose stripes each have their own
 // pattern (fec_repair_batch), k <= 4 and up to 8 output rows per launch.  It is
-// matapply_mixed<K> with R rows instead of K: the same walk (a wave's 64 units
-// lie in ONE stripe), the stripe's id and its record address wave-uniform,
+// matapply_mixed<K> with R rows instead of K: WaveWalk (a wave's 64 units lie
+// in ONE stripe), the stripe's id and its record address wave-uniform,
 // formed through readfirstlane and read through constant-address-space
 // pointers, so ids, mask and tables are scalar loads and v_perm takes the
 // tables as SGPR pairs.
@@ -1320,14 +1413,12 @@ __global__ __launch_bounds__(kBlock) void matverify_reg(const VerifyJob<K, R> jo
 // no arithmetic and no store, so none of its bytes is touched.  An id >=
 // npatterns reads no record and leaves its stripe unwritten.  Each row's
 // tables (and, for the larger shapes, its output pointer) are read where they
-// are used, as in matapply_mixed<4> and matverify_reg.
+// are used (the pin on the record pointer, job_at for the pointer).
 // ---------------------------------------------------------------------------
 template <int K, int R>
 struct alignas(16) RepairJob {
-    uint64_t sz, in_sstride, out_sstride;
-    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
-    uint32_t wps;            // waves per stripe
-    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    Walk walk;
+    uint64_t in_sstride, out_sstride;
     uint32_t npatterns;
     uint32_t rec_dwords;     // dwords per pattern record
     uint32_t tab_off;        // dword offset in a record of this launch's first row
@@ -1343,73 +1434,32 @@ template <int K, int R>
 __global__ __launch_bounds__(kBlock) void matrepair_mixed(const RepairJob<K, R> job) {
     constexpr bool AL = reg_argload(K, R);  // each row's tables are read where they are used
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
     const CU32 ids = (CU32)job.ids;
-    while (s < job.nstripes) {
-        const uint32_t c = w * 64u + lane;
-        const bool live = c < job.cps;
-        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        const uint32_t s = it.s;
+        bool live;
+        const Span sp = wave_unit(job.walk, it.w, lane, &live);
         u32x4 x[K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
-        if (live) {
-            const uint64_t ib = s * job.in_sstride + sp.off;
-            if (sp.full) {
-#pragma unroll
-                for (int j = 0; j < K; ++j) x[j] = load16(job.in[j] + ib);
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) x[j] = load_tail(job.in[j] + ib, sp.nb);
-            }
-        }
+        load_units<K>(x, job.in, s * job.in_sstride + sp.off, live, sp);
         const uint32_t id = __builtin_amdgcn_readfirstlane(ids[s]);
         if (id < job.npatterns) {
             const CU32 rp = (CU32)job.records + size_t(id) * job.rec_dwords;
             const uint32_t mask = __builtin_amdgcn_readfirstlane(rp[job.mask_off]) >> job.bit0;
             CU32 tp = rp + job.tab_off;
             Sel sel[4][K];
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                sel[0][j] = selectors(x[j].x);
-                sel[1][j] = selectors(x[j].y);
-                sel[2][j] = selectors(x[j].z);
-                sel[3][j] = selectors(x[j].w);
-            }
+            unit_sel<K>(sel, x);
             const uint64_t ob = s * job.out_sstride + sp.off;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 if ((mask >> r) & 1u) {  // wave-uniform: a scalar branch
                     if constexpr (AL) asm volatile("" : "+s"(tp));
                     Tab t[K];
-#pragma unroll
-                    for (int j = 0; j < K; ++j) {
-                        const uint32_t i = (r * K + j) * 5;
-                        t[j] = Tab{tp[i], tp[i + 1], tp[i + 2], tp[i + 3], tp[i + 4]};
-                    }
+                    row_tabs<K>(t, tp + r * K * 5);
                     const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]),
                                   gf_dot<K>(t, sel[3])};
-                    uint8_t* out;
-                    if constexpr (AL)
-                        out = kernarg_job<RepairJob<K, R>>()->out[r];
-                    else
-                        out = job.out[r];
-                    if (live) {
-                        if (sp.full)
-                            store16_pol<0>(out + ob, y);
-                        else
-                            store_tail(out + ob, y, sp.nb);
-                    }
+                    store_unit(job_at<AL>(job)->out[r] + ob, y, live, sp);
                 }
             }
-        }
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
         }
     }
 }
@@ -1418,13 +1468,13 @@ __global__ __launch_bounds__(kBlock) void matrepair_mixed(const RepairJob<K, R> 
 // rows_differ: the second step of parity verification for the shapes
 // matverify_reg does not take.  The expected check rows were computed into
 // scratch (a) by whatever kernel apply_matrix picks; this kernel compares them
-// with the stored rows (b): run-time r <= kMaxOut, the same walk and the same
+// with the stored rows (b): run-time r <= kMaxOut, WaveWalk and scrub_body's
 // ballot-then-OR reduction.  Rows go in groups of 4 so that 8 loads are in
 // flight before the first comparison.
 // ---------------------------------------------------------------------------
 struct alignas(16) DifferJob {
-    uint64_t sz, a_sstride, b_sstride;
-    uint32_t nstripes, cps, wps, gs_w, gs_s;
+    Walk walk;
+    uint64_t a_sstride, b_sstride;
     uint32_t words, bit0, r;
     uint32_t* mismatch;
     const uint8_t* a[kMaxOut];
@@ -1434,30 +1484,20 @@ struct alignas(16) DifferJob {
 __global__ __launch_bounds__(kBlock) void rows_differ(const DifferJob job) {
     constexpr uint32_t G = 4;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
-    while (s < job.nstripes) {
-        const uint32_t c = w * 64u + lane;
-        const bool live = c < job.cps;
-        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
-        const uint64_t ao = s * job.a_sstride + sp.off, bo = s * job.b_sstride + sp.off;
-        uint32_t* const base = job.mismatch + size_t(s) * job.words;
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        bool live;
+        const Span sp = wave_unit(job.walk, it.w, lane, &live);
+        const uint64_t ao = it.s * job.a_sstride + sp.off, bo = it.s * job.b_sstride + sp.off;
+        uint32_t* const base = job.mismatch + size_t(it.s) * job.words;
         for (uint32_t r0 = 0; r0 < job.r; r0 += G) {
             const uint32_t n = job.r - r0 < G ? job.r - r0 : G;
             u32x4 p[G], q[G];
 #pragma unroll
             for (uint32_t i = 0; i < G; ++i) {
                 p[i] = q[i] = u32x4{0u, 0u, 0u, 0u};
-                if (i < n && live) {
-                    if (sp.full) {
-                        p[i] = load16(job.a[r0 + i] + ao);
-                        q[i] = load16(job.b[r0 + i] + bo);
-                    } else {
-                        p[i] = load_tail(job.a[r0 + i] + ao, sp.nb);
-                        q[i] = load_tail(job.b[r0 + i] + bo, sp.nb);
-                    }
+                if (i < n) {
+                    p[i] = load_unit(job.a[r0 + i] + ao, live, sp);
+                    q[i] = load_unit(job.b[r0 + i] + bo, live, sp);
                 }
             }
             uint32_t mask = 0;
@@ -1467,162 +1507,6 @@ __global__ __launch_bounds__(kBlock) void rows_differ(const DifferJob job) {
                 if (__builtin_amdgcn_ballot_w64((d.x | d.y | d.z | d.w) != 0u) != 0ull) mask |= 1u << i;
             }
             if (mask != 0u && lane == 0u) mismatch_or(base, job.bit0 + r0, mask);
-        }
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// matlocate_reg<K, R>: single-block error location (fec_locate_batch), k <= 4
-// and 2 <= R <= 8 checks, all in one launch.  It is matverify_reg<K, R> -- the
-// same walk, loads, zero-filled tail, dead lanes and overlapped last chunk --
-// except that computed ^ stored, the R syndromes of the unit (four words
-// each), stay in the registers that held the stored rows.  The ballots form
-// the wave-uniform mismatch mask as there.  Only under a scalar branch on
-// mask != 0 the K hypotheses "only basis slot j is corrupt" are tested: the
-// syndromes of such an error satisfy s_r = Q[r][j] . s_0 (Q[r][j] = P[r][j] /
-// P[0][j]) at every byte, so a lane where some s_r ^ Q[r][j] . s_0 is nonzero
-// refutes j, and one ballot per j gives the wave's excluded bits.  A wave whose
-// syndromes are all zero refutes nothing, so skipping it loses nothing.  The Q
-// tables sit behind the verify tables in the argument block and are read
-// through the kernel-argument pointer inside the branch only: the clean path
-// carries no SGPRs for them, performs no store and no atomic.  One lane then
-// ORs mismatch bits (from bit 0) and excluded bits (from bit xbit) into the
-// stripe's working words.
-// ---------------------------------------------------------------------------
-template <int K, int R>
-struct alignas(16) LocateJob {
-    uint64_t sz, sstride;
-    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
-    uint32_t wps;            // waves per stripe
-    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
-    uint32_t words;          // working words per stripe
-    uint32_t xbit;           // bit index of basis slot 0's excluded bit
-    uint32_t pad_;
-    uint32_t* bits;
-    const uint8_t* in[K];
-    const uint8_t* chk[R];
-    uint32_t tab[K * R * 5];         // the RegJob layout: row i, input j at (i*K + j)*5
-    uint32_t qtab[K * (R - 1) * 5];  // Q[r][j], r = 1..R-1, at ((r-1)*K + j)*5
-};
-
-// <1,8> and <3,3> sit at the SGPR limit as matverify_reg shapes (106 and 105)
-// and would spill with the dirty branch's registers on top: they too read
-// tables and pointers where they are used.
-constexpr bool locate_argload(int K, int R) { return reg_argload(K, R) || K * R * 5 + 2 * (K + R) >= 56; }
-
-template <int K, int R>
-__global__ __launch_bounds__(kBlock) void matlocate_reg(const LocateJob<K, R> job) {
-    constexpr bool AL = locate_argload(K, R);  // each row's tables are read where they are used
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
-    while (s < job.nstripes) {
-        const uint32_t c = w * 64u + lane;
-        const bool live = c < job.cps;
-        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
-        u32x4 x[K], y[R];
-#pragma unroll
-        for (int j = 0; j < K; ++j) x[j] = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int r = 0; r < R; ++r) y[r] = u32x4{0u, 0u, 0u, 0u};
-        if (live) {
-            const uint64_t ib = s * job.sstride + sp.off;
-            const uint8_t* in[K];
-            const uint8_t* chk[R];
-            if constexpr (AL) {
-                const KPtr<LocateJob<K, R>> kj = kernarg_job<LocateJob<K, R>>();
-#pragma unroll
-                for (int j = 0; j < K; ++j) in[j] = kj->in[j];
-#pragma unroll
-                for (int r = 0; r < R; ++r) chk[r] = kj->chk[r];
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) in[j] = job.in[j];
-#pragma unroll
-                for (int r = 0; r < R; ++r) chk[r] = job.chk[r];
-            }
-            if (sp.full) {
-#pragma unroll
-                for (int j = 0; j < K; ++j) x[j] = load16(in[j] + ib);
-#pragma unroll
-                for (int r = 0; r < R; ++r) y[r] = load16(chk[r] + ib);
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) x[j] = load_tail(in[j] + ib, sp.nb);
-#pragma unroll
-                for (int r = 0; r < R; ++r) y[r] = load_tail(chk[r] + ib, sp.nb);
-            }
-        }
-        Sel sel[4][K];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            sel[0][j] = selectors(x[j].x);
-            sel[1][j] = selectors(x[j].y);
-            sel[2][j] = selectors(x[j].z);
-            sel[3][j] = selectors(x[j].w);
-        }
-        uint32_t mask = 0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            Tab t[K];
-            if constexpr (AL) {
-                const KPtr<LocateJob<K, R>> kj = kernarg_job<LocateJob<K, R>>();
-#pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    const uint32_t i = (r * K + j) * 5;
-                    t[j] = Tab{kj->tab[i], kj->tab[i + 1], kj->tab[i + 2], kj->tab[i + 3], kj->tab[i + 4]};
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < K; ++j) {
-                    const uint32_t* p = &job.tab[(r * K + j) * 5];
-                    t[j] = Tab{p[0], p[1], p[2], p[3], p[4]};
-                }
-            }
-            // the syndrome of row r replaces the stored row
-            y[r].x ^= gf_dot<K>(t, sel[0]);
-            y[r].y ^= gf_dot<K>(t, sel[1]);
-            y[r].z ^= gf_dot<K>(t, sel[2]);
-            y[r].w ^= gf_dot<K>(t, sel[3]);
-            const uint32_t d = y[r].x | y[r].y | y[r].z | y[r].w;
-            if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) mask |= 1u << r;
-        }
-        if (mask != 0u) {  // wave-uniform: a scalar branch, not taken on clean data
-            const Sel z[4][1] = {{selectors(y[0].x)}, {selectors(y[0].y)}, {selectors(y[0].z)}, {selectors(y[0].w)}};
-            uint32_t excl = 0;
-#pragma unroll
-            for (int j = 0; j < K; ++j) {
-                uint32_t d = 0;
-#pragma unroll
-                for (int r = 1; r < R; ++r) {
-                    const KPtr<LocateJob<K, R>> kj = kernarg_job<LocateJob<K, R>>();
-                    const uint32_t i = ((r - 1) * K + j) * 5;
-                    const Tab q[1] = {
-                        Tab{kj->qtab[i], kj->qtab[i + 1], kj->qtab[i + 2], kj->qtab[i + 3], kj->qtab[i + 4]}};
-                    d |= (y[r].x ^ gf_dot<1>(q, z[0])) | (y[r].y ^ gf_dot<1>(q, z[1])) |
-                         (y[r].z ^ gf_dot<1>(q, z[2])) | (y[r].w ^ gf_dot<1>(q, z[3]));
-                }
-                if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) excl |= 1u << j;
-            }
-            if (lane == 0u) {
-                uint32_t* const base = job.bits + size_t(s) * job.words;
-                mismatch_or(base, 0u, mask);
-                if (excl != 0u) mismatch_or(base, job.xbit, excl);
-            }
-        }
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
         }
     }
 }
@@ -1640,8 +1524,8 @@ __global__ __launch_bounds__(kBlock) void matlocate_reg(const LocateJob<K, R> jo
 // basis slots at a time.  Dirty units are rare; their speed is not a goal.
 // ---------------------------------------------------------------------------
 struct alignas(16) LocateRowsJob {
-    uint64_t sz, a_sstride, b_sstride;
-    uint32_t nstripes, cps, wps, gs_w, gs_s;
+    Walk walk;
+    uint64_t a_sstride, b_sstride;
     uint32_t words, bit0, r;
     uint32_t k, xbit, pad_;
     uint32_t* bits;
@@ -1652,25 +1536,15 @@ struct alignas(16) LocateRowsJob {
     const uint8_t* b[kMaxOut];
 };
 
-__device__ __forceinline__ u32x4 load_unit(const uint8_t* p, bool live, const Span& sp) {
-    if (!live) return u32x4{0u, 0u, 0u, 0u};
-    return sp.full ? load16(p) : load_tail(p, sp.nb);
-}
-
 __global__ __launch_bounds__(kBlock) void rows_locate(const LocateRowsJob job) {
     constexpr uint32_t G = 4;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
     const CU32 qtab = (CU32)job.qtab;
-    while (s < job.nstripes) {
-        const uint32_t c = w * 64u + lane;
-        const bool live = c < job.cps;
-        const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
-        const uint64_t ao = s * job.a_sstride + sp.off, bo = s * job.b_sstride + sp.off;
-        uint32_t* const base = job.bits + size_t(s) * job.words;
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        bool live;
+        const Span sp = wave_unit(job.walk, it.w, lane, &live);
+        const uint64_t ao = it.s * job.a_sstride + sp.off, bo = it.s * job.b_sstride + sp.off;
+        uint32_t* const base = job.bits + size_t(it.s) * job.words;
         // s_0: the first group has it as its row 0, a later group reads the pair again
         u32x4 s0{0u, 0u, 0u, 0u};
         bool dirty = false;
@@ -1712,8 +1586,7 @@ __global__ __launch_bounds__(kBlock) void rows_locate(const LocateRowsJob job) {
                     const u32x4 si = load_unit(job.a[i] + ao, live, sp) ^ load_unit(job.b[i] + bo, live, sp);
                     const CU32 tp = qtab + (size_t(gi - 1u) * job.k + j0) * 5u;
                     for (uint32_t jj = 0; jj < nj; ++jj) {
-                        const Tab t[1] = {Tab{tp[jj * 5u], tp[jj * 5u + 1u], tp[jj * 5u + 2u], tp[jj * 5u + 3u],
-                                              tp[jj * 5u + 4u]}};
+                        const Tab t[1] = {tab_at(tp + jj * 5u)};
                         const uint32_t d = (si.x ^ gf_dot<1>(t, z[0])) | (si.y ^ gf_dot<1>(t, z[1])) |
                                            (si.z ^ gf_dot<1>(t, z[2])) | (si.w ^ gf_dot<1>(t, z[3]));
                         if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) excl |= 1u << jj;
@@ -1721,12 +1594,6 @@ __global__ __launch_bounds__(kBlock) void rows_locate(const LocateRowsJob job) {
                 }
                 if (excl != 0u && lane == 0u) mismatch_or(base, job.xbit + j0, excl);
             }
-        }
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
         }
     }
 }
@@ -1868,9 +1735,9 @@ __device__ __forceinline__ void scrub_ragged_body(const RaggedScrubJob<K, R, LOC
                 }
                 Sel sel[4][K];
                 if constexpr (LOC) {
-                    ragged_sel<K>(sel, x);
+                    unit_sel<K>(sel, x);
                 } else {
-                    // written out: through ragged_sel matverify_ragged<4,3> and <4,7> take two VGPRs
+                    // written out: through unit_sel matverify_ragged<4,3> and <4,7> take two VGPRs
                     // more and lose a wave per SIMD
 #pragma unroll
                     for (int j = 0; j < K; ++j) {
@@ -1981,7 +1848,7 @@ __global__ __launch_bounds__(kBlock) void ragged_unfit(const UnfitJob job) {
 
 // ---------------------------------------------------------------------------
 // matcorrect_reg<K> / rows_correct: in-place correction (fec_correct_batch)
-// over the verdict words locate_finish wrote.  The walk is matrepair_mixed's
+// over the verdict words locate_finish wrote.  The walk is WaveWalk
 // (a wave's 64 units lie in ONE stripe), but the stripe's verdict h is read
 // FIRST, wave-uniform through a constant-address-space pointer: a verdict >=
 // nb (CLEAN, MANY, UNKNOWN) takes a scalar branch around everything, so a
@@ -2005,12 +1872,9 @@ __global__ __launch_bounds__(kBlock) void ragged_unfit(const UnfitJob job) {
 // stripes are rare; its speed is not a goal.
 // ---------------------------------------------------------------------------
 struct alignas(16) CorrectJob {
-    uint64_t sz, bstride, sstride;
-    uint32_t nstripes, cps;  // cps: 16-byte chunks per stripe
-    uint32_t wps;            // waves per stripe
-    uint32_t gs_w, gs_s;     // grid stride expressed as (waves, stripes): stride = gs_s*wps + gs_w
+    Walk walk;
+    uint64_t bstride, sstride;
     uint32_t k, nb;
-    uint32_t pad_;
     const uint32_t* tabs;     // nb records of k * 5 dwords
     const uint32_t* verdict;  // nstripes verdict words
     uint8_t* blocks;          // slot 0 of the launch's first stripe (and byte range)
@@ -2019,93 +1883,51 @@ struct alignas(16) CorrectJob {
 template <int K>
 __global__ __launch_bounds__(kBlock) void matcorrect_reg(const CorrectJob job) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
     const CU32 verdict = (CU32)job.verdict;
-    while (s < job.nstripes) {
-        const uint32_t h = __builtin_amdgcn_readfirstlane(verdict[s]);
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        const uint32_t h = __builtin_amdgcn_readfirstlane(verdict[it.s]);
         if (h < job.nb) {  // wave-uniform: a scalar branch, not taken on clean data
-            const uint32_t c = w * 64u + lane;
-            const bool live = c < job.cps;
-            const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
-            uint8_t* const base = job.blocks + s * job.sstride + sp.off;
+            bool live;
+            const Span sp = wave_unit(job.walk, it.w, lane, &live);
+            uint8_t* const base = job.blocks + it.s * job.sstride + sp.off;
             u32x4 x[K];
 #pragma unroll
             for (int l = 0; l < K; ++l) {
                 const uint32_t slot = static_cast<uint32_t>(l) == h ? static_cast<uint32_t>(K) : static_cast<uint32_t>(l);
                 x[l] = load_unit(base + slot * job.bstride, live, sp);
             }
-            const CU32 tp = (CU32)job.tabs + size_t(h) * (K * 5);
             Tab t[K];
-#pragma unroll
-            for (int l = 0; l < K; ++l) t[l] = Tab{tp[l * 5], tp[l * 5 + 1], tp[l * 5 + 2], tp[l * 5 + 3], tp[l * 5 + 4]};
+            row_tabs<K>(t, (CU32)job.tabs + size_t(h) * (K * 5));
             Sel sel[4][K];
-#pragma unroll
-            for (int l = 0; l < K; ++l) {
-                sel[0][l] = selectors(x[l].x);
-                sel[1][l] = selectors(x[l].y);
-                sel[2][l] = selectors(x[l].z);
-                sel[3][l] = selectors(x[l].w);
-            }
+            unit_sel<K>(sel, x);
             const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]), gf_dot<K>(t, sel[3])};
-            if (live) {
-                uint8_t* const out = base + h * job.bstride;
-                if (sp.full)
-                    store16_pol<0>(out, y);
-                else
-                    store_tail(out, y, sp.nb);
-            }
-        }
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
+            store_unit(base + h * job.bstride, y, live, sp);
         }
     }
 }
 
 __global__ __launch_bounds__(kBlock) void rows_correct(const CorrectJob job) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t s = gw / job.wps, w = gw - s * job.wps;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
     const CU32 verdict = (CU32)job.verdict;
-    while (s < job.nstripes) {
-        const uint32_t h = __builtin_amdgcn_readfirstlane(verdict[s]);
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        const uint32_t h = __builtin_amdgcn_readfirstlane(verdict[it.s]);
         if (h < job.nb) {  // wave-uniform
-            const uint32_t c = w * 64u + lane;
-            const bool live = c < job.cps;
-            const Span sp = chunk_span<kChunk, true>(c, sz, nfull);
-            uint8_t* const base = job.blocks + s * job.sstride + sp.off;
+            bool live;
+            const Span sp = wave_unit(job.walk, it.w, lane, &live);
+            uint8_t* const base = job.blocks + it.s * job.sstride + sp.off;
             const CU32 tp = (CU32)job.tabs + size_t(h) * job.k * 5u;
             u32x4 y{0u, 0u, 0u, 0u};
             for (uint32_t l = 0; l < job.k; ++l) {
                 const uint32_t slot = l == h ? job.k : l;
                 const u32x4 x = load_unit(base + slot * job.bstride, live, sp);
-                const Tab t[1] = {Tab{tp[l * 5u], tp[l * 5u + 1u], tp[l * 5u + 2u], tp[l * 5u + 3u], tp[l * 5u + 4u]}};
+                const Tab t[1] = {tab_at(tp + l * 5u)};
                 const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
                 y.x ^= gf_dot<1>(t, z[0]);
                 y.y ^= gf_dot<1>(t, z[1]);
                 y.z ^= gf_dot<1>(t, z[2]);
                 y.w ^= gf_dot<1>(t, z[3]);
             }
-            if (live) {
-                uint8_t* const out = base + h * job.bstride;
-                if (sp.full)
-                    store16_pol<0>(out, y);
-                else
-                    store_tail(out, y, sp.nb);
-            }
-        }
-        w += job.gs_w;
-        s += job.gs_s;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++s;
+            store_unit(base + h * job.bstride, y, live, sp);
         }
     }
 }
@@ -2202,7 +2024,7 @@ __global__ __launch_bounds__(kBlock) void matrepair_ragged(const RaggedRepairJob
                         }
                     }
                     Sel sel[4][K];
-                    ragged_sel<K>(sel, x);
+                    unit_sel<K>(sel, x);
                     // the row address advances per lane, as matapply_ragged's does
                     uint8_t* orow = out0 + sp.off;
 #pragma unroll
@@ -2294,7 +2116,7 @@ __global__ __launch_bounds__(kBlock) void matcorrect_ragged(const RaggedCorrectJ
                 for (int l = 0; l < K; ++l)
                     t[l] = Tab{tp[l * 5], tp[l * 5 + 1], tp[l * 5 + 2], tp[l * 5 + 3], tp[l * 5 + 4]};
                 Sel sel[4][K];
-                ragged_sel<K>(sel, x);
+                unit_sel<K>(sel, x);
                 const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]), gf_dot<K>(t, sel[3])};
                 if (live) {
                     uint8_t* const out = base + h * B + sp.off;
@@ -2337,7 +2159,7 @@ __global__ __launch_bounds__(kBlock) void matcorrect_ragged(const RaggedCorrectJ
 // pairs_finish: one lane per list entry; exactly one zero among the first
 // npairs pair bits names (a, b), written into both planes by plain stores.
 //
-// pairs_correct: rows_correct's walk over the list.  A wave reads its entry's
+// pairs_correct: WaveWalk over the list, as pairs_locate.  A wave reads its entry's
 // two verdict words first and touches no block unless they name a pair; then
 // record p (k source slots, 2 x k tables) is applied to the sources by
 // wave-uniform address arithmetic, and slots a and b take two streaming stores
@@ -2370,13 +2192,11 @@ __global__ __launch_bounds__(kBlock) void locate2_finish(const Finish2Job job) {
 }
 
 struct alignas(16) PairsJob {
-    uint64_t sz, bstride, sstride;
-    uint32_t nstripes, cps;
-    uint32_t wps;          // waves per stripe
-    uint32_t gs_w, gs_e;   // grid stride expressed as (waves, entries): stride = gs_e*wps + gs_w
+    Walk walk;               // over list entries: gs_s counts entries
+    uint64_t bstride, sstride;
     uint32_t k, c, nb;
     uint32_t npairs, pw;   // pw = ceil(npairs / 32)
-    uint32_t pad_[2];
+    uint32_t pad_;
     const uint32_t* list;
     uint32_t* pairbits;
     uint32_t* culprit;       // two planes of nstripes words
@@ -2386,24 +2206,19 @@ struct alignas(16) PairsJob {
     uint8_t* blocks;         // slot 0 of stripe 0
 };
 
-__device__ __forceinline__ Tab tab_at(CU32 p) { return Tab{p[0], p[1], p[2], p[3], p[4]}; }
-
 __global__ __launch_bounds__(64) void pairs_locate(const PairsJob job) {
     extern __shared__ u32x4 pairs_syn[];  // c rows of 64 lanes
     const CU32 list = (CU32)job.list;
     const uint32_t count = list[0];
-    uint32_t e = blockIdx.x / job.wps, w = blockIdx.x - e * job.wps;
-    if (e >= count) return;  // (the empty list: one scalar load)
+    WaveWalk it(job.walk, grid_wave<64>());
+    if (it.s >= count) return;  // (the empty list: one scalar load)
     const uint32_t lane = threadIdx.x;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
     const uint32_t k = job.k, c = job.c, rec = 2u + 11u * (c - 2u);
     const CU32 ptabs = (CU32)job.ptabs, recs = (CU32)job.recs;
-    while (e < count) {
-        const uint32_t s = list[size_t(1) + e];
-        const uint32_t ci = w * 64u + lane;
-        const bool live = ci < job.cps;
-        const Span sp = chunk_span<kChunk, true>(ci, sz, nfull);
+    for (; it.s < count; it.next(job.walk)) {
+        const uint32_t e = it.s, s = list[size_t(1) + e];
+        bool live;
+        const Span sp = wave_unit(job.walk, it.w, lane, &live);
         const uint8_t* const base = job.blocks + s * job.sstride + sp.off;
         for (uint32_t i = 0; i < c; ++i) pairs_syn[i * 64u + lane] = load_unit(base + (k + i) * job.bstride, live, sp);
         for (uint32_t j = 0; j < k; ++j) {
@@ -2453,12 +2268,6 @@ __global__ __launch_bounds__(64) void pairs_locate(const PairsJob job) {
                 }
             }
         }
-        w += job.gs_w;
-        e += job.gs_e;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++e;
-        }
     }
 }
 
@@ -2482,28 +2291,24 @@ __global__ __launch_bounds__(kBlock) void pairs_finish(const PairsJob job) {
             --row;
         }
         job.culprit[s] = a;
-        job.culprit[size_t(job.nstripes) + s] = a + 1u + first;
+        job.culprit[size_t(job.walk.nstripes) + s] = a + 1u + first;
     }
 }
 
 __global__ __launch_bounds__(kBlock) void pairs_correct(const PairsJob job) {
     const CU32 list = (CU32)job.list;
     const uint32_t count = list[0];
-    const uint32_t gw = blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint32_t e = gw / job.wps, w = gw - e * job.wps;
-    if (e >= count) return;
+    WaveWalk it(job.walk, grid_wave());
+    if (it.s >= count) return;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t sz = job.sz;
-    const uint32_t nfull = static_cast<uint32_t>(sz / kChunk);
     const uint32_t k = job.k;
     const CU32 verdict = (CU32)job.culprit, recs = (CU32)job.recs;
-    while (e < count) {
-        const uint32_t s = list[size_t(1) + e];
-        const uint32_t a = verdict[s], b = verdict[size_t(job.nstripes) + s];
+    for (; it.s < count; it.next(job.walk)) {
+        const uint32_t s = list[size_t(1) + it.s];
+        const uint32_t a = verdict[s], b = verdict[size_t(job.walk.nstripes) + s];
         if (a < b && b < job.nb) {  // wave-uniform
-            const uint32_t ci = w * 64u + lane;
-            const bool live = ci < job.cps;
-            const Span sp = chunk_span<kChunk, true>(ci, sz, nfull);
+            bool live;
+            const Span sp = wave_unit(job.walk, it.w, lane, &live);
             uint8_t* const base = job.blocks + s * job.sstride + sp.off;
             const uint32_t p = a * job.nb - a * (a + 1u) / 2u + (b - a - 1u);
             const CU32 rp = recs + size_t(p) * (11u * k);
@@ -2521,23 +2326,8 @@ __global__ __launch_bounds__(kBlock) void pairs_correct(const PairsJob job) {
                 yb.z ^= gf_dot<1>(tb, z[2]);
                 yb.w ^= gf_dot<1>(tb, z[3]);
             }
-            if (live) {
-                uint8_t* const oa = base + a * job.bstride;
-                uint8_t* const ob = base + b * job.bstride;
-                if (sp.full) {
-                    store16_pol<0>(oa, ya);
-                    store16_pol<0>(ob, yb);
-                } else {
-                    store_tail(oa, ya, sp.nb);
-                    store_tail(ob, yb, sp.nb);
-                }
-            }
-        }
-        w += job.gs_w;
-        e += job.gs_e;
-        if (w >= job.wps) {
-            w -= job.wps;
-            ++e;
+            store_unit(base + a * job.bstride, ya, live, sp);
+            store_unit(base + b * job.bstride, yb, live, sp);
         }
     }
 }
@@ -5127,23 +4917,24 @@ struct StagedUpload {
     }
 };
 
-// The wave-inside-one-stripe walk of a launch over ns stripes of len bytes,
-// into any job with the six walk fields; returns the grid.
-template <class J>
-uint32_t fill_walk(J& job, uint64_t len, uint64_t ns) {
+// The wave-inside-one-stripe walk (WaveWalk) of a launch over ns stripes of
+// len bytes, by workgroups of wg_waves waves, at most `cap` of them; returns
+// the grid.
+uint32_t fill_walk(Walk& k, uint64_t len, uint64_t ns, uint64_t wg_waves, uint64_t cap) {
     const uint64_t cps = (len + kChunk - 1) / kChunk, wps = (cps + 63) / 64;
-    const uint64_t waves = ns * wps, need = (waves + kBlock / 64 - 1) / (kBlock / 64);
-    const uint64_t cap = unit_grid_cap();
+    const uint64_t waves = ns * wps, need = (waves + wg_waves - 1) / wg_waves;
     const uint32_t grid = static_cast<uint32_t>(need < cap ? need : cap);
-    const uint64_t gstride = uint64_t(grid) * (kBlock / 64);
-    job.sz = len;
-    job.nstripes = static_cast<uint32_t>(ns);
-    job.cps = static_cast<uint32_t>(cps);
-    job.wps = static_cast<uint32_t>(wps);
-    job.gs_s = static_cast<uint32_t>(gstride / wps);
-    job.gs_w = static_cast<uint32_t>(gstride % wps);
+    const uint64_t gstride = uint64_t(grid) * wg_waves;
+    k.sz = len;
+    k.nstripes = static_cast<uint32_t>(ns);
+    k.cps = static_cast<uint32_t>(cps);
+    k.wps = static_cast<uint32_t>(wps);
+    k.gs_s = static_cast<uint32_t>(gstride / wps);
+    k.gs_w = static_cast<uint32_t>(gstride % wps);
+    k.pad_ = 0;
     return grid;
 }
+uint32_t fill_walk(Walk& k, uint64_t len, uint64_t ns) { return fill_walk(k, len, ns, kBlock / 64, unit_grid_cap()); }
 
 // Launches of at most Config::launch_units lanes: blocks longer than that many
 // 16-byte chunks are cut into byte ranges (whole waves of 1 KiB), batches into
@@ -5190,7 +4981,7 @@ hipError_t launch_mixed_k(const MixedSpec& m, hipStream_t stream) {
     job.tables = reinterpret_cast<const uint32_t*>(up.dev());
     // the id pointer advances per stripe group
     e = launch_pieces(m.sz, m.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const uint32_t grid = fill_walk(job, len, ns);
+        const uint32_t grid = fill_walk(job.walk, len, ns);
         job.ids = ids + s0;
         for (int j = 0; j < K; ++j) {
             job.in[j] = m.in[j] + b0 + s0 * m.in_sstride;
@@ -5240,57 +5031,56 @@ void fill_tabs(uint32_t* tab, const VerifySpec& v) {
         for (int j = 0; j < K; ++j) host_tab(&tab[(i * K + j) * 5], v.coef[size_t(i) * v.coef_stride + j]);
 }
 
-const KrNames g_verify_names("matverify_reg");
-
-struct VerifyKr {
-    template <int K, int R>
-    static hipError_t launch(const VerifySpec& v, hipStream_t stream) {
-        VerifyJob<K, R> job;
-        job.sstride = v.sstride;
-        job.words = v.words;
-        job.bit0 = v.bit0;
-        job.pad_ = 0;
-        fill_tabs<K, R>(job.tab, v);
-        const hipError_t e = launch_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-            const uint32_t grid = fill_walk(job, len, ns);
-            job.mismatch = v.mismatch + s0 * v.words;
-            for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
-            for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
-            return launch_job(reinterpret_cast<const void*>(matverify_reg<K, R>), grid, kBlock, 0, stream, job);
-        });
-        if (e == hipSuccess) t_last_kernel = g_verify_names.name[K][R];
-        return e;
-    }
-};
-constexpr KrTable<VerifyKr> g_verify_launch;
-
-// ---- error location dispatch (matlocate_reg) ------------------------------------------
 struct LocateArgs {
     const uint8_t* q;  // (r-1) x k
     uint32_t xbit;
 };
 
-const KrNames g_locate_names("matlocate_reg");
+const KrNames g_verify_names("matverify_reg"), g_locate_names("matlocate_reg");
 
+// matverify_reg<K, R> or matlocate_reg<K, R> (a: the locate call's Q and xbit).
+template <int K, int R, bool LOC>
+hipError_t launch_scrub(const VerifySpec& v, const LocateArgs* a, hipStream_t stream) {
+    ScrubJob<K, R, LOC> job;
+    job.sstride = v.sstride;
+    job.words = v.words;
+    job.bit0 = v.bit0;
+    job.xbit = 0;
+    job.qtab[0] = 0;
+    fill_tabs<K, R>(job.tab, v);
+    if constexpr (LOC) {
+        job.xbit = a->xbit;
+        for (int i = 0; i < (R - 1) * K; ++i) host_tab(&job.qtab[i * 5], a->q[i]);
+    }
+    const void* fn;
+    if constexpr (LOC)
+        fn = reinterpret_cast<const void*>(matlocate_reg<K, R>);
+    else
+        fn = reinterpret_cast<const void*>(matverify_reg<K, R>);
+    const hipError_t e = launch_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+        const uint32_t grid = fill_walk(job.walk, len, ns);
+        job.bits = v.mismatch + s0 * v.words;
+        for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
+        for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
+        return launch_job(fn, grid, kBlock, 0, stream, job);
+    });
+    if (e == hipSuccess) t_last_kernel = (LOC ? g_locate_names : g_verify_names).name[K][R];
+    return e;
+}
+
+struct VerifyKr {
+    template <int K, int R>
+    static hipError_t launch(const VerifySpec& v, hipStream_t stream) {
+        return launch_scrub<K, R, false>(v, nullptr, stream);
+    }
+};
+constexpr KrTable<VerifyKr> g_verify_launch;
+
+// ---- error location dispatch (matlocate_reg) ------------------------------------------
 struct LocateKr {
     template <int K, int R>
     static hipError_t launch(const VerifySpec& v, const LocateArgs& a, hipStream_t stream) {
-        LocateJob<K, R> job;
-        job.sstride = v.sstride;
-        job.words = v.words;
-        job.xbit = a.xbit;
-        job.pad_ = 0;
-        fill_tabs<K, R>(job.tab, v);
-        for (int i = 0; i < (R - 1) * K; ++i) host_tab(&job.qtab[i * 5], a.q[i]);
-        const hipError_t e = launch_pieces(v.sz, v.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-            const uint32_t grid = fill_walk(job, len, ns);
-            job.bits = v.mismatch + s0 * v.words;
-            for (int j = 0; j < K; ++j) job.in[j] = v.in[j] + b0 + s0 * v.sstride;
-            for (int i = 0; i < R; ++i) job.chk[i] = v.chk[i] + b0 + s0 * v.sstride;
-            return launch_job(reinterpret_cast<const void*>(matlocate_reg<K, R>), grid, kBlock, 0, stream, job);
-        });
-        if (e == hipSuccess) t_last_kernel = g_locate_names.name[K][R];
-        return e;
+        return launch_scrub<K, R, true>(v, &a, stream);
     }
 };
 constexpr KrTable<LocateKr, 2> g_locate_launch;
@@ -5322,7 +5112,7 @@ struct RepairKr {
         job.bit0 = g0;
         job.records = u.records;
         const hipError_t e = launch_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-            const uint32_t grid = fill_walk(job, len, ns);
+            const uint32_t grid = fill_walk(job.walk, len, ns);
             job.ids = u.ids + s0;
             for (int j = 0; j < K; ++j) job.in[j] = p.in[j] + b0 + s0 * p.in_sstride;
             for (int i = 0; i < R; ++i) job.out[i] = p.out[g0 + i] + b0 + s0 * p.out_sstride;
@@ -5967,7 +5757,7 @@ hipError_t launch_rows_differ(const DifferSpec& d, hipStream_t stream) {
     job.r = d.r;
     for (uint32_t i = d.r; i < static_cast<uint32_t>(kMaxOut); ++i) job.a[i] = job.b[i] = nullptr;
     const hipError_t e = launch_pieces(d.sz, d.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const uint32_t grid = fill_walk(job, len, ns);
+        const uint32_t grid = fill_walk(job.walk, len, ns);
         job.mismatch = d.mismatch + s0 * d.words;
         for (uint32_t i = 0; i < d.r; ++i) {
             job.a[i] = d.a[i] + b0 + s0 * d.a_sstride;
@@ -6033,7 +5823,7 @@ hipError_t launch_rows_locate(const DifferSpec& d, const uint8_t* a0, const uint
     job.qtab = qtab_dev;
     for (uint32_t i = d.r; i < static_cast<uint32_t>(kMaxOut); ++i) job.a[i] = job.b[i] = nullptr;
     const hipError_t e = launch_pieces(d.sz, d.nstripes, [&](uint64_t b0off, uint64_t len, uint64_t s0, uint64_t ns) {
-        const uint32_t grid = fill_walk(job, len, ns);
+        const uint32_t grid = fill_walk(job.walk, len, ns);
         job.bits = d.mismatch + s0 * d.words;
         job.a0 = a0 + b0off + s0 * d.a_sstride;
         job.b0 = b0 + b0off + s0 * d.b_sstride;
@@ -6085,11 +5875,10 @@ hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream) {
     job.sstride = p.sstride;
     job.k = p.k;
     job.nb = p.nb;
-    job.pad_ = 0;
     job.tabs = reinterpret_cast<const uint32_t*>(up.dev());
     const void* const fn = reg ? kFns[p.k] : reinterpret_cast<const void*>(rows_correct);
     e = launch_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
-        const uint32_t grid = fill_walk(job, len, ns);
+        const uint32_t grid = fill_walk(job.walk, len, ns);
         job.verdict = p.verdict + s0;
         job.blocks = p.blocks + b0 + s0 * p.sstride;
         return launch_job(fn, grid, kBlock, 0, stream, job);
@@ -6159,19 +5948,14 @@ hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
     if ((e = up.copy(dwords * sizeof(uint32_t), stream)) != hipSuccess) return e;
     const uint32_t* const dev = reinterpret_cast<const uint32_t*>(up.dev());
     PairsJob job;
-    const uint64_t cps = (p.sz + kChunk - 1) / kChunk, wps = (cps + 63) / 64;
-    job.sz = p.sz;
     job.bstride = p.bstride;
     job.sstride = p.sstride;
-    job.nstripes = static_cast<uint32_t>(p.nstripes);
-    job.cps = static_cast<uint32_t>(cps);
-    job.wps = static_cast<uint32_t>(wps);
     job.k = k;
     job.c = c;
     job.nb = nb;
     job.npairs = npairs;
     job.pw = pairs_words(nb);
-    job.pad_[0] = job.pad_[1] = 0;
+    job.pad_ = 0;
     job.list = p.list;
     job.pairbits = p.pairbits;
     job.culprit = p.culprit;
@@ -6181,16 +5965,8 @@ hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
     // The host does not know the list's length: fixed grids, sized to fill the
     // device for a fully dirty batch, that walk grid-stride.  An empty list
     // costs every wave one scalar load.
-    const uint64_t waves = p.nstripes * wps;
-    const auto walk = [&](uint64_t per_group, uint64_t groups_per_cu) {
-        const uint64_t need = (waves + per_group - 1) / per_group;
-        const uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * groups_per_cu);
-        const uint64_t grid = need < cap ? need : cap, gstride = grid * per_group;
-        job.gs_e = static_cast<uint32_t>(gstride / wps);
-        job.gs_w = static_cast<uint32_t>(gstride % wps);
-        return static_cast<uint32_t>(grid);
-    };
-    uint32_t grid = walk(1, 32);  // one wave per workgroup, c KiB of LDS each
+    // one wave per workgroup, c KiB of LDS each
+    uint32_t grid = fill_walk(job.walk, p.sz, p.nstripes, 1, hooked_grid_cap(uint64_t(g_num_cu) * 32));
     e = launch_job(reinterpret_cast<const void*>(pairs_locate), grid, 64, size_t(c) * 64 * sizeof(u32x4), stream, job);
     if (e == hipSuccess) {
         const uint64_t need = (p.nstripes + kBlock - 1) / kBlock, cap = hooked_grid_cap(uint64_t(g_num_cu) * 8);
@@ -6199,7 +5975,7 @@ hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
     }
     if (e == hipSuccess && heal) {
         job.recs = dev + off_cor;
-        grid = walk(kBlock / 64, 8);
+        grid = fill_walk(job.walk, p.sz, p.nstripes, kBlock / 64, hooked_grid_cap(uint64_t(g_num_cu) * 8));
         e = launch_job(reinterpret_cast<const void*>(pairs_correct), grid, kBlock, 0, stream, job);
     }
     up.done(stream);
