@@ -787,6 +787,81 @@ int fec_repair_batch_planned(const fec_repair_plan_t* plan,
                              const unsigned* pattern_of, size_t sz, size_t nstripes,
                              void* stream, unsigned flags);
 
+/* Batched parity update: bring the stored blocks of every stripe up to date
+ * after some of its primaries changed, from the changed blocks alone (the
+ * small-write path of a store; fec_encode_batch needs all k primaries).  The
+ * code is linear, so for every stored block b and changed primary j
+ *     block_b(new stripe) = block_b(old stripe) ^ E[b][j] . (old_j ^ new_j)
+ * with E the code's enc_matrix.  A parity node that holds a few parity blocks
+ * and no primary calls this with the delta it received; a node that holds whole
+ * wide stripes reads 1 + r blocks and writes r instead of reading k.
+ *
+ * rows: row i of stripe s, at rows + s*row_stripe_stride + i*row_block_stride,
+ * holds block block_nums[i] of that stripe: num_block_nums distinct numbers
+ * < n (host memory), in any order, 1 <= num_block_nums <= n.  Primaries are
+ * allowed (their row of E is a unit row).  The rows are updated IN PLACE.
+ *
+ * changed: nstripes x nchanged numbers (unsigned, 4 bytes each) in host OR
+ * device memory (on the blocks' device), 1 <= nchanged <= 4: word
+ * [s*nchanged + c] is the number of the primary that input slot c of stripe s
+ * carries, or FEC_UPDATE_NONE.  Input slot c of stripe s is at
+ * base + s*in_stripe_stride + c*in_block_stride, in newb and in oldb alike.
+ * With oldb == NULL newb holds the deltas d = old ^ new themselves; otherwise
+ * the kernel forms d from the two.
+ *
+ * Every slot that is not FEC_UPDATE_NONE contributes E[block_nums[i]][j] . d to
+ * row i.  Slots are independent and their contributions XOR together, so the
+ * same number in two slots is allowed (the two add).  Afterwards each stored
+ * row holds exactly the bytes fec_encode of that block number gives on the
+ * stripe with the new primaries; a stored primary row that names a changed
+ * block holds the new block.  A FEC_UPDATE_NONE slot is not read.  A row whose
+ * coefficients for the stripe's live slots are all zero (this can only be a
+ * primary row) is neither read nor written, and a stripe whose slots are all
+ * FEC_UPDATE_NONE is untouched.  Nothing outside the sz bytes of a row is
+ * written.  The inputs must not overlap the rows: the result is then
+ * unspecified.
+ *
+ * Numbers in HOST memory are checked: one that is neither < k nor
+ * FEC_UPDATE_NONE is FEC_EINVAL, naming the stripe and the slot.  Numbers in
+ * DEVICE memory cannot be seen by the host: such a slot is treated as
+ * FEC_UPDATE_NONE and no error is reported (the rule a device-side pattern_of
+ * follows in fec_repair_batch).
+ *
+ * oldb, newb and rows are device memory on one device, or page-locked host
+ * memory; pageable host memory returns FEC_EINVAL (this call does not stage).
+ * FEC_FLAG_ASYNC and FEC_FLAG_LIBRARY_STREAM as in fec_repair_batch;
+ * FEC_FLAG_ROW_PADDING is accepted and ignored.  The call returns FEC_EINVAL
+ * while the stream is being captured into a graph (its coefficient records are
+ * uploaded, through staging the library owns, when the call is made;
+ * block_nums and a host-side changed may be reused as soon as it returns).
+ *
+ * Checked before any GPU work, in this order, each FEC_EINVAL with a message:
+ * invalid fec_t; NULL newb, rows, block_nums or changed; num_block_nums == 0 or
+ * > n; a block number >= n; a duplicate block number; nchanged == 0 or > 4;
+ * nstripes >= 2^32; a bad number in a HOST-side changed.  Then FEC_ENODEV when
+ * no GPU is visible.  nstripes == 0 or sz == 0 returns FEC_OK.
+ *
+ * Every code runs on matupdate_reg<nchanged, r>: one column of E per changed
+ * block is involved, so the kernel does not depend on k.  A launch takes at
+ * most 8 rows; more run as row groups of 8 over one upload, EACH RE-READING THE
+ * INPUTS (the 40 parity rows of K=20/M=60 are 5 launches).  Nothing
+ * synchronises the stream. */
+#define FEC_UPDATE_NONE 0xFFFFFFFFu /* a slot of `changed` this stripe does not use */
+int fec_update_batch(const fec_t* code,
+                     const gf* oldb, const gf* newb,
+                     size_t in_block_stride, size_t in_stripe_stride,
+                     gf* rows, size_t row_block_stride, size_t row_stripe_stride,
+                     const unsigned* block_nums, size_t num_block_nums,
+                     const unsigned* changed, size_t nchanged,
+                     size_t sz, size_t nstripes, void* stream, unsigned flags);
+
+/* Host only, no GPU: coefs[i] = E[block_nums[i]][changed_block], the
+ * coefficient fec_update_batch multiplies the delta of primary changed_block
+ * by for stored row i.  The same checks on code, block_nums (and coefs) and
+ * the numbers; changed_block >= k is FEC_EINVAL.  FEC_OK / FEC_EINVAL. */
+int fec_update_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums,
+                    unsigned changed_block, gf* coefs);
+
 /* Ragged repair: fec_repair_batch over stripes that each have their own size,
  * in one launch.  The arena arguments are those of fec_encode_batch_ragged,
  * the pattern arguments those of fec_repair_batch.

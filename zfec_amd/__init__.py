@@ -453,6 +453,122 @@ class Encoder(_fec.Encoder):
                             "block nums in [k, m-1] = [%d, %d], but one was %r" % (k, m - 1, x))
         return _ragged_call(self, "encode_batch_ragged", data, sizes, offsets, out, out_offsets, nums, len(nums))
 
+    def update_batch(self, parity, changed, new, old=None, blocknums=None):
+        """Bring the stored blocks of many stripes up to date after some of
+        their primaries changed, from the changed blocks alone, in place
+        (fec_update_batch): the small-write path.  No other primary is read.
+
+        parity: uint8 device tensor [nstripes, r, sz] (any strides with unit
+        stride along sz): row i of a stripe holds block blocknums[i], distinct
+        numbers in [0, m-1] in any order, primaries allowed (default k..m-1).
+        changed: [nstripes] or [nstripes, c] integers, 1 <= c <= 4 -- a list,
+        a numpy array or a torch tensor on the host or on parity's device --
+        the number of the primary each input slot carries, or -1 for "none".
+        new (and old): uint8 tensors [nstripes, sz] or [nstripes, c, sz] on
+        parity's device, not overlapping it.  With old=None new holds the
+        deltas old ^ new themselves.  The same primary in two slots is allowed:
+        the two contributions add.  Host-side numbers are checked; a device-side
+        number that is not in [0, k-1] makes its slot a "none".
+
+        Afterwards every row holds what encode() gives for its block number on
+        the stripe with the new primaries.  Returns parity; the work is
+        enqueued on the current stream."""
+        import numpy as np
+
+        k, m = self.k, self.m
+        is_tensor = type(parity).__module__.startswith("torch") and hasattr(parity, "data_ptr")
+        if not is_tensor or str(parity.dtype) != "torch.uint8" or parity.dim() != 3:
+            raise Error("Precondition violation: parity is required to be a uint8 device tensor [nstripes, r, sz]")
+        ns, r, sz = parity.shape
+        nums = list(range(k, m)) if blocknums is None else list(blocknums)
+        for x in nums:
+            if not isinstance(x, (int, np.integer)) or isinstance(x, bool) or x < 0 or x >= m:
+                raise Error("Precondition violation: update_batch block nums are required to be in [0, m-1] = "
+                            "[0, %d], but one was %r" % (m - 1, x))
+        nums = [int(x) for x in nums]
+        if len(set(nums)) != len(nums):
+            raise Error("Precondition violation: update_batch block nums are required to be distinct, but got %r"
+                        % (nums,))
+        if len(nums) != r or r == 0:
+            raise Error("Precondition violation: parity is required to hold one row per block num: %d rows, %d block "
+                        "nums" % (r, len(nums)))
+        if (sz > 1 and parity.stride(2) != 1) or min(parity.stride(0), parity.stride(1)) < 0:
+            raise Error("Precondition violation: parity rows are required to be contiguous along sz")
+        # changed: host numbers as a numpy table, device numbers as they are
+        ch_dev = None
+        if hasattr(changed, "data_ptr"):
+            if changed.dtype.is_floating_point or str(changed.dtype) == "torch.bool":
+                raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
+                            "[nstripes, c]")
+            if changed.is_cuda:
+                ch_dev = changed
+                shape = tuple(changed.shape)
+            else:
+                changed = changed.numpy()
+        if ch_dev is None:
+            ch = np.asarray(changed)
+            if ch.size and ch.dtype.kind not in "iu":
+                raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
+                            "[nstripes, c]")
+            shape = ch.shape
+        if len(shape) not in (1, 2) or shape[0] != ns:
+            raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
+                        "[nstripes, c] with nstripes = %d, not %r" % (ns, tuple(shape)))
+        c = 1 if len(shape) == 1 else shape[1]
+        if c < 1 or c > 4:
+            raise Error("Precondition violation: update_batch takes between 1 and 4 changed blocks per stripe, not %d"
+                        % c)
+        if ch_dev is None and ch.size and (ch.min() < -1 or ch.max() >= k):
+            bad = ch[(ch < -1) | (ch >= k)].reshape(-1)[0]
+            raise Error("Precondition violation: changed block nums are required to be primaries in [0, k-1] = "
+                        "[0, %d] or -1 (none), but one was %d" % (k - 1, bad))
+        for t, what in ((new, "new"), (old, "old")):
+            if t is None and what == "old":
+                continue
+            ok = type(t).__module__.startswith("torch") and hasattr(t, "data_ptr") and str(t.dtype) == "torch.uint8"
+            if not ok or tuple(t.shape) not in ((ns, c, sz),) + (((ns, sz),) if c == 1 else ()):
+                raise Error("Precondition violation: %s is required to be a uint8 tensor [nstripes, c, sz] = "
+                            "[%d, %d, %d]%s" % (what, ns, c, sz, " or [nstripes, sz]" if c == 1 else ""))
+            if t.device != parity.device:
+                raise Error("Precondition violation: %s is required to be on parity's device" % what)
+        if not parity.is_cuda:
+            raise Error("Precondition violation: parity is required to be a uint8 device tensor [nstripes, r, sz], "
+                        "not a host tensor")
+        if ch_dev is not None and ch_dev.device != parity.device:
+            raise Error("Precondition violation: a device-side changed is required to be on parity's device")
+        if ns and sz:
+            import torch
+
+            new3 = new.unsqueeze(1) if new.dim() == 2 else new
+            old3 = None
+            if old is not None:
+                old3 = old.unsqueeze(1) if old.dim() == 2 else old
+            # one pair of strides serves both inputs
+            if (sz > 1 and new3.stride(2) != 1) or min(new3.stride(0), new3.stride(1)) < 0 or (
+                    old3 is not None and old3.stride() != new3.stride()):
+                new3 = new3.contiguous()
+                old3 = old3.contiguous() if old3 is not None else None
+            if ch_dev is not None:
+                # whatever is not a primary becomes -1 (the bits of FEC_UPDATE_NONE) before the
+                # narrowing, so that an int64 number like 2^32 + j cannot wrap into the primary j
+                wide = ch_dev.to(torch.int64)
+                words = torch.where((wide < 0) | (wide >= k), torch.full_like(wide, -1), wide).to(
+                    torch.int32).contiguous()
+                ch_ptr = words.data_ptr()
+            else:
+                words = np.ascontiguousarray(ch.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+                ch_ptr = words.ctypes.data
+            from . import capi
+
+            # `words` need only outlive the call: host numbers are copied into the
+            # library's staging, device numbers are read by work of this stream
+            with torch.cuda.device(parity.device), _as_error():
+                _capi_code(self).update_batch(old3.data_ptr() if old3 is not None else 0, new3.data_ptr(),
+                                              new3.stride(1), new3.stride(0), parity.data_ptr(), parity.stride(1),
+                                              parity.stride(0), nums, ch_ptr, c, sz, ns,
+                                              stream=_stream_handle(parity.device), flags=capi.FEC_FLAG_ASYNC)
+        return parity
+
     def _encode_device(self, inblocks, desired):
         import torch
 

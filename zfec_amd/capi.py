@@ -82,12 +82,15 @@ SYMBOLS = [
     ("fec_repair_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _UP, _SZ, _SZ, _P, _SZ,
                                                _P, _U]),
     ("fec_correct_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
+    ("fec_update_batch", ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _UP, _SZ, _P, _SZ, _SZ, _SZ, _P, _U]),
+    ("fec_update_rows", ctypes.c_int, [_P, _UP, _SZ, _U, _P]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_LOCATE_NONE = 0xFFFFFFFC  # fec_locate2_batch: the second word of a verdict that is no pair
 FEC_LOCATE_UNFIT = 0xFFFFFFFB  # fec_locate_batch_ragged: a device-side descriptor that does not fit the arena
 LOCATE_UNFIT = -5  # the same as the int32 the Python methods return
 FEC_REPAIR_NONE = 0xFFFFFFFF  # a target slot its pattern does not use
+FEC_UPDATE_NONE = 0xFFFFFFFF  # fec_update_batch: a slot of `changed` its stripe does not use
 
 JIT_OFF, JIT_AUTO, JIT_FORCE = 0, 1, 2
 FEC_JOB_ENCODE, FEC_JOB_DECODE = 0, 1
@@ -344,6 +347,18 @@ class Code(object):
         if st:
             check(st)
 
+    def update_batch(self, oldb, newb, ibs, iss, rows, rbs, rss, block_nums, changed_ptr, nchanged, sz, nstripes,
+                     stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_update_batch: `oldb` is 0 when `newb` holds the deltas;
+        `changed_ptr` is the address of nstripes * nchanged uint32 primary
+        numbers (FEC_UPDATE_NONE for an unused slot) in host or device memory,
+        which the caller keeps alive until the call returns."""
+        st = lib().fec_update_batch(self.ptr, oldb or None, newb or None, ibs, iss, rows or None, rbs, rss,
+                                    _nums(block_nums), len(block_nums), changed_ptr or None, nchanged, sz, nstripes,
+                                    stream or None, flags)
+        if st:
+            check(st)
+
     def repair_plan(self, present, targets, device=None):
         """fec_repair_plan_new: the patterns of repair_batch (`present` [P, k],
         `targets` [P, t], -1 for FEC_REPAIR_NONE) resolved once into a
@@ -585,6 +600,15 @@ def repair_rows(code, present, targets):
     rows = (ctypes.c_ubyte * max(1, len(tg) * code.k))()
     check(lib().fec_repair_rows(code.ptr, uint_array(present), uint_array(tg), len(tg), ctypes.cast(rows, _P)))
     return bytes(rows)[:len(tg) * code.k]
+
+
+def update_rows(code, block_nums, changed_block):
+    """fec_update_rows: the len(block_nums) coefficients E[block_nums[i]][changed_block]
+    fec_update_batch multiplies the delta of primary `changed_block` by."""
+    nums = list(block_nums)
+    coefs = (ctypes.c_ubyte * max(1, len(nums)))()
+    check(lib().fec_update_rows(code.ptr, uint_array(nums), len(nums), changed_block, ctypes.cast(coefs, _P)))
+    return bytes(coefs[: len(nums)])
 
 
 class BatchJob(ctypes.Structure):

@@ -461,15 +461,15 @@ struct BatchBuf {
 // memory as it is, page-locked host memory as the device maps it), the device
 // -- current while `guard` lives -- its per-thread context and the stream.
 struct BatchMem {
-    const gf* z[2] = {nullptr, nullptr};
-    int bdev[2] = {-1, -1};  // each buffer's device, -1: host memory
+    const gf* z[3] = {nullptr, nullptr, nullptr};
+    int bdev[3] = {-1, -1, -1};  // each buffer's device, -1: host memory
     int dev = -1;
     DevCtx* d = nullptr;
     hipStream_t st = nullptr;
     std::optional<DeviceGuard> guard;
 };
 
-// Resolves the buffers (at most two) of the call `fn`: one pointer query per
+// Resolves the buffers (at most three) of the call `fn`: one pointer query per
 // buffer, a second pair for a page-locked one.  Pageable host memory is
 // refused -- except with fn == nullptr (fec_encode_batch / fec_decode_batch,
 // which stage it): its z stays null.  `side` (may be null) names a further
@@ -485,9 +485,12 @@ int resolve_batch(BatchMem& m, const char* fn, const BatchBuf* bufs, int nbufs, 
             return set_status(FEC_EINVAL, "%s takes device or page-locked host memory: %s is pageable host memory, "
                                           "which this call does not stage", fn, bufs[i].label);
     }
-    if (m.bdev[0] >= 0 && m.bdev[1] >= 0 && m.bdev[0] != m.bdev[1])
-        return set_status(FEC_EINVAL, "batched entry points take memory on one device");
-    m.dev = m.bdev[0] >= 0 ? m.bdev[0] : m.bdev[1];
+    for (int i = 0; i < nbufs; ++i) {
+        if (m.bdev[i] < 0) continue;
+        if (m.dev >= 0 && m.dev != m.bdev[i])
+            return set_status(FEC_EINVAL, "batched entry points take memory on one device");
+        m.dev = m.bdev[i];
+    }
     if (m.dev >= 0 && side_dev >= 0 && side_dev != m.dev)
         return set_status(FEC_EINVAL, "%s lives on device %d, the blocks on device %d", side, side_dev, m.dev);
     if (m.dev < 0) m.dev = side_dev;
@@ -2998,6 +3001,116 @@ FEC_API int fec_repair_batch(const fec_t* code, const gf* src, size_t src_block_
     return guarded([&] {
         return run_repair(code, src, src_block_stride, src_stripe_stride, dst, dst_block_stride, dst_stripe_stride,
                           present, targets, ntargets, npatterns, pattern_of, idev, sz, nstripes, stream, flags);
+    });
+}
+
+// ---- batched parity update: changed primaries into the stored rows -----------------------
+namespace {
+// The checks fec_update_batch and fec_update_rows share, in the documented
+// order: the code, the pointers (`what` names the first null one, or is null),
+// then the stored rows' numbers -- their count, each one's range, duplicates.
+int check_update_rows(const fec_t* code, const char* null_what, const unsigned* block_nums, size_t num) {
+    if (!valid_code(code)) return set_status(FEC_EINVAL, "invalid fec_t");
+    if (null_what) return set_status(FEC_EINVAL, "%s is NULL", null_what);
+    if (num == 0 || num > code->n)
+        return set_status(FEC_EINVAL, "num_block_nums is %zu: a call updates between 1 and n = %u stored rows", num,
+                          unsigned(code->n));
+    for (size_t i = 0; i < num; ++i)
+        if (block_nums[i] >= code->n)
+            return set_status(FEC_EINVAL, "block number %u out of range (n = %u)", block_nums[i], unsigned(code->n));
+    unsigned char seen[256] = {};
+    for (size_t i = 0; i < num; ++i) {
+        if (seen[block_nums[i]]) return set_status(FEC_EINVAL, "duplicate block number %u", block_nums[i]);
+        seen[block_nums[i]] = 1;
+    }
+    return FEC_OK;
+}
+
+int run_update(const fec_t* code, const gf* oldb, const gf* newb, size_t ibs, size_t iss, gf* rows, size_t rbs,
+               size_t rss, const unsigned* block_nums, size_t nrows, const unsigned* changed, int cdev, size_t nc,
+               size_t sz, size_t nstripes, void* stream, unsigned flags) {
+    const unsigned k = code->k;
+    // device memory on one device, or page-locked host memory (the rows updated in place);
+    // the records are uploaded per call, so the call cannot be captured
+    const size_t in_extent = (nstripes - 1) * iss + (nc - 1) * ibs + sz;
+    const BatchBuf bufs[3] = {{newb, in_extent, "newb"},
+                              {rows, (nstripes - 1) * rss + (nrows - 1) * rbs + sz, "rows"},
+                              {oldb, in_extent, "oldb"}};
+    BatchMem mem;
+    if (resolve_batch(mem, "fec_update_batch", bufs, oldb ? 3 : 2, "changed", cdev, stream, flags, kCaptureTables))
+        return t_status;
+    hipStream_t st = mem.st;
+    thread_local std::vector<uint8_t> coefs;
+    coefs.resize(size_t(k) * nrows);
+    for (unsigned j = 0; j < k; ++j)
+        for (size_t i = 0; i < nrows; ++i) coefs[j * nrows + i] = code->enc_matrix[size_t(block_nums[i]) * k + j];
+    uint8_t* out[kUpdateMaxRows];
+    for (size_t i = 0; i < nrows; ++i) out[i] = const_cast<gf*>(mem.z[1]) + i * rbs;
+    UpdateSpec u;
+    u.k = k;
+    u.nrows = static_cast<uint32_t>(nrows);
+    u.c = static_cast<uint32_t>(nc);
+    u.coefs = coefs.data();
+    u.changed_host = cdev < 0 ? changed : nullptr;
+    u.changed_dev = cdev < 0 ? nullptr : changed;
+    u.oldb = oldb ? mem.z[2] : nullptr;
+    u.newb = mem.z[0];
+    u.in_bstride = ibs;
+    u.in_sstride = iss;
+    u.rows = out;
+    u.row_sstride = rss;
+    u.sz = sz;
+    u.nstripes = nstripes;
+    ++t_launches;
+    hipError_t e = launch_update(u, st);
+    if (e != hipSuccess) return hip_fail(e, "launch_update");
+    if (!(flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_update_rows(const fec_t* code, const unsigned* block_nums, size_t num_block_nums,
+                            unsigned changed_block, gf* coefs) {
+    if (check_update_rows(code, !block_nums ? "block_nums" : !coefs ? "coefs" : nullptr, block_nums, num_block_nums))
+        return t_status;
+    if (changed_block >= code->k)
+        return set_status(FEC_EINVAL, "changed block %u is not a primary (k = %u)", changed_block, unsigned(code->k));
+    for (size_t i = 0; i < num_block_nums; ++i)
+        coefs[i] = code->enc_matrix[size_t(block_nums[i]) * code->k + changed_block];
+    return set_status(FEC_OK);
+}
+
+FEC_API int fec_update_batch(const fec_t* code, const gf* oldb, const gf* newb, size_t in_block_stride,
+                             size_t in_stripe_stride, gf* rows, size_t row_block_stride, size_t row_stripe_stride,
+                             const unsigned* block_nums, size_t num_block_nums, const unsigned* changed,
+                             size_t nchanged, size_t sz, size_t nstripes, void* stream, unsigned flags) {
+    // every check that needs no GPU comes first
+    static_assert(kUpdateMaxRows >= 256, "a call may name every block of the widest code");
+    if (check_update_rows(code,
+                          !newb ? "newb" : !rows ? "rows" : !block_nums ? "block_nums" : !changed ? "changed" : nullptr,
+                          block_nums, num_block_nums))
+        return t_status;
+    if (nchanged == 0 || nchanged > kUpdateMaxSlots)
+        return set_status(FEC_EINVAL, "nchanged is %zu: a stripe carries between 1 and %u changed blocks", nchanged,
+                          unsigned(kUpdateMaxSlots));
+    if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
+    const int ngpu = gpu_available();
+    const int cdev = ngpu ? pointer_device(changed) : -1;
+    if (cdev < 0)  // numbers in device memory cannot be checked: the kernel takes a bad one for FEC_UPDATE_NONE
+        for (size_t s = 0; s < nstripes; ++s)
+            for (size_t c = 0; c < nchanged; ++c) {
+                const unsigned j = changed[s * nchanged + c];
+                if (j != FEC_UPDATE_NONE && j >= code->k)
+                    return set_status(FEC_EINVAL, "stripe %zu, slot %zu: changed block %u is neither a primary "
+                                                  "(k = %u) nor FEC_UPDATE_NONE", s, c, j, unsigned(code->k));
+            }
+    if (!ngpu) return no_gpu();
+    if (sz == 0 || nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        return run_update(code, oldb, newb, in_block_stride, in_stripe_stride, rows, row_block_stride,
+                          row_stripe_stride, block_nums, num_block_nums, changed, cdev, nchanged, sz, nstripes, stream,
+                          flags);
     });
 }
 

@@ -51,6 +51,10 @@
 //   matrepair_mixed<K, R> matapply_mixed with R rows per pattern instead of K, each
 //                       row stored only where its pattern's live-row mask says
 //                       so (fec_repair_batch).
+//   matupdate_reg<C, R> matrepair_mixed's shape with one record per primary: the C
+//                       changed blocks of a stripe (deltas, or old and new
+//                       bytes) XOR-ed into R stored rows in place, for any k
+//                       (fec_update_batch).  Blocks end with the byte tail.
 //   matrepair_ragged<K, R>, matcorrect_ragged<K>
 //                       ragged_walk around matrepair_mixed's per-stripe record (a
 //                       size AND a pattern per stripe) and around matcorrect_reg's
@@ -359,11 +363,14 @@ struct WaveWalk {
 };
 
 // This lane's chunk of wave w of a stripe: chunk w*64 + lane with chunk_span's
-// overlapped last chunk; *live: the stripe has that chunk.
+// overlapped last chunk; *live: the stripe has that chunk.  OVERLAP = false
+// ends the block with the byte tail instead: a kernel that XORs into its
+// output (matupdate_reg) must touch every byte exactly once.
+template <bool OVERLAP = true>
 __device__ __forceinline__ Span wave_unit(const Walk& k, uint32_t w, uint32_t lane, bool* live) {
     const uint32_t c = w * 64u + lane;
     *live = c < k.cps;
-    return chunk_span<kChunk, true>(c, k.sz, static_cast<uint32_t>(k.sz / kChunk));
+    return chunk_span<kChunk, OVERLAP>(c, k.sz, static_cast<uint32_t>(k.sz / kChunk));
 }
 
 // ---- one unit: loads, selectors, tables, store (dense and ragged walks alike) ----
@@ -1458,6 +1465,112 @@ __global__ __launch_bounds__(kBlock) void matrepair_mixed(const RepairJob<K, R> 
                     const u32x4 y{gf_dot<K>(t, sel[0]), gf_dot<K>(t, sel[1]), gf_dot<K>(t, sel[2]),
                                   gf_dot<K>(t, sel[3])};
                     store_unit(job_at<AL>(job)->out[r] + ob, y, live, sp);
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// matupdate_reg<C, R>: the parity update of changed primaries
+// (fec_update_batch): every stripe carries up to C input slots, each the delta
+// (or the old and the new bytes) of one primary whose number is the stripe's
+// own, and R stored rows are brought up to date in place:
+//   row_i ^= sum over the live slots c of E[block_nums[i]][j_c] * d_c.
+// Only one column of E per slot is involved, so the kernel does not depend on
+// the code's k.  It has matrepair_mixed's shape with one "pattern" per
+// primary: record j in device memory holds the tables of E[block_nums[i]][j]
+// for ALL the call's rows (a call with more than 8 rows is several launches
+// over one upload), one Tab per row, then the live-row mask, one dword per 32
+// rows: bit i is set when the coefficient is not zero.  Records are padded to
+// 16 bytes.  A launch takes rows [g0, g0 + R), g0 a multiple of 8: tab_off is
+// its first row's dword offset in a record, mask_off the dword with its mask
+// bits and bit0 its first bit there.
+//
+// The stripe's C numbers are read through a constant-address-space pointer and
+// readfirstlane: scalar loads, wave-uniform, and every branch on them is a
+// scalar branch.  A slot whose number is not < k (FEC_UPDATE_NONE, or a
+// device-side number out of range) loads nothing and contributes x = 0, so
+// its table pointer only has to be valid (record 0).  The row mask is the OR
+// of the live slots' masks; a row whose bit is clear is neither read nor
+// written, and a stripe with no live slot is left alone.  The loads of the
+// live rows are issued before the first of them is used; each row's tables
+// are read where they are used (the pin on the record pointers, job_at for
+// the row pointer), as in matrepair_mixed.
+//
+// This is the one register kernel that XORs into its output, so a block ends
+// with the byte tail (wave_unit<false>), never with the overlapped last chunk:
+// two lanes storing the same bytes would apply the delta twice, or race.
+// ---------------------------------------------------------------------------
+template <int C, int R>
+struct alignas(16) UpdateJob {
+    Walk walk;
+    uint64_t in_sstride, row_sstride;
+    uint32_t k;           // records (one per primary)
+    uint32_t rec_dwords;  // dwords per record
+    uint32_t tab_off;     // dword offset in a record of this launch's first row
+    uint32_t mask_off;    // dword offset in a record of the mask dword of this launch's rows
+    uint32_t bit0;        // bit in that dword of this launch's first row
+    uint32_t has_old;     // 0: nw holds the deltas
+    const uint32_t* records;  // k x rec_dwords
+    const uint32_t* changed;  // nstripes x C primary numbers
+    const uint8_t* nw[C];
+    const uint8_t* od[C];
+    uint8_t* row[R];
+};
+
+template <int C, int R>
+__global__ __launch_bounds__(kBlock) void matupdate_reg(const UpdateJob<C, R> job) {
+    constexpr bool AL = reg_argload(C, R);  // each row's tables are read where they are used
+    const uint32_t lane = threadIdx.x & 63u;
+    const CU32 ch = (CU32)job.changed;
+    for (WaveWalk it(job.walk, grid_wave()); it.s < job.walk.nstripes; it.next(job.walk)) {
+        const uint32_t s = it.s;
+        bool live;
+        const Span sp = wave_unit<false>(job.walk, it.w, lane, &live);
+        const uint64_t ib = s * job.in_sstride + sp.off;
+        u32x4 xn[C], xo[C];
+        CU32 tp[C];
+        uint32_t mask = 0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            xn[c] = xo[c] = u32x4{0u, 0u, 0u, 0u};
+            tp[c] = (CU32)job.records + job.tab_off;
+            const uint32_t j = __builtin_amdgcn_readfirstlane(ch[size_t(s) * C + c]);
+            if (j < job.k) {  // wave-uniform: a scalar branch
+                const CU32 rp = (CU32)job.records + size_t(j) * job.rec_dwords;
+                mask |= __builtin_amdgcn_readfirstlane(rp[job.mask_off]);
+                tp[c] = rp + job.tab_off;
+                xn[c] = load_unit(job.nw[c] + ib, live, sp);
+                if (job.has_old) xo[c] = load_unit(job.od[c] + ib, live, sp);
+            }
+        }
+        mask = (mask >> job.bit0) & ((1u << R) - 1u);
+        if (mask) {
+            const uint64_t ob = s * job.row_sstride + sp.off;
+            u32x4 y[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                y[r] = u32x4{0u, 0u, 0u, 0u};
+                if ((mask >> r) & 1u) y[r] = load_unit(job_at<AL>(job)->row[r] + ob, live, sp);
+            }
+            u32x4 x[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) x[c] = xn[c] ^ xo[c];
+            Sel sel[4][C];
+            unit_sel<C>(sel, x);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if ((mask >> r) & 1u) {
+                    Tab t[C];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        if constexpr (AL) asm volatile("" : "+s"(tp[c]));
+                        t[c] = tab_at(tp[c] + r * 5);
+                    }
+                    const u32x4 v{y[r].x ^ gf_dot<C>(t, sel[0]), y[r].y ^ gf_dot<C>(t, sel[1]),
+                                  y[r].z ^ gf_dot<C>(t, sel[2]), y[r].w ^ gf_dot<C>(t, sel[3])};
+                    store_unit(job_at<AL>(job)->row[r] + ob, v, live, sp);
                 }
             }
         }
@@ -5181,6 +5294,80 @@ hipError_t launch_repair_all(const RepairSpec& p, hipStream_t stream) {
     return e;
 }
 
+// ---- matupdate_reg dispatch ----------------------------------------------------------
+// One upload through a MixedRing slot (the k records, then any host-side
+// numbers) serves every row group of a call.
+struct UpdateUpload {
+    const uint32_t* records;  // device
+    const uint32_t* changed;  // device
+    uint32_t rec_dwords, mask_off;
+};
+
+constexpr uint32_t update_rec_dwords(uint32_t nrows) { return (nrows * 5 + (nrows + 31) / 32 + 3) / 4 * 4; }
+
+const KrNames g_update_names("matupdate_reg");
+
+// Rows [g0, g0 + R) of every stripe; K is the number of input slots.
+struct UpdateKr {
+    template <int K, int R>
+    static hipError_t launch(const UpdateSpec& p, const UpdateUpload& u, uint32_t g0, hipStream_t stream) {
+        UpdateJob<K, R> job;
+        job.in_sstride = p.in_sstride;
+        job.row_sstride = p.row_sstride;
+        job.k = p.k;
+        job.rec_dwords = u.rec_dwords;
+        job.tab_off = g0 * 5;
+        job.mask_off = u.mask_off + g0 / 32;
+        job.bit0 = g0 % 32;
+        job.has_old = p.oldb != nullptr;
+        job.records = u.records;
+        const hipError_t e = launch_pieces(p.sz, p.nstripes, [&](uint64_t b0, uint64_t len, uint64_t s0, uint64_t ns) {
+            const uint32_t grid = fill_walk(job.walk, len, ns);
+            job.changed = u.changed + s0 * K;
+            for (int c = 0; c < K; ++c) {
+                const uint64_t off = b0 + s0 * p.in_sstride + c * p.in_bstride;
+                job.nw[c] = p.newb + off;
+                job.od[c] = p.oldb ? p.oldb + off : nullptr;
+            }
+            for (int i = 0; i < R; ++i) job.row[i] = p.rows[g0 + i] + b0 + s0 * p.row_sstride;
+            return launch_job(reinterpret_cast<const void*>(matupdate_reg<K, R>), grid, kBlock, 0, stream, job);
+        });
+        if (e == hipSuccess) t_last_kernel = g_update_names.name[K][R];
+        return e;
+    }
+};
+constexpr KrTable<UpdateKr> g_update_launch;
+
+hipError_t launch_update_all(const UpdateSpec& p, hipStream_t stream) {
+    const uint32_t rec_dwords = update_rec_dwords(p.nrows), mask_off = p.nrows * 5;
+    const size_t tab_bytes = (size_t(p.k) * rec_dwords * 4 + 255) / 256 * 256;
+    const size_t ch_bytes = p.changed_host ? size_t(p.nstripes) * p.c * 4 : 0;
+    StagedUpload up;
+    hipError_t e = up.acquire(tab_bytes + ch_bytes);
+    if (e != hipSuccess) return e;
+    uint32_t* ht = reinterpret_cast<uint32_t*>(up.host());
+    for (uint32_t j = 0; j < p.k; ++j) {
+        uint32_t* rec = ht + size_t(j) * rec_dwords;
+        for (uint32_t i = mask_off; i < rec_dwords; ++i) rec[i] = 0;
+        for (uint32_t i = 0; i < p.nrows; ++i) {
+            const uint8_t coef = p.coefs[size_t(j) * p.nrows + i];
+            host_tab(rec + i * 5, coef);
+            if (coef) rec[mask_off + i / 32] |= 1u << (i % 32);
+        }
+    }
+    if (ch_bytes) std::memcpy(up.host() + tab_bytes, p.changed_host, ch_bytes);
+    if ((e = up.copy(tab_bytes + ch_bytes, stream)) != hipSuccess) return e;
+    UpdateUpload u;
+    u.records = reinterpret_cast<const uint32_t*>(up.dev());
+    u.changed = p.changed_host ? reinterpret_cast<const uint32_t*>(up.dev() + tab_bytes) : p.changed_dev;
+    u.rec_dwords = rec_dwords;
+    u.mask_off = mask_off;
+    for (uint32_t g0 = 0; g0 < p.nrows && e == hipSuccess; g0 += kRegR)
+        e = g_update_launch(p.c, std::min<uint32_t>(kRegR, p.nrows - g0))(p, u, g0, stream);
+    up.done(stream);
+    return e;
+}
+
 // ---- matapply_ragged dispatch ---------------------------------------------------------
 // The grid of matapply_ragged: a wave per unit where a unit moves 10 KiB or more
 // (k + r >= 10: the K=3/M=10 encode), else the fewest units per wave that do --
@@ -5717,6 +5904,18 @@ hipError_t launch_repair(const RepairSpec& p, hipStream_t stream) {
     reset_signal();
     if (p.k > kMixedMaxK) return launch_repair_wide(p, stream);
     return launch_repair_all(p, stream);
+}
+
+hipError_t launch_update(const UpdateSpec& p, hipStream_t stream) {
+    static_assert(kUpdateMaxSlots == uint32_t(kRegK), "one matupdate_reg<C, R> per slot count");
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (p.k < 1 || p.nrows < 1 || p.nrows > kUpdateMaxRows || p.c < 1 || p.c > kUpdateMaxSlots || !p.coefs ||
+        (!p.changed_host && !p.changed_dev) || !p.newb || !p.rows || p.sz == 0 || p.nstripes == 0 ||
+        p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    return launch_update_all(p, stream);
 }
 
 hipError_t launch_verify(const VerifySpec& v, hipStream_t stream) {

@@ -112,6 +112,33 @@ struct RepairSpec {
 };
 hipError_t launch_repair(const RepairSpec& p, hipStream_t stream);
 
+// The parity update of changed primaries (matupdate_reg<C, R>, any k): stripe s
+// carries c input slots, slot i the delta of primary changed[s * c + i] (or its
+// old and new bytes: oldb non-null), and every stored row i gets
+// coefs[j * nrows + i] * delta XOR-ed in, in place; coefs column-major by
+// primary: coefs[j * nrows + i] = E[block_nums[i]][j].  A slot whose number is
+// not < k is not read; a row whose coefficients for the stripe's live slots are
+// all zero is neither read nor written.  More than 8 rows run as launches of 8
+// over one upload, each re-reading the inputs.  The numbers are nstripes x c
+// uint32 in host memory (changed_host: uploaded with the records) or in device
+// memory (changed_dev: read in place).  Staging and graph capture as
+// launch_mixed.
+constexpr uint32_t kUpdateMaxSlots = 4;
+constexpr uint32_t kUpdateMaxRows = 256;
+struct UpdateSpec {
+    uint32_t k, nrows, c;
+    const uint8_t* coefs;  // k x nrows coefficients (host memory)
+    const uint32_t* changed_host;
+    const uint32_t* changed_dev;
+    const uint8_t* oldb;  // slot 0 of stripe 0, or null: newb holds the deltas
+    const uint8_t* newb;
+    uint64_t in_bstride, in_sstride;
+    uint8_t* const* rows;  // nrows row bases (stripe 0), kernel-visible addresses
+    uint64_t row_sstride;
+    uint64_t sz, nstripes;
+};
+hipError_t launch_update(const UpdateSpec& p, hipStream_t stream);
+
 // The same two calls for wider codes (4 < k <= kMaxIn, sz >= 2048,
 // generic_mode() == 2): launch_mixed and launch_repair build one record per
 // pattern (below) into the same staging slot and make ONE launch of the mix
