@@ -70,23 +70,28 @@ tsan: build/thread/driver
 	TSAN_OPTIONS="halt_on_error=0 second_deadlock_stack=1" ./build/thread/driver
 
 # The validation paths of the ragged scrub calls (fec_verify_batch_ragged,
-# fec_locate_batch_ragged) and of fec_repair_batch_ragged and
-# fec_correct_batch_ragged under AddressSanitizer and
-# UndefinedBehaviorSanitizer: stand-alone programs,
-# tests/c/ragged_scrub_validate.cpp and tests/c/ragged_repair_validate.cpp, each
-# over the same host objects; no GPU needed.
+# fec_locate_batch_ragged), of fec_repair_batch_ragged and
+# fec_correct_batch_ragged, and of fec_update_batch_ragged under
+# AddressSanitizer and UndefinedBehaviorSanitizer: stand-alone programs,
+# tests/c/ragged_scrub_validate.cpp, tests/c/ragged_repair_validate.cpp and
+# tests/c/ragged_update_validate.cpp, each over the same host objects; no GPU
+# needed.
+# The device code is compiled as the library's is (-O3): the sanitizers look at
+# the host code, and the register kernels' SGPR pins do not compile below that.
 VALSRC := $(filter-out tests/c/sanitize_driver.cpp,$(SANSRC))
 
-build/scrub/validate build/repair/validate: build/%/validate: $(VALSRC) tests/c/ragged_%_validate.cpp $(SRC)/*.hpp \
-                                            include/zfec_hip.h
+build/scrub/validate build/update/validate build/repair/validate: build/%/validate: $(VALSRC) \
+                                            tests/c/ragged_%_validate.cpp $(SRC)/*.hpp include/zfec_hip.h
 	mkdir -p build/$*
 	set -e; for f in $(VALSRC) tests/c/ragged_$*_validate.cpp; do \
-	  $(HIPCC) $(SANFLAGS) -Xarch_host -fsanitize=address,undefined -c $$f -o build/$*/$$(basename $$f).o; done
+	  $(HIPCC) $(SANFLAGS) -Xarch_device -O3 -Xarch_host -fsanitize=address,undefined -c $$f \
+	    -o build/$*/$$(basename $$f).o; done
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -fno-gpu-sanitize -o $@ build/$*/*.o -ldl -lpthread
 
 asan-scrub: build/scrub/validate
+asan-update: build/update/validate
 asan-repair: build/repair/validate
-asan-scrub asan-repair:
+asan-scrub asan-update asan-repair:
 	ASAN_OPTIONS=detect_leaks=0 ./$<
 
 # The no-GPU Python tests of the C-ABI (tests/test_cpu_surface.py: validation,
@@ -109,4 +114,4 @@ clean:
 	rm -f $(SRC)/*.o $(LIB) $(PYEXT)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle ref clean asan tsan asan-py asan-scrub asan-repair
+.PHONY: all oracle ref clean asan tsan asan-py asan-scrub asan-update asan-repair

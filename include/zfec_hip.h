@@ -923,6 +923,76 @@ int fec_repair_batch_ragged(const fec_t* code,
                             size_t npatterns, const unsigned* pattern_of,
                             size_t nstripes, void* stream, unsigned flags);
 
+/* Ragged parity update: fec_update_batch over stripes that each have their own
+ * size, in one launch.  The arithmetic is fec_update_batch's, the layout
+ * fec_repair_batch_ragged's.
+ *
+ * Input slot c of stripe s starts at newb + in_offsets[s] + c*B, with B =
+ * in_block_stride, or sizes[s] when the stride is 0, and at the same offset in
+ * oldb; with oldb == NULL newb holds the deltas old ^ new themselves.  Row i of
+ * stripe s starts at rows + row_offsets[s] + i*B', B' formed the same way from
+ * row_block_stride, and holds block block_nums[i]: num_block_nums distinct
+ * numbers < n (host memory), in any order, primaries allowed.  Offsets are
+ * arbitrary bytes.  A zero-size stripe is neither read nor written.
+ *
+ * changed: nstripes x nchanged numbers (unsigned, 4 bytes each), 1 <= nchanged
+ * <= 4: word [s*nchanged + c] is the number of the primary input slot c of
+ * stripe s carries, or FEC_UPDATE_NONE.  Every live slot contributes
+ * E[block_nums[i]][j] . d to row i, IN PLACE; the same number in two slots
+ * contributes twice.  A FEC_UPDATE_NONE slot is not read.  A row whose
+ * coefficients for the stripe's live slots are all zero is neither read nor
+ * written, and a stripe with no live slot is untouched.  The bytes are those of
+ * fec_update_batch called once per stripe with nstripes = 1 and sz = sizes[s].
+ *
+ * sizes, in_offsets and row_offsets are all in host memory or all in device
+ * memory on the blocks' device (a mix is FEC_EINVAL); changed is independently
+ * host or device memory, as pattern_of is in fec_repair_batch_ragged.  Host
+ * arrays are copied when the call is made; device arrays are read where they
+ * are, in stream order.  NOTHING synchronises the stream, for any code.
+ *
+ * A stripe with sizes[s] > 0 FITS when offset + (slots - 1)*B + sizes[s] <=
+ * bytes holds on both sides, evaluated without wrapping, slots being nchanged
+ * for the inputs (oldb and newb are two arenas of in_bytes each) and
+ * num_block_nums for the rows: the place of a FEC_UPDATE_NONE slot must exist
+ * although it is not read, the rule FEC_REPAIR_NONE rows follow.  With host
+ * descriptor arrays a stripe that does not fit is FEC_EINVAL, the message
+ * naming the stripe and the side (the inputs / the rows).  A host-side number
+ * that is neither < k nor FEC_UPDATE_NONE is FEC_EINVAL, naming the stripe and
+ * the slot.  With device arrays the kernel makes both tests: a stripe that does
+ * not fit is neither read nor written, a bad device-side number makes its slot
+ * a FEC_UPDATE_NONE, and no error is reported.
+ *
+ * Checked before any GPU work, in this order, each FEC_EINVAL with a message
+ * naming the call: fec_update_batch's checks in its order (invalid fec_t; NULL
+ * newb, rows, block_nums or changed; num_block_nums == 0 or > n; a block number
+ * >= n; a duplicate block number; nchanged == 0 or > 4); a NULL sizes,
+ * in_offsets or row_offsets; nstripes >= 2^32; descriptor arrays of mixed
+ * memory kinds; a bad number in a HOST-side changed; with host arrays a stripe
+ * that does not fit.  Then FEC_ENODEV when no GPU is visible.  nstripes == 0
+ * returns FEC_OK.  A batch whose sizes are all zero launches nothing (host
+ * arrays).  oldb, newb and rows are device memory on one device or page-locked
+ * host memory; pageable memory returns FEC_EINVAL.  The call stages per call,
+ * so it returns FEC_EINVAL while the stream is being captured into a graph.
+ * FEC_FLAG_ASYNC and FEC_FLAG_LIBRARY_STREAM as in fec_repair_batch_ragged;
+ * FEC_FLAG_ROW_PADDING is accepted and ignored.  The rows of different stripes
+ * must not overlap each other or the inputs: the result is then unspecified.
+ *
+ * Every code runs on matupdate_ragged<nchanged, r>: matupdate_reg's unit inside
+ * matapply_ragged's walk.  One column of E per changed block is involved, so the
+ * kernel does not depend on k, and no shape is cut into runs.  A launch takes
+ * at most 8 rows; more run as row groups of 8 over one staging, each re-reading
+ * the inputs.  The kernel XORs into the rows, so a block ends with its byte
+ * tail, never with a last chunk shifted back over its neighbour. */
+int fec_update_batch_ragged(const fec_t* code,
+                            const gf* oldb, const gf* newb, size_t in_bytes, size_t in_block_stride,
+                            const unsigned long long* in_offsets,
+                            gf* rows, size_t row_bytes, size_t row_block_stride,
+                            const unsigned long long* row_offsets,
+                            const unsigned long long* sizes,
+                            const unsigned* block_nums, size_t num_block_nums,
+                            const unsigned* changed, size_t nchanged,
+                            size_t nstripes, void* stream, unsigned flags);
+
 /* Ragged in-place correction: fec_correct_batch over stripes that each have
  * their own size.  The arguments are exactly fec_locate_batch_ragged's, with
  * the arena writable.

@@ -255,6 +255,73 @@ def _ragged_call(coder, fn, data, sizes, offsets, out, out_offsets, nums, r):
     return out, out_offsets
 
 
+def _update_nums(blocknums, k, m, what):
+    """The block numbers of the stored rows of an update (default k..m-1):
+    distinct ints in [0, m-1]."""
+    import numpy as np
+
+    nums = list(range(k, m)) if blocknums is None else list(blocknums)
+    for x in nums:
+        if not isinstance(x, (int, np.integer)) or isinstance(x, bool) or x < 0 or x >= m:
+            raise Error("Precondition violation: %s block nums are required to be in [0, m-1] = "
+                        "[0, %d], but one was %r" % (what, m - 1, x))
+    nums = [int(x) for x in nums]
+    if len(set(nums)) != len(nums):
+        raise Error("Precondition violation: %s block nums are required to be distinct, but got %r" % (what, nums))
+    return nums
+
+
+def _update_changed(changed, ns, k, what):
+    """The `changed` argument of Encoder.update_batch / update_ragged checked:
+    returns (host numbers as a numpy table or None, the device tensor or None,
+    slots per stripe)."""
+    import numpy as np
+
+    # changed: host numbers as a numpy table, device numbers as they are
+    ch = ch_dev = None
+    if hasattr(changed, "data_ptr"):
+        if changed.dtype.is_floating_point or str(changed.dtype) == "torch.bool":
+            raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
+                        "[nstripes, c]")
+        if changed.is_cuda:
+            ch_dev = changed
+            shape = tuple(changed.shape)
+        else:
+            changed = changed.numpy()
+    if ch_dev is None:
+        ch = np.asarray(changed)
+        if ch.size and ch.dtype.kind not in "iu":
+            raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
+                        "[nstripes, c]")
+        shape = ch.shape
+    if len(shape) not in (1, 2) or shape[0] != ns:
+        raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
+                    "[nstripes, c] with nstripes = %d, not %r" % (ns, tuple(shape)))
+    c = 1 if len(shape) == 1 else shape[1]
+    if c < 1 or c > 4:
+        raise Error("Precondition violation: %s takes between 1 and 4 changed blocks per stripe, not %d" % (what, c))
+    if ch_dev is None and ch.size and (ch.min() < -1 or ch.max() >= k):
+        bad = ch[(ch < -1) | (ch >= k)].reshape(-1)[0]
+        raise Error("Precondition violation: changed block nums are required to be primaries in [0, k-1] = "
+                    "[0, %d] or -1 (none), but one was %d" % (k - 1, bad))
+    return ch, ch_dev, c
+
+
+def _update_words(ch, ch_dev, k):
+    """The uint32 words of checked `changed` numbers: (keep-alive, address)."""
+    import numpy as np
+    import torch
+
+    if ch_dev is not None:
+        # whatever is not a primary becomes -1 (the bits of FEC_UPDATE_NONE) before the
+        # narrowing, so that an int64 number like 2^32 + j cannot wrap into the primary j
+        wide = ch_dev.to(torch.int64)
+        words = torch.where((wide < 0) | (wide >= k), torch.full_like(wide, -1), wide).to(torch.int32).contiguous()
+        return words, words.data_ptr()
+    words = np.ascontiguousarray(ch.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    return words, words.ctypes.data
+
+
 def _capi_code(coder):
     code = getattr(coder, "_batch_code", None)
     if code is None:
@@ -473,55 +540,18 @@ class Encoder(_fec.Encoder):
         Afterwards every row holds what encode() gives for its block number on
         the stripe with the new primaries.  Returns parity; the work is
         enqueued on the current stream."""
-        import numpy as np
-
         k, m = self.k, self.m
         is_tensor = type(parity).__module__.startswith("torch") and hasattr(parity, "data_ptr")
         if not is_tensor or str(parity.dtype) != "torch.uint8" or parity.dim() != 3:
             raise Error("Precondition violation: parity is required to be a uint8 device tensor [nstripes, r, sz]")
         ns, r, sz = parity.shape
-        nums = list(range(k, m)) if blocknums is None else list(blocknums)
-        for x in nums:
-            if not isinstance(x, (int, np.integer)) or isinstance(x, bool) or x < 0 or x >= m:
-                raise Error("Precondition violation: update_batch block nums are required to be in [0, m-1] = "
-                            "[0, %d], but one was %r" % (m - 1, x))
-        nums = [int(x) for x in nums]
-        if len(set(nums)) != len(nums):
-            raise Error("Precondition violation: update_batch block nums are required to be distinct, but got %r"
-                        % (nums,))
+        nums = _update_nums(blocknums, k, m, "update_batch")
         if len(nums) != r or r == 0:
             raise Error("Precondition violation: parity is required to hold one row per block num: %d rows, %d block "
                         "nums" % (r, len(nums)))
         if (sz > 1 and parity.stride(2) != 1) or min(parity.stride(0), parity.stride(1)) < 0:
             raise Error("Precondition violation: parity rows are required to be contiguous along sz")
-        # changed: host numbers as a numpy table, device numbers as they are
-        ch_dev = None
-        if hasattr(changed, "data_ptr"):
-            if changed.dtype.is_floating_point or str(changed.dtype) == "torch.bool":
-                raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
-                            "[nstripes, c]")
-            if changed.is_cuda:
-                ch_dev = changed
-                shape = tuple(changed.shape)
-            else:
-                changed = changed.numpy()
-        if ch_dev is None:
-            ch = np.asarray(changed)
-            if ch.size and ch.dtype.kind not in "iu":
-                raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
-                            "[nstripes, c]")
-            shape = ch.shape
-        if len(shape) not in (1, 2) or shape[0] != ns:
-            raise Error("Precondition violation: changed is required to be an integer array [nstripes] or "
-                        "[nstripes, c] with nstripes = %d, not %r" % (ns, tuple(shape)))
-        c = 1 if len(shape) == 1 else shape[1]
-        if c < 1 or c > 4:
-            raise Error("Precondition violation: update_batch takes between 1 and 4 changed blocks per stripe, not %d"
-                        % c)
-        if ch_dev is None and ch.size and (ch.min() < -1 or ch.max() >= k):
-            bad = ch[(ch < -1) | (ch >= k)].reshape(-1)[0]
-            raise Error("Precondition violation: changed block nums are required to be primaries in [0, k-1] = "
-                        "[0, %d] or -1 (none), but one was %d" % (k - 1, bad))
+        ch, ch_dev, c = _update_changed(changed, ns, k, "update_batch")
         for t, what in ((new, "new"), (old, "old")):
             if t is None and what == "old":
                 continue
@@ -548,16 +578,7 @@ class Encoder(_fec.Encoder):
                     old3 is not None and old3.stride() != new3.stride()):
                 new3 = new3.contiguous()
                 old3 = old3.contiguous() if old3 is not None else None
-            if ch_dev is not None:
-                # whatever is not a primary becomes -1 (the bits of FEC_UPDATE_NONE) before the
-                # narrowing, so that an int64 number like 2^32 + j cannot wrap into the primary j
-                wide = ch_dev.to(torch.int64)
-                words = torch.where((wide < 0) | (wide >= k), torch.full_like(wide, -1), wide).to(
-                    torch.int32).contiguous()
-                ch_ptr = words.data_ptr()
-            else:
-                words = np.ascontiguousarray(ch.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
-                ch_ptr = words.ctypes.data
+            words, ch_ptr = _update_words(ch, ch_dev, k)
             from . import capi
 
             # `words` need only outlive the call: host numbers are copied into the
@@ -567,6 +588,94 @@ class Encoder(_fec.Encoder):
                                               new3.stride(1), new3.stride(0), parity.data_ptr(), parity.stride(1),
                                               parity.stride(0), nums, ch_ptr, c, sz, ns,
                                               stream=_stream_handle(parity.device), flags=capi.FEC_FLAG_ASYNC)
+        return parity
+
+    def update_ragged(self, parity, sizes, changed, new, old=None, blocknums=None, offsets=None, in_offsets=None):
+        """update_batch over stripes that each have their own size, in one
+        launch for every code (fec_update_batch_ragged).
+
+        parity, new (and old) are 1-D contiguous uint8 device tensors, arenas
+        of packed objects: row i of stripe s is the sizes[s] bytes from
+        parity[offsets[s] + i * sizes[s]] and holds block blocknums[i]
+        (distinct, in [0, m-1], default k..m-1); input slot j of stripe s is
+        the sizes[s] bytes from new[in_offsets[s] + j * sizes[s]], and from the
+        same place in old.  With old=None new holds the deltas old ^ new.
+        sizes and the offsets are lists, numpy arrays or int64 tensors, all on
+        the host or all on parity's device; the default offsets are the packed
+        layouts r * (cumsum(sizes) - sizes) and c * (cumsum(sizes) - sizes).
+        changed is update_batch's: [nstripes] or [nstripes, c] integers, 1 <= c
+        <= 4, -1 for "none", on the host or on parity's device.
+
+        With descriptors on the device nothing synchronises with the host, and
+        a stripe whose descriptor does not fit is left alone; with descriptors
+        on the CPU such a stripe is an Error.  Returns parity; the work is
+        enqueued on the current stream."""
+        import numpy as np
+        import torch
+
+        k, m = self.k, self.m
+        for t, what in ((parity, "parity"), (new, "new"), (old, "old")):
+            if t is None and what == "old":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+                raise Error("Precondition violation: %s is required to be a 1-D contiguous uint8 device tensor" % what)
+        nums = _update_nums(blocknums, k, m, "update_ragged")
+        r = len(nums)
+        if r == 0:
+            raise Error("Precondition violation: update_ragged block nums are required to name at least one row")
+        arrays = []
+        for a, what in ((sizes, "sizes"), (offsets, "offsets"), (in_offsets, "in_offsets")):
+            if a is None and what != "sizes":
+                continue
+            if isinstance(a, np.ndarray) and a.dtype.kind in "iu" and a.ndim == 1:
+                a = a.tolist()
+            arrays.append((what, _ragged_words(a, what)))
+        sizes = arrays[0][1]
+        ns = sizes.numel()
+        for what, a in arrays[1:]:
+            if a.numel() != ns:
+                raise Error("Precondition violation: %s is required to hold one word per stripe: %d, not %d"
+                            % (what, ns, a.numel()))
+            if a.device != sizes.device:
+                raise Error("Precondition violation: sizes, offsets and in_offsets are required to be all on parity's "
+                            "device or all on the CPU, but sizes is on %s and %s on %s" % (sizes.device, what, a.device))
+        ch, ch_dev, c = _update_changed(changed, ns, k, "update_ragged")
+        if old is not None and old.numel() != new.numel():
+            raise Error("Precondition violation: old is required to be an arena of new's size: %d bytes, not %d"
+                        % (new.numel(), old.numel()))
+        if not parity.is_cuda:
+            raise Error("Precondition violation: parity is required to be a 1-D contiguous uint8 device tensor, not a "
+                        "host tensor")
+        for t, what in ((new, "new"), (old, "old")):
+            if t is not None and t.device != parity.device:
+                raise Error("Precondition violation: %s is required to be on parity's device" % what)
+        if sizes.is_cuda and sizes.device != parity.device:
+            raise Error("Precondition violation: sizes, offsets and in_offsets are required to be all on parity's "
+                        "device or all on the CPU, but sizes is on %s and parity on %s" % (sizes.device, parity.device))
+        if ch_dev is not None and ch_dev.device != parity.device:
+            raise Error("Precondition violation: a device-side changed is required to be on parity's device")
+        if not sizes.is_cuda:
+            for what, a in arrays:
+                if ns and int(a.min()) < 0:
+                    raise Error("Precondition violation: %s is required to hold sizes and offsets in [0, 2^63), but "
+                                "one was %d" % (what, int(a.min())))
+        given = dict(arrays)
+        if "offsets" not in given or "in_offsets" not in given:
+            start = torch.cumsum(sizes, 0) - sizes
+        offsets = given["offsets"] if "offsets" in given else r * start
+        in_offsets = given["in_offsets"] if "in_offsets" in given else c * start
+        if ns and parity.numel() and new.numel():
+            words, ch_ptr = _update_words(ch, ch_dev, k)
+            from . import capi
+
+            # `words` and the descriptor tensors need only outlive the call: host arrays are copied
+            # into the library's staging, device arrays are read by work of this stream
+            with torch.cuda.device(parity.device), _as_error():
+                _capi_code(self).update_batch_ragged(old.data_ptr() if old is not None else 0, new.data_ptr(),
+                                                     new.numel(), 0, in_offsets.data_ptr(), parity.data_ptr(),
+                                                     parity.numel(), 0, offsets.data_ptr(), sizes.data_ptr(), nums,
+                                                     ch_ptr, c, ns, stream=_stream_handle(parity.device),
+                                                     flags=capi.FEC_FLAG_ASYNC)
         return parity
 
     def _encode_device(self, inblocks, desired):

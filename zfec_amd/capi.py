@@ -84,6 +84,8 @@ SYMBOLS = [
     ("fec_correct_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
     ("fec_update_batch", ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _UP, _SZ, _P, _SZ, _SZ, _SZ, _P, _U]),
     ("fec_update_rows", ctypes.c_int, [_P, _UP, _SZ, _U, _P]),
+    ("fec_update_batch_ragged", ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _P, _SZ, _SZ, _P,
+                                               _U]),
 ]
 FEC_LOCATE_CLEAN, FEC_LOCATE_MANY, FEC_LOCATE_UNKNOWN = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD  # fec_locate_batch verdicts
 FEC_LOCATE_NONE = 0xFFFFFFFC  # fec_locate2_batch: the second word of a verdict that is no pair
@@ -356,6 +358,22 @@ class Code(object):
         st = lib().fec_update_batch(self.ptr, oldb or None, newb or None, ibs, iss, rows or None, rbs, rss,
                                     _nums(block_nums), len(block_nums), changed_ptr or None, nchanged, sz, nstripes,
                                     stream or None, flags)
+        if st:
+            check(st)
+
+    def update_batch_ragged(self, oldb, newb, in_bytes, ibs, in_offsets_ptr, rows, row_bytes, rbs, row_offsets_ptr,
+                            sizes_ptr, block_nums, changed_ptr, nchanged, nstripes, stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_update_batch_ragged: update_batch over stripes that each have
+        their own size.  `oldb` is 0 when `newb` holds the deltas; the three
+        `_ptr` descriptor arguments are the addresses of nstripes 8-byte words
+        each, all in host or all in device memory, and `changed_ptr` that of
+        nstripes * nchanged uint32 primary numbers (FEC_UPDATE_NONE for an
+        unused slot) in host or device memory; the caller keeps them alive
+        until the call returns."""
+        st = lib().fec_update_batch_ragged(self.ptr, oldb or None, newb or None, in_bytes, ibs, in_offsets_ptr or None,
+                                           rows or None, row_bytes, rbs, row_offsets_ptr or None, sizes_ptr or None,
+                                           _nums(block_nums), len(block_nums), changed_ptr or None, nchanged, nstripes,
+                                           stream or None, flags)
         if st:
             check(st)
 

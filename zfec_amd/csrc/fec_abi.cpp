@@ -3250,6 +3250,123 @@ FEC_API int fec_repair_batch_ragged(const fec_t* code, const gf* src, size_t src
     });
 }
 
+// ---- ragged update: a size per stripe, changed primaries into the stored rows ---------------
+namespace {
+struct RaggedUpdateCall {
+    const char* fn;
+    const gf *oldb, *newb;
+    size_t in_bytes, ibs;
+    const unsigned long long* ioff;
+    gf* rows;
+    size_t row_bytes, rbs;
+    const unsigned long long* roff;
+    const unsigned long long* sizes;
+    size_t nstripes;
+    void* stream;
+    unsigned flags;
+};
+
+RaggedArgs ragged_update_args(const RaggedUpdateCall& c, size_t nc, size_t nrows) {
+    return RaggedArgs{c.fn,
+                      "%s: sizes, in_offsets and row_offsets are of mixed memory kinds: all three in host memory, or "
+                      "all three in device memory on the blocks' device",
+                      2, {{"the inputs", "in_offsets", "in_bytes", c.in_bytes, c.ibs, nc},
+                                {"the rows", "row_offsets", "row_bytes", c.row_bytes, c.rbs, nrows}},
+                      c.nstripes, c.sizes, {c.ioff, c.roff}};
+}
+
+int run_update_ragged(const RaggedUpdateCall& c, const fec_t* code, const unsigned* block_nums, size_t nrows,
+                      const unsigned* changed, int cdev, size_t nc, int ddev) {
+    const unsigned k = code->k;
+    // device memory on one device, or page-locked host memory (the rows updated in place)
+    const BatchBuf bufs[3] = {{c.newb, c.in_bytes, "newb"}, {c.rows, c.row_bytes, "rows"}, {c.oldb, c.in_bytes, "oldb"}};
+    BatchMem mem;
+    if (resolve_batch(mem, c.fn, bufs, c.oldb ? 3 : 2, "sizes", ddev, c.stream, c.flags, kCaptureRagged))
+        return t_status;
+    if (cdev >= 0 && cdev != mem.dev)
+        return set_status(FEC_EINVAL, "%s: changed lives on device %d, the blocks on device %d", c.fn, cdev, mem.dev);
+    hipStream_t st = mem.st;
+    thread_local std::vector<uint8_t> coefs;
+    coefs.resize(size_t(k) * nrows);
+    for (unsigned j = 0; j < k; ++j)
+        for (size_t i = 0; i < nrows; ++i) coefs[j * nrows + i] = code->enc_matrix[size_t(block_nums[i]) * k + j];
+    RaggedUpdateSpec u;
+    u.k = k;
+    u.nrows = static_cast<uint32_t>(nrows);
+    u.c = static_cast<uint32_t>(nc);
+    u.coefs = coefs.data();
+    u.changed_host = cdev < 0 ? changed : nullptr;
+    u.changed_dev = cdev < 0 ? nullptr : changed;
+    u.oldb = c.oldb ? mem.z[2] : nullptr;
+    u.newb = mem.z[0];
+    u.rows = const_cast<gf*>(mem.z[1]);
+    u.in_bytes = c.in_bytes;
+    u.row_bytes = c.row_bytes;
+    u.in_bstride = c.ibs;
+    u.row_bstride = c.rbs;
+    u.sizes = reinterpret_cast<const uint64_t*>(c.sizes);
+    u.in_off = reinterpret_cast<const uint64_t*>(c.ioff);
+    u.row_off = reinterpret_cast<const uint64_t*>(c.roff);
+    u.desc_host = ddev < 0;
+    u.nstripes = c.nstripes;
+    ++t_launches;
+    hipError_t e = launch_ragged_update(u, st);
+    if (e != hipSuccess) return hip_fail(e, "launch_ragged_update");
+    if (!(c.flags & FEC_FLAG_ASYNC) && (e = hipStreamSynchronize(st)) != hipSuccess)
+        return hip_fail(e, "hipStreamSynchronize");
+    return set_status(FEC_OK);
+}
+}  // namespace
+
+FEC_API int fec_update_batch_ragged(const fec_t* code, const gf* oldb, const gf* newb, size_t in_bytes,
+                                    size_t in_block_stride, const unsigned long long* in_offsets, gf* rows,
+                                    size_t row_bytes, size_t row_block_stride,
+                                    const unsigned long long* row_offsets, const unsigned long long* sizes,
+                                    const unsigned* block_nums, size_t num_block_nums, const unsigned* changed,
+                                    size_t nchanged, size_t nstripes, void* stream, unsigned flags) {
+    const RaggedUpdateCall c{"fec_update_batch_ragged", oldb,        newb,  in_bytes, in_block_stride, in_offsets, rows,
+                             row_bytes,                 row_block_stride, row_offsets, sizes, nstripes,   stream,
+                             flags};
+    // fec_update_batch's checks of the code, the pointers, the rows' numbers and the slot count, in its order
+    const auto update_args = [&]() -> int {
+        if (check_update_rows(
+                code, !newb ? "newb" : !rows ? "rows" : !block_nums ? "block_nums" : !changed ? "changed" : nullptr,
+                block_nums, num_block_nums))
+            return t_status;
+        if (nchanged == 0 || nchanged > kUpdateMaxSlots)
+            return set_status(FEC_EINVAL, "nchanged is %zu: a stripe carries between 1 and %u changed blocks",
+                              nchanged, unsigned(kUpdateMaxSlots));
+        return FEC_OK;
+    };
+    if (update_args()) {
+        const std::string msg = t_msg;
+        return set_status(t_status, "%s: %s", c.fn, msg.c_str());
+    }
+    for (const auto& a : {std::make_pair(static_cast<const void*>(sizes), "sizes"),
+                          std::make_pair(static_cast<const void*>(in_offsets), "in_offsets"),
+                          std::make_pair(static_cast<const void*>(row_offsets), "row_offsets")})
+        if (!a.first) return set_status(FEC_EINVAL, "%s: %s is NULL", c.fn, a.second);
+    if (nstripes == 0) return set_status(FEC_OK);
+    return guarded([&] {
+        int ddev = -1;
+        const RaggedArgs d = ragged_update_args(c, nchanged, num_block_nums);
+        if (check_ragged_kinds(d, &ddev)) return t_status;
+        const int cdev = gpu_available() ? pointer_device(changed) : -1;
+        if (cdev < 0)  // numbers in device memory cannot be checked: the kernel takes a bad one for FEC_UPDATE_NONE
+            for (size_t s = 0; s < nstripes; ++s)
+                for (size_t i = 0; i < nchanged; ++i) {
+                    const unsigned j = changed[s * nchanged + i];
+                    if (j != FEC_UPDATE_NONE && j >= code->k)
+                        return set_status(FEC_EINVAL, "%s: stripe %zu, slot %zu: changed block %u is neither a "
+                                                      "primary (k = %u) nor FEC_UPDATE_NONE", c.fn, s, i, j,
+                                          unsigned(code->k));
+                }
+        if (check_ragged_fit(d, ddev)) return t_status;
+        if (!gpu_available()) return no_gpu();
+        return run_update_ragged(c, code, block_nums, num_block_nums, changed, cdev, nchanged, ddev);
+    });
+}
+
 // ---- pattern plans: the per-pattern work of fec_repair_batch done once --------------------
 // Immutable after fec_repair_plan_new: the host-side rows and masks (the run
 // path) and, in device memory of its own, the records the kernels read.

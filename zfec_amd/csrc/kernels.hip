@@ -22,7 +22,7 @@
 //   matapply_rows<K, R> the same arithmetic, one wave per stripe of short blocks.
 //   matapply_mixed<K>   the same arithmetic, K outputs, each stripe's tables picked
 //                       by its pattern id from a device-side table (scalar loads).
-//   ragged_walk         not a kernel: the walk of the five ragged families below,
+//   ragged_walk         not a kernel: the walk of the six ragged families below,
 //                       every stripe its own size.  A wave walks a short range of
 //                       1 KiB units, finds its stripe by a search over their prefix
 //                       sum (ragged_scan writes it for device-side sizes) and reads
@@ -60,6 +60,9 @@
 //                       size AND a pattern per stripe) and around matcorrect_reg's
 //                       unit, the stripe's verdict read with its descriptor
 //                       (fec_repair_batch_ragged / fec_correct_batch_ragged).
+//   matupdate_ragged<C, R> matupdate_reg's wave step inside ragged_walk, any k: the
+//                       one ragged kernel that XORs into its output, so its
+//                       blocks end with the byte tail (fec_update_batch_ragged).
 //   matapply_lds        any k <= 32, r <= 48 (longer codes are split by the
 //                       caller): each workgroup expands its coefficients into
 //                       LDS tables from a compile-time bank of all 256 values;
@@ -1061,21 +1064,27 @@ __device__ __forceinline__ void ragged_walk(const RaggedDesc<NOFF, WORD>& d, Bod
     }
 }
 
-// chunk_span<kChunk, true> with a 64-bit chunk number (a stripe is not bounded
-// by 2^32 chunks here: its size is whatever the descriptor says).
+// chunk_span<kChunk, OVERLAP> with a 64-bit chunk number (a stripe is not
+// bounded by 2^32 chunks here: its size is whatever the descriptor says).
+template <bool OVERLAP = true>
 __device__ __forceinline__ Span ragged_span(uint64_t c, uint64_t sz, uint64_t nfull) {
     const uint64_t off = c * kChunk;
     if (c < nfull) return Span{off, true, kChunk};
-    if (sz >= kChunk) return Span{sz - kChunk, true, kChunk};
+    if (OVERLAP && sz >= kChunk) return Span{sz - kChunk, true, kChunk};
     return Span{off, false, static_cast<uint32_t>(sz - off)};
 }
 
 // This lane's chunk of unit w of a stripe of sz bytes: chunk w*64 + lane with
 // ragged_span's overlapped last chunk; *live: the stripe has that chunk.
+// OVERLAP = false ends the block with the byte tail instead, as
+// wave_unit<false> does: every byte belongs to exactly one lane of exactly one
+// unit, which a kernel that XORs into its output (matupdate_ragged) needs --
+// the unit before the tail's may be the last of ANOTHER wave's range.
+template <bool OVERLAP = true>
 __device__ __forceinline__ Span ragged_unit(uint64_t w, uint32_t lane, uint64_t sz, bool* live) {
     const uint64_t c = w * 64u + lane;
     *live = c < (sz + kChunk - 1) / kChunk;
-    return ragged_span(c, sz, sz / kChunk);
+    return ragged_span<OVERLAP>(c, sz, sz / kChunk);
 }
 
 // The lane's address of the next row.  The empty asm keeps it a per-lane
@@ -1575,6 +1584,160 @@ __global__ __launch_bounds__(kBlock) void matupdate_reg(const UpdateJob<C, R> jo
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// matupdate_ragged<C, R>: the parity update of a batch whose stripes each have
+// their own size (fec_update_batch_ragged), any k: matupdate_reg's wave step
+// inside ragged_walk.  The records are matupdate_reg's, unchanged (one per
+// primary: a Tab per row of the call, then the live-row mask dwords); the
+// arenas, descriptors and fit test are matrepair_ragged's, the input side over
+// C slots and the row side over ALL the call's rows.  A launch takes rows
+// [row0, row0 + R) of every stripe, row0 a multiple of 8.
+//
+// Per stripe: the C numbers at changed[s * C + c] come by scalar loads and
+// readfirstlane; a slot whose number is not < k is not read (its bit in
+// `slots` stays clear, its table pointer is record 0's: valid, multiplied by
+// x = 0).  The row mask is the OR of the live slots' masks; a row whose bit is
+// clear is neither read nor written, and a stripe with no live row in this
+// launch, one that does not fit either side, or an empty one costs scalar work
+// only.  Numbers, masks and table pointers are formed inside the stripe's own
+// scope: nothing carries from one stripe of a wave's range to the next.
+//
+// Per unit every load -- the live slots' inputs, then the live rows -- is
+// issued before the first store, and each row's tables are read where they are
+// used (the pins on the row's dword offset and on the masks).  Row and slot
+// addresses advance per lane (next_row).
+//
+// The block end is the byte tail (ragged_unit<false>): the kernel XORs into
+// its output, and in this walk the unit that holds the tail of a stripe of
+// 1024 w + t bytes, 0 < t < 16, may be the first of one wave's range while the
+// unit before it is the last of another's.  An overlapped last chunk would
+// read 16 - t bytes that wave has, or has not yet, updated, and apply the
+// delta to them again.  Records, numbers and descriptors are written before
+// the launch, never by this kernel, so the scalar reads are coherent.
+// ---------------------------------------------------------------------------
+struct alignas(16) RaggedUpdateJob {
+    uint64_t in_bstride, row_bstride;  // 0: the stripe's own size (packed objects)
+    uint64_t in_bytes, row_bytes;      // extents of the input arenas (each) and of the row arena
+    uint32_t nstripes;
+    uint32_t rows_all;    // stored rows per stripe of the whole call (the fit test)
+    uint32_t row0;        // this launch takes rows row0 .. row0 + R
+    uint32_t k;           // records (one per primary)
+    uint32_t rec_dwords;  // dwords per record
+    uint32_t tab_off;     // dword offset in a record of this launch's first row
+    uint32_t mask_off;    // dword offset in a record of the mask dword of this launch's rows
+    uint32_t bit0;        // bit in that dword of this launch's first row
+    const uint64_t* ustart;  // nstripes + 1
+    const uint64_t* sizes;
+    const uint64_t* in_off;
+    const uint64_t* row_off;
+    const uint32_t* records;  // k x rec_dwords
+    const uint32_t* changed;  // nstripes x C primary numbers
+    const uint8_t* nw;
+    const uint8_t* od;  // null: nw holds the deltas
+    uint8_t* rows;
+};
+
+template <int C, int R>
+__global__ __launch_bounds__(kBlock) void matupdate_ragged(const RaggedUpdateJob job) {
+    using J = RaggedUpdateJob;
+    const uint32_t lane = threadIdx.x & 63u;
+    const RaggedDesc<2, false> desc{job.nstripes, job.ustart, job.sizes, {job.in_off, job.row_off}, nullptr};
+    ragged_walk(desc, [&](const RaggedStripe<2, false>& cur, uint32_t s, uint64_t u, uint64_t stop) {
+        const uint64_t sz = cur.sz;
+        const uint64_t ib = job.in_bstride ? job.in_bstride : sz, ob = job.row_bstride ? job.row_bstride : sz;
+        // the launch's record geometry is read from the argument segment where a stripe needs
+        // it, not kept in SGPRs across the walk
+        const KPtr<J> kj = kernarg_job<J>();
+        if (u < stop && ragged_fits(cur.off[0], ib, C, sz, job.in_bytes) &&
+            ragged_fits(cur.off[1], ob, job.rows_all, sz, job.row_bytes)) {
+            // this stripe's numbers, table pointers and masks: formed here, dead at the closing brace
+            const CU32 ch = (CU32)kj->changed + size_t(s) * C;
+            const uint32_t nrec = kj->k;
+            CU32 tp[C];
+            uint32_t slots = 0, smask = 0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                tp[c] = (CU32)kj->records + kj->tab_off;
+                const uint32_t j = __builtin_amdgcn_readfirstlane(ch[c]);
+                if (j < nrec) {  // wave-uniform: a scalar branch
+                    const CU32 rp = (CU32)kj->records + size_t(j) * kj->rec_dwords;
+                    smask |= __builtin_amdgcn_readfirstlane(rp[kj->mask_off]);
+                    tp[c] = rp + kj->tab_off;
+                    slots |= 1u << c;
+                }
+                // said to be wave-uniform once more: left to itself the compiler may choose between
+                // the two pointers per lane, and the pin below wants an SGPR pair
+                tp[c] = (CU32)uniform64((uint64_t)tp[c]);
+            }
+            smask = (smask >> kj->bit0) & ((1u << R) - 1u);
+            if (smask != 0u) {  // wave-uniform: a stripe with no live row here is not read
+                // the arenas' bases, as matrepair_ragged's
+                const uint8_t* const nw0 = kj->nw + cur.off[0];
+                const uint8_t* const od0 = kj->od ? kj->od + cur.off[0] : nullptr;
+                uint8_t* const row0 = kj->rows + cur.off[1] + kj->row0 * ob;
+                for (uint64_t w = u - cur.u0, we = stop - cur.u0; w < we; ++w) {
+                    // opaque per unit: the row and slot tests stay bit tests of one SGPR each
+                    uint32_t mask = smask, sl = slots;
+                    asm volatile("" : "+s"(mask), "+s"(sl));
+                    bool live;
+                    const Span sp = ragged_unit<false>(w, lane, sz, &live);
+                    // one pair of lane branches (live, full) around all the loads; inside them the
+                    // slot and row tests are scalar branches.  A dead lane and a none slot hold zeros.
+                    u32x4 x[C], xo[C], y[R];
+#pragma unroll
+                    for (int c = 0; c < C; ++c) x[c] = xo[c] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int r = 0; r < R; ++r) y[r] = u32x4{0u, 0u, 0u, 0u};
+                    const auto load_all = [&](auto ld) {
+                        const uint8_t* in = nw0 + sp.off;
+#pragma unroll
+                        for (int c = 0; c < C; ++c, in = next_row(in, ib))
+                            if ((sl >> c) & 1u) x[c] = ld(in);
+                        if (od0) {  // wave-uniform
+                            in = od0 + sp.off;
+#pragma unroll
+                            for (int c = 0; c < C; ++c, in = next_row(in, ib))
+                                if ((sl >> c) & 1u) xo[c] = ld(in);
+                        }
+                        const uint8_t* row = row0 + sp.off;
+#pragma unroll
+                        for (int r = 0; r < R; ++r, row = next_row(row, ob))
+                            if ((mask >> r) & 1u) y[r] = ld(row);
+                    };
+                    if (live) {
+                        if (sp.full)
+                            load_all([](const uint8_t* p) { return load16(p); });
+                        else
+                            load_all([&](const uint8_t* p) { return load_tail(p, sp.nb); });
+                    }
+#pragma unroll
+                    for (int c = 0; c < C; ++c) x[c] = x[c] ^ xo[c];
+                    Sel sel[4][C];
+                    unit_sel<C>(sel, x);
+                    uint8_t* orow = row0 + sp.off;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        if ((mask >> r) & 1u) {  // wave-uniform: a scalar branch
+                            Tab t[C];
+#pragma unroll
+                            for (int c = 0; c < C; ++c) {
+                                // the row's offset is opaque here, so its tables are read here
+                                uint32_t at = r * 5;
+                                asm volatile("" : "+s"(at));
+                                t[c] = tab_at(tp[c] + at);
+                            }
+                            const u32x4 v{y[r].x ^ gf_dot<C>(t, sel[0]), y[r].y ^ gf_dot<C>(t, sel[1]),
+                                          y[r].z ^ gf_dot<C>(t, sel[2]), y[r].w ^ gf_dot<C>(t, sel[3])};
+                            store_unit(orow, v, live, sp);
+                        }
+                        orow += ob;
+                    }
+                }
+            }
+        }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -5305,6 +5468,21 @@ struct UpdateUpload {
 
 constexpr uint32_t update_rec_dwords(uint32_t nrows) { return (nrows * 5 + (nrows + 31) / 32 + 3) / 4 * 4; }
 
+// The k records of an update at `ht`: record j the tables of coefs[j * nrows + i]
+// for every row i, then the live-row mask dwords, padded to 16 bytes.
+void update_fill_records(uint32_t* ht, const uint8_t* coefs, uint32_t k, uint32_t nrows) {
+    const uint32_t rec_dwords = update_rec_dwords(nrows), mask_off = nrows * 5;
+    for (uint32_t j = 0; j < k; ++j) {
+        uint32_t* rec = ht + size_t(j) * rec_dwords;
+        for (uint32_t i = mask_off; i < rec_dwords; ++i) rec[i] = 0;
+        for (uint32_t i = 0; i < nrows; ++i) {
+            const uint8_t coef = coefs[size_t(j) * nrows + i];
+            host_tab(rec + i * 5, coef);
+            if (coef) rec[mask_off + i / 32] |= 1u << (i % 32);
+        }
+    }
+}
+
 const KrNames g_update_names("matupdate_reg");
 
 // Rows [g0, g0 + R) of every stripe; K is the number of input slots.
@@ -5345,16 +5523,7 @@ hipError_t launch_update_all(const UpdateSpec& p, hipStream_t stream) {
     StagedUpload up;
     hipError_t e = up.acquire(tab_bytes + ch_bytes);
     if (e != hipSuccess) return e;
-    uint32_t* ht = reinterpret_cast<uint32_t*>(up.host());
-    for (uint32_t j = 0; j < p.k; ++j) {
-        uint32_t* rec = ht + size_t(j) * rec_dwords;
-        for (uint32_t i = mask_off; i < rec_dwords; ++i) rec[i] = 0;
-        for (uint32_t i = 0; i < p.nrows; ++i) {
-            const uint8_t coef = p.coefs[size_t(j) * p.nrows + i];
-            host_tab(rec + i * 5, coef);
-            if (coef) rec[mask_off + i / 32] |= 1u << (i % 32);
-        }
-    }
+    update_fill_records(reinterpret_cast<uint32_t*>(up.host()), p.coefs, p.k, p.nrows);
     if (ch_bytes) std::memcpy(up.host() + tab_bytes, p.changed_host, ch_bytes);
     if ((e = up.copy(tab_bytes + ch_bytes, stream)) != hipSuccess) return e;
     UpdateUpload u;
@@ -5682,6 +5851,80 @@ hipError_t launch_ragged_repair_all(const RaggedRepairSpec& p, hipStream_t strea
             rmax = std::max<uint32_t>(rmax, __builtin_popcount((p.masks[q] >> g0) & ((1u << rg) - 1u)));
         if (!rmax) continue;  // rows no pattern stores
         e = g_ragged_repair_launch(k, rg)(p, st.d, g0, ragged_grid(st.units, ragged_units_per_wave(k, rmax)), stream);
+    }
+    st.up.done(stream);
+    return e;
+}
+
+// ---- matupdate_ragged dispatch ----------------------------------------------------------
+const KrNames g_ragged_update_names("matupdate_ragged");
+
+// The staged head of a ragged update: matupdate_reg's k records, then the
+// host-side numbers, each padded to 256 bytes.
+size_t ragged_update_tab_bytes(const RaggedUpdateSpec& p) {
+    return (size_t(p.k) * update_rec_dwords(p.nrows) * 4 + 255) / 256 * 256;
+}
+
+// Rows [g0, g0 + R) of every stripe; K is the number of input slots.
+struct RaggedUpdateKr {
+    template <int K, int R>
+    static hipError_t launch(const RaggedUpdateSpec& p, const RaggedDev& d, uint32_t g0, uint32_t grid,
+                             hipStream_t stream) {
+        RaggedUpdateJob job;
+        job.in_bstride = p.in_bstride;
+        job.row_bstride = p.row_bstride;
+        job.in_bytes = p.in_bytes;
+        job.row_bytes = p.row_bytes;
+        job.nstripes = static_cast<uint32_t>(p.nstripes);
+        job.rows_all = p.nrows;
+        job.row0 = g0;
+        job.k = p.k;
+        job.rec_dwords = update_rec_dwords(p.nrows);
+        job.tab_off = g0 * 5;
+        job.mask_off = p.nrows * 5 + g0 / 32;
+        job.bit0 = g0 % 32;
+        job.ustart = d.ustart;
+        job.sizes = d.sizes;
+        job.in_off = d.off[0];
+        job.row_off = d.off[1];
+        job.records = reinterpret_cast<const uint32_t*>(d.head);
+        job.changed =
+            p.changed_dev ? p.changed_dev : reinterpret_cast<const uint32_t*>(d.head + ragged_update_tab_bytes(p));
+        job.nw = p.newb;
+        job.od = p.oldb;
+        job.rows = p.rows;
+        const hipError_t e =
+            launch_job(reinterpret_cast<const void*>(matupdate_ragged<K, R>), grid, kBlock, 0, stream, job);
+        if (e == hipSuccess) t_last_kernel = g_ragged_update_names.name[K][R];
+        return e;
+    }
+};
+constexpr KrTable<RaggedUpdateKr> g_ragged_update_launch;
+
+// RaggedStage with a head of [records | host-side numbers].  The grid rule is
+// matapply_ragged's over the blocks a unit really moves: c inputs (2 c with old
+// bytes) and the launch's rows twice, read and written.  No row group can be
+// empty: a parity row's coefficients are never zero, and a primary row is live
+// for the stripes that change it.
+hipError_t launch_ragged_update_all(const RaggedUpdateSpec& p, hipStream_t stream) {
+    const uint64_t ns = p.nstripes;
+    const size_t tab_bytes = ragged_update_tab_bytes(p);
+    const size_t ch_bytes = p.changed_host ? (size_t(ns) * p.c * 4 + 255) / 256 * 256 : 0;
+    const auto fill_head = [&](uint8_t* host) {
+        update_fill_records(reinterpret_cast<uint32_t*>(host), p.coefs, p.k, p.nrows);
+        if (ch_bytes) std::memcpy(host + tab_bytes, p.changed_host, size_t(ns) * p.c * 4);
+    };
+    RaggedStage st;
+    hipError_t e = st.stage(p.sizes, {p.in_off, p.row_off}, ns, p.desc_host, std::min(p.in_bytes, p.row_bytes),
+                            std::min(ragged_units_bound(p.in_bytes, p.in_bstride, p.c),
+                                     ragged_units_bound(p.row_bytes, p.row_bstride, p.nrows)),
+                            tab_bytes + ch_bytes, fill_head, stream);
+    if (e != hipSuccess || !st.units) return e;
+    const uint32_t moved_in = p.c * (p.oldb ? 2u : 1u);
+    for (uint32_t g0 = 0; g0 < p.nrows && e == hipSuccess; g0 += kRegR) {
+        const uint32_t rg = std::min<uint32_t>(kRegR, p.nrows - g0);
+        e = g_ragged_update_launch(p.c, rg)(p, st.d, g0, ragged_grid(st.units, ragged_units_per_wave(moved_in, 2 * rg)),
+                                            stream);
     }
     st.up.done(stream);
     return e;
@@ -6265,6 +6508,17 @@ hipError_t launch_ragged_repair(const RaggedRepairSpec& p, hipStream_t stream) {
     if (stream_capturing(stream)) return hipErrorNotSupported;
     reset_signal();
     return launch_ragged_repair_all(p, stream);
+}
+
+hipError_t launch_ragged_update(const RaggedUpdateSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (p.k < 1 || p.nrows < 1 || p.nrows > kUpdateMaxRows || p.c < 1 || p.c > kUpdateMaxSlots || !p.coefs ||
+        (!p.changed_host == !p.changed_dev) || !p.newb || !p.rows || !p.sizes || !p.in_off || !p.row_off ||
+        p.nstripes == 0 || p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    return launch_ragged_update_all(p, stream);
 }
 
 void ragged_scrub_release(const RaggedScrubStaged& t, hipStream_t stream) {

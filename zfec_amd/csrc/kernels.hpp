@@ -486,6 +486,36 @@ struct RaggedRepairSpec {
 };
 hipError_t launch_ragged_repair(const RaggedRepairSpec& p, hipStream_t stream);
 
+// The parity update of such a batch (matupdate_ragged<C, R>, ANY k;
+// fec_update_batch_ragged): the arithmetic, records and numbers of
+// launch_update, the arenas, descriptors, fit rule and units of launch_ragged.
+// Input slot i of stripe s is at newb + in_off[s] + i * B (and at the same
+// offset in oldb, a second arena of in_bytes, where that is non-null), stored
+// row i at rows + row_off[s] + i * B'; the fit test covers c slots and all
+// nrows rows.  A stripe that does not fit, or none of whose numbers is < k, is
+// neither read nor written; a row is read and written only where a live slot's
+// coefficient for it is not zero.  More than 8 rows run as row groups of 8
+// over one staging, each re-reading the inputs.  One staging slot holds the
+// records, host-side numbers and host-side descriptors (one copy), or the
+// records, host-side numbers and ragged_scan's ustart; hipErrorNotSupported
+// under capture.  Every code takes this one path: nothing is cut into runs and
+// nothing synchronises.
+struct RaggedUpdateSpec {
+    uint32_t k, nrows, c;
+    const uint8_t* coefs;  // k x nrows coefficients, as UpdateSpec's (host memory)
+    const uint32_t* changed_host;  // nstripes x c numbers in host memory, or
+    const uint32_t* changed_dev;   // in device memory
+    const uint8_t* oldb;           // the arenas, kernel-visible addresses; oldb may be null
+    const uint8_t* newb;
+    uint8_t* rows;
+    uint64_t in_bytes, row_bytes;
+    uint64_t in_bstride, row_bstride;
+    const uint64_t *sizes, *in_off, *row_off;  // nstripes each
+    bool desc_host;
+    uint64_t nstripes;
+};
+hipError_t launch_ragged_update(const RaggedUpdateSpec& p, hipStream_t stream);
+
 // Whether `stream` is being captured into a HIP graph.  The table forms (a
 // device-side table the host fills and reuses at enqueue time) decline then:
 // a captured graph would replay copies from host slots rewritten since, or
