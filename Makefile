@@ -71,16 +71,17 @@ tsan: build/thread/driver
 
 # The validation paths of the ragged scrub calls (fec_verify_batch_ragged,
 # fec_locate_batch_ragged), of fec_repair_batch_ragged and
-# fec_correct_batch_ragged, and of fec_update_batch_ragged under
+# fec_correct_batch_ragged, of fec_update_batch_ragged, and of
+# fec_locate2_batch_ragged and fec_correct2_batch_ragged under
 # AddressSanitizer and UndefinedBehaviorSanitizer: stand-alone programs,
-# tests/c/ragged_scrub_validate.cpp, tests/c/ragged_repair_validate.cpp and
-# tests/c/ragged_update_validate.cpp, each over the same host objects; no GPU
-# needed.
+# tests/c/ragged_scrub_validate.cpp, tests/c/ragged_repair_validate.cpp,
+# tests/c/ragged_update_validate.cpp and tests/c/ragged_pairs_validate.cpp,
+# each over the same host objects; no GPU needed.
 # The device code is compiled as the library's is (-O3): the sanitizers look at
 # the host code, and the register kernels' SGPR pins do not compile below that.
 VALSRC := $(filter-out tests/c/sanitize_driver.cpp,$(SANSRC))
 
-build/scrub/validate build/update/validate build/repair/validate: build/%/validate: $(VALSRC) \
+build/scrub/validate build/update/validate build/pairs/validate build/repair/validate: build/%/validate: $(VALSRC) \
                                             tests/c/ragged_%_validate.cpp $(SRC)/*.hpp include/zfec_hip.h
 	mkdir -p build/$*
 	set -e; for f in $(VALSRC) tests/c/ragged_$*_validate.cpp; do \
@@ -91,7 +92,8 @@ build/scrub/validate build/update/validate build/repair/validate: build/%/valida
 asan-scrub: build/scrub/validate
 asan-update: build/update/validate
 asan-repair: build/repair/validate
-asan-scrub asan-update asan-repair:
+asan-pairs: build/pairs/validate
+asan-scrub asan-update asan-repair asan-pairs:
 	ASAN_OPTIONS=detect_leaks=0 ./$<
 
 # The no-GPU Python tests of the C-ABI (tests/test_cpu_surface.py: validation,
@@ -114,4 +116,4 @@ clean:
 	rm -f $(SRC)/*.o $(LIB) $(PYEXT)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle ref clean asan tsan asan-py asan-scrub asan-update asan-repair
+.PHONY: all oracle ref clean asan tsan asan-py asan-scrub asan-update asan-repair asan-pairs

@@ -1023,6 +1023,67 @@ int fec_correct_batch_ragged(const fec_t* code,
                              size_t nstripes,
                              unsigned* culprit, void* stream, unsigned flags);
 
+/* Ragged pair location and correction: fec_locate2_batch / fec_correct2_batch
+ * over stripes that each have their own size.  The arguments, their checks and
+ * the order of the checks are fec_locate_batch_ragged's /
+ * fec_correct_batch_ragged's, the messages naming these calls.  culprit holds
+ * two planes as in fec_locate2_batch: words s and nstripes + s belong to
+ * stripe s, 2 * nstripes words in all.
+ *
+ * Per stripe:
+ *   - stripe s gets the two words fec_locate2_batch gives for that stripe alone
+ *     with sz = sizes[s]: rules 1-4 with FEC_LOCATE_NONE in plane 1, and the
+ *     pair (a, b) where rule 5 applies (c >= 4 and nb <= 32).  Outside that the
+ *     words are (fec_locate_batch_ragged's verdict, FEC_LOCATE_NONE) and no
+ *     error is returned;
+ *   - a zero-size stripe is (FEC_LOCATE_CLEAN, FEC_LOCATE_NONE), neither read
+ *     nor written;
+ *   - with descriptor arrays in device memory a stripe that does not fit the
+ *     arena is neither read nor written and gets (FEC_LOCATE_UNFIT,
+ *     FEC_LOCATE_NONE); with host-side arrays it is FEC_EINVAL.
+ * fec_correct2_batch_ragged returns the verdicts of the blocks as they were on
+ * entry.  A single-slot verdict is healed exactly as fec_correct_batch_ragged
+ * heals it; for a pair (a, b) the sizes[s] bytes of slots a and b are rewritten
+ * from the k lowest other slots by fec_correct2_rows' rows.  Nothing else in
+ * caller memory is written: no byte of a CLEAN, MANY, UNKNOWN, UNFIT or
+ * zero-size stripe, no other slot of a healed stripe, no byte past sizes[s] of
+ * a rewritten slot (in a packed object that byte is the next slot's or the
+ * next stripe's).
+ *
+ * Memory kinds, culprit in device memory (in place, FEC_FLAG_ASYNC honoured) or
+ * host memory (gathered and copied back, synchronous), page-locked arenas,
+ * capture (FEC_EINVAL) and nstripes == 0 (FEC_OK) are the siblings'.
+ *
+ * For k <= 4 and 4 <= c <= 8 everything runs in the caller's stream and the
+ * host reads neither a verdict nor the list: the ragged location
+ * (matlocate_ragged<k,c>) with its descriptors staged and kept;
+ * locate2_finish, which writes both planes and the dirty list; ragged_unfit
+ * (device-side descriptors) over plane 0; (correct) matcorrect_ragged<k> for
+ * the single slots; then pairs_locate_ragged, pairs_finish and (correct)
+ * pairs_correct_ragged over the list, each listed stripe's size and offset
+ * read by scalar loads and each kernel making its own fit test.  With k <= 4
+ * and c < 4 the single-block ragged call runs and plane 1 is filled with NONE.
+ * The other shapes (k > 4 or c > 8) are cut into runs of equal consecutive
+ * stripes as fec_locate_batch_ragged cuts them, each run one fec_locate2_batch
+ * / fec_correct2_batch into the whole call's planes.  fec_last_kernel_name()
+ * is pairs_locate_ragged / pairs_correct_ragged where the ragged pair pass
+ * ran, else what the single-block ragged call (or the run's uniform call)
+ * reports. */
+int fec_locate2_batch_ragged(const fec_t* code,
+                             const gf* src, size_t src_bytes, size_t src_block_stride,
+                             const unsigned long long* src_offsets,
+                             const unsigned long long* sizes,
+                             const unsigned* block_nums, size_t num_block_nums,
+                             size_t nstripes,
+                             unsigned* culprit, void* stream, unsigned flags);
+int fec_correct2_batch_ragged(const fec_t* code,
+                              gf* blocks, size_t bytes, size_t block_stride,
+                              const unsigned long long* offsets,
+                              const unsigned long long* sizes,
+                              const unsigned* block_nums, size_t num_block_nums,
+                              size_t nstripes,
+                              unsigned* culprit, void* stream, unsigned flags);
+
 /* Batched calls over several GPUs of this process.  The nstripes stripes are
  * split into contiguous, balanced ranges, one per entry of devices[] (entry d
  * gets stripes [d*q + min(d, e), ...), q = nstripes / ndevices, e = the

@@ -1301,6 +1301,46 @@ class Decoder(_fec.Decoder):
                                                       stream=_stream_handle(data.device))
         return out
 
+    def locate2_ragged(self, data, sizes, blocknums, offsets=None):
+        """locate2_batch over stripes that each have their own size, in one
+        call (fec_locate2_batch_ragged).
+
+        Arguments as locate_ragged.  Returns a torch.int32 tensor
+        [2, nstripes] on the data's device.  Column s is what locate2_batch
+        gives for stripe s alone: (a, b), a < b, the SLOTS of its two corrupt
+        blocks, or (v, LOCATE_NONE) with v what locate_ragged returns,
+        LOCATE_CLEAN for a zero-size stripe and LOCATE_UNFIT (-5) included.
+        Pairs are looked for with nb - k >= 4 checks and nb <= 32 blocks per
+        stripe; other shapes get locate_ragged's verdicts."""
+        return self._scrub2_ragged(data, sizes, blocknums, offsets, "locate2_batch_ragged")
+
+    def correct2_ragged(self, data, sizes, blocknums, offsets=None):
+        """correct2_batch over stripes that each have their own size: scrub,
+        locate and heal up to two blocks per stripe in place, in one call
+        (fec_correct2_batch_ragged).
+
+        Arguments as locate_ragged.  Returns the torch.int32 verdicts
+        [2, nstripes] locate2_ragged would return for the data as it was on
+        entry, and CORRECTS `data` IN PLACE: a single slot exactly as
+        correct_ragged does, and for a pair (a, b) the sizes[s] bytes of slots
+        a and b, from the k lowest other slots of the stripe.  Nothing else is
+        written: no byte of a clean, LOCATE_MANY, LOCATE_UNKNOWN, LOCATE_UNFIT
+        or zero-size stripe, no other slot of a healed stripe, no byte past
+        sizes[s] of a rewritten slot.  The work is enqueued on the current
+        stream."""
+        return self._scrub2_ragged(data, sizes, blocknums, offsets, "correct2_batch_ragged")
+
+    def _scrub2_ragged(self, data, sizes, blocknums, offsets, what):
+        import torch
+
+        nums, ns, szs, offs = self._ragged_scrub_args(data, sizes, blocknums, offsets)
+        out = torch.empty((2, ns), dtype=torch.int32, device=data.device)
+        if ns:
+            with torch.cuda.device(data.device), _as_error():
+                getattr(_capi_code(self), what)(data.data_ptr(), data.numel(), 0, offs.data_ptr(), szs.data_ptr(),
+                                                nums, ns, out.data_ptr(), stream=_stream_handle(data.device))
+        return out
+
     def _ragged_scrub_args(self, data, sizes, blocknums, offsets):
         """The preconditions of verify_ragged / locate_ragged; returns
         (nums, nstripes, sizes, offsets), the two descriptor tensors on one device."""

@@ -82,6 +82,8 @@ SYMBOLS = [
     ("fec_repair_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _UP, _SZ, _SZ, _P, _SZ,
                                                _P, _U]),
     ("fec_correct_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
+    ("fec_locate2_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
+    ("fec_correct2_batch_ragged", ctypes.c_int, [_P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _SZ, _P, _P, _U]),
     ("fec_update_batch", ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _UP, _SZ, _P, _SZ, _SZ, _SZ, _P, _U]),
     ("fec_update_rows", ctypes.c_int, [_P, _UP, _SZ, _U, _P]),
     ("fec_update_batch_ragged", ctypes.c_int, [_P, _P, _P, _SZ, _SZ, _P, _P, _SZ, _SZ, _P, _P, _UP, _SZ, _P, _SZ, _SZ, _P,
@@ -488,6 +490,29 @@ class Code(object):
         place from k other slots of their stripe."""
         st = lib().fec_correct2_batch(self.ptr, blocks, bs, ss, _nums(block_nums), len(block_nums), sz, nstripes,
                                       culprit_ptr or None, stream or None, flags)
+        if st:
+            check(st)
+
+    def locate2_batch_ragged(self, src, src_bytes, sbs, src_offsets_ptr, sizes_ptr, block_nums, nstripes, culprit_ptr,
+                             stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_locate2_batch_ragged: the arguments of locate_batch_ragged;
+        `culprit_ptr` is the address of 2 * nstripes uint32 words in device or
+        host memory, the two planes of locate2_batch (FEC_LOCATE_UNFIT in
+        plane 0 for a device-side descriptor that does not fit)."""
+        st = lib().fec_locate2_batch_ragged(self.ptr, src, src_bytes, sbs, src_offsets_ptr or None, sizes_ptr or None,
+                                            _nums(block_nums), len(block_nums), nstripes, culprit_ptr or None,
+                                            stream or None, flags)
+        if st:
+            check(st)
+
+    def correct2_batch_ragged(self, blocks, nbytes, bs, offsets_ptr, sizes_ptr, block_nums, nstripes, culprit_ptr,
+                              stream=0, flags=FEC_FLAG_ASYNC):
+        """fec_correct2_batch_ragged: the arguments of locate2_batch_ragged,
+        `blocks` writable.  The slot or the two slots a verdict names are
+        rewritten in place, sizes[s] bytes each."""
+        st = lib().fec_correct2_batch_ragged(self.ptr, blocks, nbytes, bs, offsets_ptr or None, sizes_ptr or None,
+                                             _nums(block_nums), len(block_nums), nstripes, culprit_ptr or None,
+                                             stream or None, flags)
         if st:
             check(st)
 

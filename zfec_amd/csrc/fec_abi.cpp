@@ -2295,6 +2295,37 @@ void pair_correct_rows(const uint8_t* P, unsigned k, unsigned a, unsigned b, uin
     rb[n + 1] = f.mul[p0[a]][id];
 }
 
+// The records of a pair pass, for launch_pairs and launch_pairs_ragged: every
+// pair's pivots (pair_pivots) and, with heal, its sources and rows
+// (pair_correct_rows), in pair-index order.  The vectors are the thread's.
+struct PairRecs {
+    const uint8_t* pivots = nullptr;
+    const uint32_t* sources = nullptr;  // null: locate only
+    const uint8_t* crows = nullptr;
+    int build(const uint8_t* P, unsigned k, unsigned c, bool heal, const char* fn) {
+        const unsigned nb = k + c, npairs = nb * (nb - 1) / 2;
+        const size_t pbytes = 2 + 3 * size_t(c - 2);
+        thread_local std::vector<uint8_t> pv, cr;
+        thread_local std::vector<uint32_t> so;
+        pv.resize(npairs * pbytes);
+        if (heal) {
+            so.resize(size_t(npairs) * k);
+            cr.resize(size_t(npairs) * 2 * k);
+        }
+        unsigned p = 0;
+        for (unsigned a = 0; a + 1 < nb; ++a)
+            for (unsigned b = a + 1; b < nb; ++b, ++p) {
+                if (!pair_pivots(P, k, c, a, b, pv.data() + p * pbytes))
+                    return set_status(FEC_ESINGULAR, "%s: slots %u and %u have dependent check columns", fn, a, b);
+                if (heal) pair_correct_rows(P, k, a, b, so.data() + size_t(p) * k, cr.data() + size_t(p) * 2 * k);
+            }
+        pivots = pv.data();
+        sources = heal ? so.data() : nullptr;
+        crows = heal ? cr.data() : nullptr;
+        return FEC_OK;
+    }
+};
+
 // The working words of a call (W = ceil(c/32) + ceil(k/32) per stripe, mismatch
 // bits from bit 0, excluded bits from bit 32*ceil(c/32)) live in the thread's
 // vmask buffer, under run_verify's ev_verify ordering; a host-side culprit is
@@ -2303,9 +2334,14 @@ void pair_correct_rows(const uint8_t* P, unsigned k, unsigned a, unsigned b, uin
 // With `heal` (fec_correct_batch; `fn` names the call in messages) one
 // correction follows locate_finish in the same stream, over the verdict words
 // in device memory: the host never sees them.
+//
+// `plane` (pairs): the words from culprit's plane 0 to its plane 1, 0 for
+// nstripes.  A run of a ragged call passes the whole call's stripe count and
+// culprit + s0, so its words land in the whole call's planes; words gathered
+// for a host-side culprit stay nstripes apart and are copied back per plane.
 int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const unsigned* nums, size_t nb, size_t sz,
                size_t nstripes, unsigned* culprit, void* stream, unsigned flags, const char* fn = "fec_locate_batch",
-               bool heal = false, bool pairs = false) {
+               bool heal = false, bool pairs = false, size_t plane = 0) {
     const unsigned k = code->k, c = static_cast<unsigned>(nb - k), cw = (c + 31) / 32, words = cw + (k + 31) / 32;
     const unsigned xbit = 32 * cw;
     if (nstripes >= (size_t(1) << 32)) return set_status(FEC_EINVAL, "%zu stripes: a call takes fewer than 2^32", nstripes);
@@ -2317,6 +2353,7 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     const size_t out_bytes = nstripes * sizeof(uint32_t) * (pairs ? 2 : 1);
     const size_t pair_words = pass2 ? 1 + nstripes + nstripes * pw : 0;
     const int cdev = pointer_device(culprit);
+    const size_t oplane = cdev >= 0 && plane ? plane : nstripes;  // of the words the kernels write
     // device memory on one device, or page-locked host memory (read in place); sz == 0 reads no block
     const BatchBuf buf = {src, (nstripes - 1) * sss + (nb - 1) * sbs + sz, heal ? "blocks" : "src"};
     BatchMem mem;
@@ -2369,7 +2406,8 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
         // the block-reading kernel stays fec_last_kernel_name()'s answer
         ++t_launches;
         if (pairs) {
-            if ((e = launch_locate2_finish(bits, words, k, c, nstripes, out, list, pairbits, st)) != hipSuccess)
+            if ((e = launch_locate2_finish(bits, words, k, c, nstripes, out, list, pairbits, st, oplane)) !=
+                hipSuccess)
                 rc = hip_fail(e, "launch_locate2_finish");
         } else if ((e = launch_locate_finish(bits, words, k, c, nstripes, out, st)) != hipSuccess) {
             rc = hip_fail(e, "launch_locate_finish");
@@ -2394,31 +2432,16 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
     }
     if (!rc && pass2) {
         // plane 0 still reads MANY for the listed stripes: the pair pass names (a, b) and, with heal, rewrites them
-        const unsigned npairs = static_cast<unsigned>(nb * (nb - 1) / 2);
-        const size_t pbytes = 2 + 3 * size_t(c - 2);
-        thread_local std::vector<uint8_t> pivots, crows;
-        thread_local std::vector<uint32_t> sources;
-        pivots.resize(npairs * pbytes);
-        if (heal) {
-            sources.resize(size_t(npairs) * k);
-            crows.resize(size_t(npairs) * 2 * k);
-        }
-        unsigned p = 0;
-        for (unsigned a = 0; a + 1 < nb; ++a)
-            for (unsigned b = a + 1; b < nb && !rc; ++b, ++p) {
-                if (!pair_pivots(P.data(), k, c, a, b, pivots.data() + p * pbytes))
-                    rc = set_status(FEC_ESINGULAR, "%s: slots %u and %u have dependent check columns", fn, a, b);
-                else if (heal)
-                    pair_correct_rows(P.data(), k, a, b, sources.data() + size_t(p) * k,
-                                      crows.data() + size_t(p) * 2 * k);
-            }
+        PairRecs recs;
+        rc = recs.build(P.data(), k, c, heal, fn);
         PairsSpec ps;
         ps.k = k;
         ps.c = c;
         ps.P = P.data();
-        ps.pivots = pivots.data();
-        ps.sources = heal ? sources.data() : nullptr;
-        ps.crows = heal ? crows.data() : nullptr;
+        ps.pivots = recs.pivots;
+        ps.sources = recs.sources;
+        ps.crows = recs.crows;
+        ps.plane = oplane;
         ps.blocks = const_cast<uint8_t*>(zsrc);
         ps.bstride = sbs;
         ps.sstride = sss;
@@ -2432,8 +2455,15 @@ int run_locate(const fec_t* code, const gf* src, size_t sbs, size_t sss, const u
             if ((e = launch_pairs(ps, st)) != hipSuccess) rc = hip_fail(e, "launch_pairs");
         }
     }
-    if (!rc && cdev < 0 && (e = hipMemcpyAsync(culprit, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
-        rc = hip_fail(e, "hipMemcpyAsync D2H (culprit)");
+    if (!rc && cdev < 0) {
+        // (the caller's planes lie further apart than the gathered ones: one copy per plane)
+        const bool split = pairs && plane && plane != nstripes;
+        if ((e = hipMemcpyAsync(culprit, out, split ? out_bytes / 2 : out_bytes, hipMemcpyDeviceToHost, st)) !=
+                hipSuccess ||
+            (split && (e = hipMemcpyAsync(culprit + plane, out + nstripes, out_bytes / 2, hipMemcpyDeviceToHost,
+                                          st)) != hipSuccess))
+            rc = hip_fail(e, "hipMemcpyAsync D2H (culprit)");
+    }
     order.release();
     if (rc) return rc;
     if ((cdev < 0 || !(flags & FEC_FLAG_ASYNC)) && (e = hipStreamSynchronize(st)) != hipSuccess)
@@ -2486,7 +2516,8 @@ struct ScrubCall {
     unsigned* out;  // mismatch or culprit
     void* stream;
     unsigned flags;
-    bool heal = false;  // fec_correct_batch_ragged: src is the caller's writable blocks
+    bool heal = false;   // fec_correct_batch_ragged: src is the caller's writable blocks
+    bool pairs = false;  // fec_locate2_batch_ragged / fec_correct2_batch_ragged: out is two planes of nstripes words
     const char* arena() const { return heal ? "blocks" : "src"; }
 };
 
@@ -2529,8 +2560,13 @@ int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int 
     const unsigned k = code->k, cc = static_cast<unsigned>(c.nb - k), cw = (cc + 31) / 32;
     const unsigned words = c.locate ? cw + (k + 31) / 32 : cw, xbit = 32 * cw;
     const size_t ns = c.nstripes;
+    // the pair pass (c.pairs implies c.locate): the dirty list, its counter first and cleared with the
+    // working words, and the entries' pair words lie behind the working words, as in run_locate
+    const bool pass2 = c.pairs && pairs_shape_ok(k, cc);
+    const size_t pw = pass2 ? pairs_words(static_cast<uint32_t>(c.nb)) : 0;
+    const size_t pair_words = pass2 ? 1 + ns + ns * pw : 0;
     const size_t work_bytes = ns * words * sizeof(uint32_t);
-    const size_t out_bytes = ns * (c.locate ? 1 : cw) * sizeof(uint32_t);
+    const size_t out_bytes = ns * (c.pairs ? 2 : c.locate ? 1 : cw) * sizeof(uint32_t);
     DevCtx* const d = mem.d;
     hipStream_t st = mem.st;
     hipError_t e;
@@ -2539,13 +2575,17 @@ int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int 
     const bool own = c.locate || rdev < 0;  // words the library owns are in use
     if (own) {
         if (order.acquire()) return t_status;
-        if (ensure_verify_buf(*d, d->vmask, d->vmask_cap, (c.locate ? work_bytes : 0) + (rdev < 0 ? out_bytes : 0)))
+        if (ensure_verify_buf(*d, d->vmask, d->vmask_cap,
+                              (c.locate ? work_bytes + pair_words * sizeof(uint32_t) : 0) +
+                                  (rdev < 0 ? out_bytes : 0)))
             return t_status;
     }
     uint32_t* const vm = static_cast<uint32_t*>(d->vmask);
     uint32_t* const bits = own ? vm : c.out;
-    uint32_t* const out = rdev >= 0 ? c.out : c.locate ? vm + ns * words : vm;
-    if ((e = hipMemsetAsync(bits, 0, work_bytes, st)) != hipSuccess)
+    uint32_t* const list = pass2 ? vm + ns * words : nullptr;
+    uint32_t* const pairbits = pass2 ? list + 1 + ns : nullptr;
+    uint32_t* const out = rdev >= 0 ? c.out : c.locate ? vm + ns * words + pair_words : vm;
+    if ((e = hipMemsetAsync(bits, 0, work_bytes + (pass2 ? sizeof(uint32_t) : 0), st)) != hipSuccess)
         return hip_fail(e, "hipMemsetAsync (result words)");
     thread_local std::vector<uint8_t> P, Q;
     P.resize(size_t(cc) * k);
@@ -2582,16 +2622,23 @@ int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int 
         g.bits = bits;
         g.words = words;
         g.xbit = xbit;
-        g.keep = heal ? &staged : nullptr;
+        g.keep = heal || pass2 ? &staged : nullptr;
         ++t_launches;
         if ((e = launch_ragged_scrub(g, st)) != hipSuccess) rc = hip_fail(e, "launch_ragged_scrub");
     }
     if (!rc && c.locate) {
         // the block-reading kernel stays fec_last_kernel_name()'s answer
         ++t_launches;
-        if ((e = launch_locate_finish(bits, words, k, cc, ns, out, st)) != hipSuccess)
+        if (c.pairs) {
+            // both planes, and (pass2) every MANY stripe onto the dirty list
+            if ((e = launch_locate2_finish(bits, words, k, cc, ns, out, list, pairbits, st)) != hipSuccess)
+                rc = hip_fail(e, "launch_locate2_finish");
+        } else if ((e = launch_locate_finish(bits, words, k, cc, ns, out, st)) != hipSuccess) {
             rc = hip_fail(e, "launch_locate_finish");
-        if (!rc && ddev >= 0) rc = unfit(0, out);  // overwrites the verdict of what was not read
+        }
+        // Overwrites the verdict (plane 0) of what was not read.  Such a stripe has no bit set, so
+        // locate2_finish called it CLEAN and it cannot be on the dirty list: the pair pass never sees it.
+        if (!rc && ddev >= 0) rc = unfit(0, out);
     }
     if (!rc && heal && staged.slot) {
         // row h of the nb x k correction matrix rebuilds slot h, over the verdict words in device
@@ -2611,6 +2658,33 @@ int run_ragged_scrub_fused(const fec_t* code, const ScrubCall& c, int ddev, int 
         cs.staged = staged;
         ++t_launches;
         if ((e = launch_ragged_correct(cs, st)) != hipSuccess) rc = hip_fail(e, "launch_ragged_correct");
+    }
+    if (!rc && pass2 && staged.slot) {
+        // plane 0 still reads MANY for the listed stripes: the pair pass names (a, b) and, with heal,
+        // rewrites them, over the descriptors the location staged.  (No slot: nothing was read, the
+        // list is empty.)  The host reads neither the list nor a verdict.
+        PairRecs recs;
+        rc = recs.build(P.data(), k, cc, c.heal, c.fn);
+        PairsRaggedSpec ps;
+        ps.k = k;
+        ps.c = cc;
+        ps.P = P.data();
+        ps.pivots = recs.pivots;
+        ps.sources = recs.sources;
+        ps.crows = recs.crows;
+        ps.blocks = const_cast<uint8_t*>(mem.z[0]);
+        ps.bytes = c.src_bytes;
+        ps.bstride = c.sbs;
+        ps.sizes = staged.sizes;
+        ps.off = staged.off;
+        ps.nstripes = ns;
+        ps.list = list;
+        ps.pairbits = pairbits;
+        ps.culprit = out;
+        if (!rc) {
+            t_launches += c.heal ? 3 : 2;
+            if ((e = launch_pairs_ragged(ps, st)) != hipSuccess) rc = hip_fail(e, "launch_pairs_ragged");
+        }
     }
     ragged_scrub_release(staged, st);
     if (!rc && rdev < 0 && (e = hipMemcpyAsync(c.out, out, out_bytes, hipMemcpyDeviceToHost, st)) != hipSuccess)
@@ -2648,8 +2722,13 @@ int run_ragged_scrub_runs(const fec_t* code, const ScrubCall& c, int ddev, int r
                                     c.src_bytes, c.locate ? 0 : cc, c.out, st);
             if (e != hipSuccess) return hip_fail(e, "launch_ragged_unfit");
         }
+        // plane 1 of a pair call: NONE everywhere; a run's locate2_finish writes its own stripes again
+        if (c.pairs && (e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.out + ns),
+                                              static_cast<int>(FEC_LOCATE_NONE), ns, st)) != hipSuccess)
+            return hip_fail(e, "hipMemsetD32Async (plane 1)");
     } else {
         std::memset(c.out, fill, out_bytes);
+        if (c.pairs) std::fill(c.out + ns, c.out + 2 * ns, unsigned(FEC_LOCATE_NONE));
         for (size_t s = 0; s < ns; ++s) {
             if (!d.sizes[s] || live(s)) continue;
             if (c.locate)
@@ -2665,7 +2744,7 @@ int run_ragged_scrub_runs(const fec_t* code, const ScrubCall& c, int ddev, int r
                 const size_t sz = d.sizes[s0], bs = c.sbs ? c.sbs : sz;
                 const gf* const src = c.src + d.off[0][s0];
                 return c.locate ? run_locate(code, src, bs, step[0], c.nums, c.nb, sz, s1 - s0, c.out + s0, c.stream,
-                                             jf, c.fn, c.heal)
+                                             jf, c.fn, c.heal, c.pairs, c.pairs ? ns : 0)
                                 : run_verify(code, src, bs, step[0], c.nums, c.nb, sz, s1 - s0, c.out + s0 * cw,
                                              c.stream, jf);
             }))
@@ -2811,6 +2890,25 @@ FEC_API int fec_correct2_batch(const fec_t* code, gf* blocks, size_t block_strid
         return run_locate(code, blocks, block_stride, stripe_stride, block_nums, num_block_nums, sz, nstripes, culprit,
                           stream, flags, "fec_correct2_batch", true, true);
     });
+}
+
+// The ragged forms: the ragged location's checks, paths and staging, two planes and the pair pass behind it.
+FEC_API int fec_locate2_batch_ragged(const fec_t* code, const gf* src, size_t src_bytes, size_t src_block_stride,
+                                     const unsigned long long* src_offsets, const unsigned long long* sizes,
+                                     const unsigned* block_nums, size_t num_block_nums, size_t nstripes,
+                                     unsigned* culprit, void* stream, unsigned flags) {
+    const ScrubCall c{"fec_locate2_batch_ragged", true, src, src_bytes, src_block_stride, src_offsets, sizes,
+                      block_nums, num_block_nums, nstripes, culprit, stream, flags, false, true};
+    return guarded([&] { return ragged_scrub(code, c); });
+}
+
+FEC_API int fec_correct2_batch_ragged(const fec_t* code, gf* blocks, size_t bytes, size_t block_stride,
+                                      const unsigned long long* offsets, const unsigned long long* sizes,
+                                      const unsigned* block_nums, size_t num_block_nums, size_t nstripes,
+                                      unsigned* culprit, void* stream, unsigned flags) {
+    const ScrubCall c{"fec_correct2_batch_ragged", true, blocks, bytes, block_stride, offsets, sizes,
+                      block_nums, num_block_nums, nstripes, culprit, stream, flags, true, true};
+    return guarded([&] { return ragged_scrub(code, c); });
 }
 
 // ---- batched repair: any lost blocks of every stripe -----------------------------------

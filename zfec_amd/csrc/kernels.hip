@@ -48,6 +48,11 @@
 //                       syndromes in LDS, every pair of slots tested against
 //                       them (fec_locate2_batch); pairs_finish names the one
 //                       pair left, pairs_correct rewrites it (fec_correct2_batch).
+//   pairs_locate_ragged, pairs_correct_ragged
+//                       the same two units over the dirty list of a ragged
+//                       location, each listed stripe's size and offset read by
+//                       scalar loads (fec_locate2_batch_ragged /
+//                       fec_correct2_batch_ragged).
 //   matrepair_mixed<K, R> matapply_mixed with R rows per pattern instead of K, each
 //                       row stored only where its pattern's live-row mask says
 //                       so (fec_repair_batch).
@@ -2450,7 +2455,9 @@ struct alignas(16) Finish2Job {
     uint32_t* list;      // [0] the counter, [1 + e] the stripe of entry e
     uint32_t* pairbits;  // pw words per entry
     uint32_t nstripes, k, c, words;
-    uint32_t pw, pad_[3];  // pw == 0: no pair pass
+    uint32_t pw;     // pw == 0: no pair pass
+    uint32_t plane;  // words from plane 0 to plane 1 (a run of a ragged call: the whole call's stripes)
+    uint32_t pad_[2];
 };
 
 __global__ __launch_bounds__(kBlock) void locate2_finish(const Finish2Job job) {
@@ -2458,7 +2465,7 @@ __global__ __launch_bounds__(kBlock) void locate2_finish(const Finish2Job job) {
     if (s >= job.nstripes) return;
     const uint32_t v = finish_verdict(job.bits + size_t(s) * job.words, job.k, job.c);
     job.culprit[s] = v;
-    job.culprit[size_t(job.nstripes) + s] = kLocateNone;
+    job.culprit[size_t(job.plane) + s] = kLocateNone;
     if (v == kLocateMany && job.pw != 0u) {
         const uint32_t e = __hip_atomic_fetch_add(job.list, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         job.list[size_t(1) + e] = s;
@@ -2472,78 +2479,87 @@ struct alignas(16) PairsJob {
     uint64_t bstride, sstride;
     uint32_t k, c, nb;
     uint32_t npairs, pw;   // pw = ceil(npairs / 32)
-    uint32_t pad_;
+    uint32_t plane;        // words from plane 0 to plane 1
     const uint32_t* list;
     uint32_t* pairbits;
-    uint32_t* culprit;       // two planes of nstripes words
+    uint32_t* culprit;       // two planes, `plane` words apart
     const uint32_t* ptabs;   // pairs_locate: P's c * k tables (row-major)
     const uint32_t* recs;    // pairs_locate: npairs records of 2 + 11 (c - 2) dwords;
                              // pairs_correct: npairs records of k + 10 k dwords
     uint8_t* blocks;         // slot 0 of stripe 0
 };
 
+extern __shared__ u32x4 pairs_syn[];  // c rows of 64 lanes
+
+// One unit of the pair location, for pairs_locate and pairs_locate_ragged
+// alike: `base` is this lane's span of slot 0, B the stripe's block stride,
+// `words` the entry's pair words.
+__device__ __forceinline__ void pairs_locate_unit(const uint8_t* base, uint64_t B, bool live, const Span& sp,
+                                                  uint32_t lane, uint32_t k, uint32_t c, uint32_t npairs, CU32 ptabs,
+                                                  CU32 recs, uint32_t* words) {
+    const uint32_t rec = 2u + 11u * (c - 2u);
+    for (uint32_t i = 0; i < c; ++i) pairs_syn[i * 64u + lane] = load_unit(base + (k + i) * B, live, sp);
+    for (uint32_t j = 0; j < k; ++j) {
+        const u32x4 x = load_unit(base + j * B, live, sp);
+        const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
+        for (uint32_t i = 0; i < c; ++i) {
+            const Tab t[1] = {tab_at(ptabs + (size_t(i) * k + j) * 5u)};
+            u32x4 v = pairs_syn[i * 64u + lane];
+            v.x ^= gf_dot<1>(t, z[0]);
+            v.y ^= gf_dot<1>(t, z[1]);
+            v.z ^= gf_dot<1>(t, z[2]);
+            v.w ^= gf_dot<1>(t, z[3]);
+            pairs_syn[i * 64u + lane] = v;
+        }
+    }
+    uint32_t any = 0;
+    for (uint32_t i = 0; i < c; ++i) {
+        const u32x4 v = pairs_syn[i * 64u + lane];
+        any |= v.x | v.y | v.z | v.w;
+    }
+    if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {  // wave-uniform
+        uint32_t refuted = 0;
+        for (uint32_t p = 0; p < npairs; ++p) {
+            const CU32 rp = recs + size_t(p) * rec;
+            const u32x4 s0 = pairs_syn[rp[0] * 64u + lane], s1 = pairs_syn[rp[1] * 64u + lane];
+            const Sel z[4][2] = {{selectors(s0.x), selectors(s1.x)},
+                                 {selectors(s0.y), selectors(s1.y)},
+                                 {selectors(s0.z), selectors(s1.z)},
+                                 {selectors(s0.w), selectors(s1.w)}};
+            for (uint32_t m = 0; m + 2u < c; ++m) {
+                const CU32 q = rp + 2u + 11u * m;
+                const u32x4 si = pairs_syn[q[0] * 64u + lane];
+                const Tab t[2] = {tab_at(q + 1), tab_at(q + 6)};
+                const uint32_t d = (si.x ^ gf_dot<2>(t, z[0])) | (si.y ^ gf_dot<2>(t, z[1])) |
+                                   (si.z ^ gf_dot<2>(t, z[2])) | (si.w ^ gf_dot<2>(t, z[3]));
+                if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) {
+                    refuted |= 1u << (p & 31u);
+                    break;
+                }
+            }
+            if ((p & 31u) == 31u || p + 1u == npairs) {
+                if (refuted != 0u && lane == 0u)
+                    (void)__hip_atomic_fetch_or(words + (p >> 5), refuted, __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT);
+                refuted = 0;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void pairs_locate(const PairsJob job) {
-    extern __shared__ u32x4 pairs_syn[];  // c rows of 64 lanes
     const CU32 list = (CU32)job.list;
     const uint32_t count = list[0];
     WaveWalk it(job.walk, grid_wave<64>());
     if (it.s >= count) return;  // (the empty list: one scalar load)
     const uint32_t lane = threadIdx.x;
-    const uint32_t k = job.k, c = job.c, rec = 2u + 11u * (c - 2u);
     const CU32 ptabs = (CU32)job.ptabs, recs = (CU32)job.recs;
     for (; it.s < count; it.next(job.walk)) {
         const uint32_t e = it.s, s = list[size_t(1) + e];
         bool live;
         const Span sp = wave_unit(job.walk, it.w, lane, &live);
-        const uint8_t* const base = job.blocks + s * job.sstride + sp.off;
-        for (uint32_t i = 0; i < c; ++i) pairs_syn[i * 64u + lane] = load_unit(base + (k + i) * job.bstride, live, sp);
-        for (uint32_t j = 0; j < k; ++j) {
-            const u32x4 x = load_unit(base + j * job.bstride, live, sp);
-            const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
-            for (uint32_t i = 0; i < c; ++i) {
-                const Tab t[1] = {tab_at(ptabs + (size_t(i) * k + j) * 5u)};
-                u32x4 v = pairs_syn[i * 64u + lane];
-                v.x ^= gf_dot<1>(t, z[0]);
-                v.y ^= gf_dot<1>(t, z[1]);
-                v.z ^= gf_dot<1>(t, z[2]);
-                v.w ^= gf_dot<1>(t, z[3]);
-                pairs_syn[i * 64u + lane] = v;
-            }
-        }
-        uint32_t any = 0;
-        for (uint32_t i = 0; i < c; ++i) {
-            const u32x4 v = pairs_syn[i * 64u + lane];
-            any |= v.x | v.y | v.z | v.w;
-        }
-        if (__builtin_amdgcn_ballot_w64(any != 0u) != 0ull) {  // wave-uniform
-            uint32_t* const words = job.pairbits + size_t(e) * job.pw;
-            uint32_t refuted = 0;
-            for (uint32_t p = 0; p < job.npairs; ++p) {
-                const CU32 rp = recs + size_t(p) * rec;
-                const u32x4 s0 = pairs_syn[rp[0] * 64u + lane], s1 = pairs_syn[rp[1] * 64u + lane];
-                const Sel z[4][2] = {{selectors(s0.x), selectors(s1.x)},
-                                     {selectors(s0.y), selectors(s1.y)},
-                                     {selectors(s0.z), selectors(s1.z)},
-                                     {selectors(s0.w), selectors(s1.w)}};
-                for (uint32_t m = 0; m + 2u < c; ++m) {
-                    const CU32 q = rp + 2u + 11u * m;
-                    const u32x4 si = pairs_syn[q[0] * 64u + lane];
-                    const Tab t[2] = {tab_at(q + 1), tab_at(q + 6)};
-                    const uint32_t d = (si.x ^ gf_dot<2>(t, z[0])) | (si.y ^ gf_dot<2>(t, z[1])) |
-                                       (si.z ^ gf_dot<2>(t, z[2])) | (si.w ^ gf_dot<2>(t, z[3]));
-                    if (__builtin_amdgcn_ballot_w64(d != 0u) != 0ull) {
-                        refuted |= 1u << (p & 31u);
-                        break;
-                    }
-                }
-                if ((p & 31u) == 31u || p + 1u == job.npairs) {
-                    if (refuted != 0u && lane == 0u)
-                        (void)__hip_atomic_fetch_or(words + (p >> 5), refuted, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-                    refuted = 0;
-                }
-            }
-        }
+        pairs_locate_unit(job.blocks + s * job.sstride + sp.off, job.bstride, live, sp, lane, job.k, job.c,
+                          job.npairs, ptabs, recs, job.pairbits + size_t(e) * job.pw);
     }
 }
 
@@ -2567,8 +2583,32 @@ __global__ __launch_bounds__(kBlock) void pairs_finish(const PairsJob job) {
             --row;
         }
         job.culprit[s] = a;
-        job.culprit[size_t(job.walk.nstripes) + s] = a + 1u + first;
+        job.culprit[size_t(job.plane) + s] = a + 1u + first;
     }
+}
+
+// One unit of the pair correction, for pairs_correct and pairs_correct_ragged
+// alike: record rp (k source slots, 2 x k tables) applied at `base`, this
+// lane's span of slot 0, B the stripe's block stride.  store_unit writes no
+// byte past the block's end.
+__device__ __forceinline__ void pairs_correct_unit(uint8_t* base, uint64_t B, bool live, const Span& sp, uint32_t k,
+                                                   CU32 rp, uint32_t a, uint32_t b) {
+    u32x4 ya{0u, 0u, 0u, 0u}, yb{0u, 0u, 0u, 0u};
+    for (uint32_t l = 0; l < k; ++l) {
+        const u32x4 x = load_unit(base + rp[l] * B, live, sp);
+        const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
+        const Tab ta[1] = {tab_at(rp + k + 5u * l)}, tb[1] = {tab_at(rp + 6u * k + 5u * l)};
+        ya.x ^= gf_dot<1>(ta, z[0]);
+        ya.y ^= gf_dot<1>(ta, z[1]);
+        ya.z ^= gf_dot<1>(ta, z[2]);
+        ya.w ^= gf_dot<1>(ta, z[3]);
+        yb.x ^= gf_dot<1>(tb, z[0]);
+        yb.y ^= gf_dot<1>(tb, z[1]);
+        yb.z ^= gf_dot<1>(tb, z[2]);
+        yb.w ^= gf_dot<1>(tb, z[3]);
+    }
+    store_unit(base + a * B, ya, live, sp);
+    store_unit(base + b * B, yb, live, sp);
 }
 
 __global__ __launch_bounds__(kBlock) void pairs_correct(const PairsJob job) {
@@ -2581,29 +2621,112 @@ __global__ __launch_bounds__(kBlock) void pairs_correct(const PairsJob job) {
     const CU32 verdict = (CU32)job.culprit, recs = (CU32)job.recs;
     for (; it.s < count; it.next(job.walk)) {
         const uint32_t s = list[size_t(1) + it.s];
-        const uint32_t a = verdict[s], b = verdict[size_t(job.walk.nstripes) + s];
+        const uint32_t a = verdict[s], b = verdict[size_t(job.plane) + s];
         if (a < b && b < job.nb) {  // wave-uniform
             bool live;
             const Span sp = wave_unit(job.walk, it.w, lane, &live);
-            uint8_t* const base = job.blocks + s * job.sstride + sp.off;
             const uint32_t p = a * job.nb - a * (a + 1u) / 2u + (b - a - 1u);
-            const CU32 rp = recs + size_t(p) * (11u * k);
-            u32x4 ya{0u, 0u, 0u, 0u}, yb{0u, 0u, 0u, 0u};
-            for (uint32_t l = 0; l < k; ++l) {
-                const u32x4 x = load_unit(base + rp[l] * job.bstride, live, sp);
-                const Sel z[4][1] = {{selectors(x.x)}, {selectors(x.y)}, {selectors(x.z)}, {selectors(x.w)}};
-                const Tab ta[1] = {tab_at(rp + k + 5u * l)}, tb[1] = {tab_at(rp + 6u * k + 5u * l)};
-                ya.x ^= gf_dot<1>(ta, z[0]);
-                ya.y ^= gf_dot<1>(ta, z[1]);
-                ya.z ^= gf_dot<1>(ta, z[2]);
-                ya.w ^= gf_dot<1>(ta, z[3]);
-                yb.x ^= gf_dot<1>(tb, z[0]);
-                yb.y ^= gf_dot<1>(tb, z[1]);
-                yb.z ^= gf_dot<1>(tb, z[2]);
-                yb.w ^= gf_dot<1>(tb, z[3]);
-            }
-            store_unit(base + a * job.bstride, ya, live, sp);
-            store_unit(base + b * job.bstride, yb, live, sp);
+            pairs_correct_unit(job.blocks + s * job.sstride + sp.off, job.bstride, live, sp, k,
+                               recs + size_t(p) * (11u * k), a, b);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// pairs_locate_ragged / pairs_correct_ragged: pairs_locate / pairs_correct over
+// the dirty list of a batch whose stripes each have their own size
+// (fec_locate2_batch_ragged / fec_correct2_batch_ragged).  The host knows
+// neither the list's length nor, with device-side descriptors, any listed
+// stripe's size, so it fixes the grid and the waves walk work items
+// grid-stride: item i is share i % kPairSplit of entry i / kPairSplit, the
+// units j, j + kPairSplit, ... of that entry's stripe.  A short stripe leaves
+// its higher shares nothing to do (scalar loads and a scalar branch); a long
+// one is spread over kPairSplit waves.  A wave reads the counter by a scalar
+// load first and leaves at once on an empty list.  The entry's stripe, and that
+// stripe's size and offset, come by scalar loads from the arrays the location
+// staged or the caller's device arrays: written before the launch, never by
+// these kernels.  The block stride is bstride ? bstride : sizes[s].
+//
+// Each kernel makes its own fit test over all nb slots (ragged_fits) and does
+// not rely on the verdict, as matcorrect_ragged.  Units are ragged_unit's: the
+// overlapped last chunk for a block of at least 16 bytes, bytes below a chunk.
+// The unit bodies are the uniform kernels' (pairs_locate_unit,
+// pairs_correct_unit): the syndromes' LDS layout, c rows of 64 lanes in which
+// a lane reads only what it wrote, and the relaxed device-scope fetch_or of
+// the refuted pair bits, which here come from several waves and several units
+// of one stripe.  pairs_correct_ragged stores through store_unit
+// (store16_pol<0> / store_tail): no byte past sizes[s] of slots a and b is
+// written.  The targets are never among the sources, so a stripe split between
+// waves, and the two lanes of an overlapped chunk, write identical bytes and
+// read none that are written: no order between them is needed.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kPairSplit = 4;
+
+struct alignas(16) PairsRaggedJob {
+    uint64_t bstride;   // 0: the stripe's own size (packed objects)
+    uint64_t bytes;     // extent of the arena
+    uint32_t nstripes;  // also the words from plane 0 to plane 1
+    uint32_t k, c, nb;
+    uint32_t npairs, pw;
+    const uint64_t* sizes;
+    const uint64_t* off;
+    const uint32_t* list;
+    uint32_t* pairbits;
+    const uint32_t* culprit;  // pairs_correct_ragged: the two planes
+    const uint32_t* ptabs;    // as PairsJob
+    const uint32_t* recs;
+    uint8_t* blocks;  // the arena
+};
+
+__global__ __launch_bounds__(64) void pairs_locate_ragged(const PairsRaggedJob job) {
+    const CU32 list = (CU32)job.list;
+    const uint64_t items = uint64_t(list[0]) * kPairSplit;
+    uint64_t it = blockIdx.x;
+    if (it >= items) return;  // (the empty list: one scalar load)
+    const uint32_t lane = threadIdx.x;
+    const CU32 ptabs = (CU32)job.ptabs, recs = (CU32)job.recs;
+    for (; it < items; it += gridDim.x) {
+        const uint32_t e = static_cast<uint32_t>(it / kPairSplit), j = static_cast<uint32_t>(it % kPairSplit);
+        const uint32_t s = list[size_t(1) + e];
+        if (s >= job.nstripes) continue;
+        const uint64_t sz = ((CU64)job.sizes)[s], off = ((CU64)job.off)[s];
+        const uint64_t B = job.bstride ? job.bstride : sz, nu = ragged_units_of(sz);
+        // wave-uniform: a scalar branch
+        if (j >= nu || !ragged_fits(off, B, job.nb, sz, job.bytes)) continue;
+        const uint8_t* const base = job.blocks + off;
+        uint32_t* const words = job.pairbits + size_t(e) * job.pw;
+        for (uint64_t w = j; w < nu; w += kPairSplit) {
+            bool live;
+            const Span sp = ragged_unit(w, lane, sz, &live);
+            pairs_locate_unit(base + sp.off, B, live, sp, lane, job.k, job.c, job.npairs, ptabs, recs, words);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void pairs_correct_ragged(const PairsRaggedJob job) {
+    const CU32 list = (CU32)job.list;
+    const uint64_t items = uint64_t(list[0]) * kPairSplit;
+    uint64_t it = grid_wave();
+    if (it >= items) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t k = job.k;
+    const CU32 verdict = (CU32)job.culprit, recs = (CU32)job.recs;
+    for (; it < items; it += uint64_t(gridDim.x) * (kBlock / 64)) {
+        const uint32_t e = static_cast<uint32_t>(it / kPairSplit), j = static_cast<uint32_t>(it % kPairSplit);
+        const uint32_t s = list[size_t(1) + e];
+        if (s >= job.nstripes) continue;
+        const uint32_t a = verdict[s], b = verdict[size_t(job.nstripes) + s];
+        if (!(a < b && b < job.nb)) continue;  // wave-uniform: the planes stayed (MANY, NONE)
+        const uint64_t sz = ((CU64)job.sizes)[s], off = ((CU64)job.off)[s];
+        const uint64_t B = job.bstride ? job.bstride : sz, nu = ragged_units_of(sz);
+        if (j >= nu || !ragged_fits(off, B, job.nb, sz, job.bytes)) continue;
+        uint8_t* const base = job.blocks + off;
+        const uint32_t p = a * job.nb - a * (a + 1u) / 2u + (b - a - 1u);
+        const CU32 rp = recs + size_t(p) * (11u * k);
+        for (uint64_t w = j; w < nu; w += kPairSplit) {
+            bool live;
+            const Span sp = ragged_unit(w, lane, sz, &live);
+            pairs_correct_unit(base + sp.off, B, live, sp, k, rp, a, b);
         }
     }
 }
@@ -6331,11 +6454,12 @@ hipError_t launch_correct(const CorrectSpec& p, hipStream_t stream) {
 }
 
 hipError_t launch_locate2_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
-                                 uint32_t* culprit, uint32_t* list, uint32_t* pairbits, hipStream_t stream) {
+                                 uint32_t* culprit, uint32_t* list, uint32_t* pairbits, hipStream_t stream,
+                                 uint64_t plane) {
     std::call_once(g_dispatch_once, init_dispatch);
     if (!bits || !culprit || k < 1 || c < 1 || nstripes == 0 || nstripes >= (1ull << 32) ||
         words != (c + 31) / 32 + (k + 31) / 32 || (list != nullptr) != (pairbits != nullptr) ||
-        (list && !pairs_shape_ok(k, c)))
+        (list && !pairs_shape_ok(k, c)) || (plane && plane < nstripes) || plane >= (1ull << 32))
         return hipErrorInvalidValue;
     Finish2Job job;
     job.bits = bits;
@@ -6347,34 +6471,33 @@ hipError_t launch_locate2_finish(const uint32_t* bits, uint32_t words, uint32_t 
     job.c = c;
     job.words = words;
     job.pw = list ? pairs_words(k + c) : 0u;
-    job.pad_[0] = job.pad_[1] = job.pad_[2] = 0;
+    job.plane = static_cast<uint32_t>(plane ? plane : nstripes);
+    job.pad_[0] = job.pad_[1] = 0;
     const uint32_t grid = static_cast<uint32_t>((nstripes + kBlock - 1) / kBlock);
     return launch_job(reinterpret_cast<const void*>(locate2_finish), grid, kBlock, 0, stream, job);
 }
 
-hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
-    std::call_once(g_dispatch_once, init_dispatch);
-    if (!pairs_shape_ok(p.k, p.c) || !p.P || !p.pivots || (p.sources != nullptr) != (p.crows != nullptr) ||
-        !p.blocks || !p.list || !p.pairbits || !p.culprit || p.sz == 0 || p.nstripes == 0 ||
-        p.nstripes >= (1ull << 32))
-        return hipErrorInvalidValue;
-    if (stream_capturing(stream)) return hipErrorNotSupported;
-    reset_signal();
-    const uint32_t k = p.k, c = p.c, nb = k + c, npairs = nb * (nb - 1) / 2;
-    const bool heal = p.sources != nullptr;
-    // one upload: P's tables, the pairs' location records, then (heal) their correction records
+namespace {
+// The one upload of a pair pass: P's tables, the pairs' location records, then
+// (sources and crows given) their correction records, the latter two at dword
+// offsets *off_loc and *off_cor.
+hipError_t pairs_upload(StagedUpload& up, uint32_t k, uint32_t c, const uint8_t* P, const uint8_t* pivots,
+                        const uint32_t* sources, const uint8_t* crows, hipStream_t stream, size_t* off_loc,
+                        size_t* off_cor) {
+    const uint32_t nb = k + c, npairs = nb * (nb - 1) / 2;
+    const bool heal = sources != nullptr;
     const size_t prec = 2 + 11 * size_t(c - 2), crec = 11 * size_t(k);
-    const size_t off_loc = size_t(c) * k * 5, off_cor = off_loc + npairs * prec;
-    const size_t dwords = off_cor + (heal ? npairs * crec : 0);
-    StagedUpload up;
+    *off_loc = size_t(c) * k * 5;
+    *off_cor = *off_loc + npairs * prec;
+    const size_t dwords = *off_cor + (heal ? npairs * crec : 0);
     hipError_t e = up.acquire(dwords * sizeof(uint32_t));
     if (e != hipSuccess) return e;
     uint32_t* const ht = reinterpret_cast<uint32_t*>(up.host());
-    for (size_t i = 0; i < size_t(c) * k; ++i) host_tab(ht + i * 5, p.P[i]);
+    for (size_t i = 0; i < size_t(c) * k; ++i) host_tab(ht + i * 5, P[i]);
     const size_t pbytes = 2 + 3 * size_t(c - 2);
     for (uint32_t q = 0; q < npairs; ++q) {
-        const uint8_t* src = p.pivots + q * pbytes;
-        uint32_t* dst = ht + off_loc + q * prec;
+        const uint8_t* src = pivots + q * pbytes;
+        uint32_t* dst = ht + *off_loc + q * prec;
         dst[0] = src[0];
         dst[1] = src[1];
         for (uint32_t m = 0; m + 2 < c; ++m) {
@@ -6383,11 +6506,28 @@ hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
             host_tab(dst + 2 + 11 * m + 6, src[2 + 3 * m + 2]);
         }
         if (!heal) continue;
-        dst = ht + off_cor + q * crec;
-        for (uint32_t l = 0; l < k; ++l) dst[l] = p.sources[size_t(q) * k + l];
-        for (uint32_t l = 0; l < 2 * k; ++l) host_tab(dst + k + 5 * l, p.crows[size_t(q) * 2 * k + l]);
+        dst = ht + *off_cor + q * crec;
+        for (uint32_t l = 0; l < k; ++l) dst[l] = sources[size_t(q) * k + l];
+        for (uint32_t l = 0; l < 2 * k; ++l) host_tab(dst + k + 5 * l, crows[size_t(q) * 2 * k + l]);
     }
-    if ((e = up.copy(dwords * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    return up.copy(dwords * sizeof(uint32_t), stream);
+}
+}  // namespace
+
+hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (!pairs_shape_ok(p.k, p.c) || !p.P || !p.pivots || (p.sources != nullptr) != (p.crows != nullptr) ||
+        !p.blocks || !p.list || !p.pairbits || !p.culprit || p.sz == 0 || p.nstripes == 0 ||
+        p.nstripes >= (1ull << 32) || (p.plane && p.plane < p.nstripes) || p.plane >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    const uint32_t k = p.k, c = p.c, nb = k + c, npairs = nb * (nb - 1) / 2;
+    const bool heal = p.sources != nullptr;
+    size_t off_loc, off_cor;
+    StagedUpload up;
+    hipError_t e = pairs_upload(up, k, c, p.P, p.pivots, p.sources, p.crows, stream, &off_loc, &off_cor);
+    if (e != hipSuccess) return e;
     const uint32_t* const dev = reinterpret_cast<const uint32_t*>(up.dev());
     PairsJob job;
     job.bstride = p.bstride;
@@ -6397,7 +6537,7 @@ hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
     job.nb = nb;
     job.npairs = npairs;
     job.pw = pairs_words(nb);
-    job.pad_ = 0;
+    job.plane = static_cast<uint32_t>(p.plane ? p.plane : p.nstripes);
     job.list = p.list;
     job.pairbits = p.pairbits;
     job.culprit = p.culprit;
@@ -6422,6 +6562,75 @@ hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream) {
     }
     up.done(stream);
     if (e == hipSuccess) t_last_kernel = heal ? "pairs_correct" : "pairs_locate";
+    return e;
+}
+
+hipError_t launch_pairs_ragged(const PairsRaggedSpec& p, hipStream_t stream) {
+    std::call_once(g_dispatch_once, init_dispatch);
+    if (!pairs_shape_ok(p.k, p.c) || !p.P || !p.pivots || (p.sources != nullptr) != (p.crows != nullptr) ||
+        !p.blocks || !p.sizes || !p.off || !p.list || !p.pairbits || !p.culprit || p.nstripes == 0 ||
+        p.nstripes >= (1ull << 32))
+        return hipErrorInvalidValue;
+    if (stream_capturing(stream)) return hipErrorNotSupported;
+    reset_signal();
+    const uint32_t k = p.k, c = p.c, nb = k + c, npairs = nb * (nb - 1) / 2;
+    const bool heal = p.sources != nullptr;
+    size_t off_loc, off_cor;
+    StagedUpload up;
+    hipError_t e = pairs_upload(up, k, c, p.P, p.pivots, p.sources, p.crows, stream, &off_loc, &off_cor);
+    if (e != hipSuccess) return e;
+    const uint32_t* const dev = reinterpret_cast<const uint32_t*>(up.dev());
+    PairsRaggedJob rj;
+    rj.bstride = p.bstride;
+    rj.bytes = p.bytes;
+    rj.nstripes = static_cast<uint32_t>(p.nstripes);
+    rj.k = k;
+    rj.c = c;
+    rj.nb = nb;
+    rj.npairs = npairs;
+    rj.pw = pairs_words(nb);
+    rj.sizes = p.sizes;
+    rj.off = p.off;
+    rj.list = p.list;
+    rj.pairbits = p.pairbits;
+    rj.culprit = p.culprit;
+    rj.ptabs = dev;
+    rj.recs = dev + off_loc;
+    rj.blocks = p.blocks;
+    // pairs_finish as it is: of its job it reads the list, the pair words, the planes and their stride
+    PairsJob fj{};
+    fj.k = k;
+    fj.c = c;
+    fj.nb = nb;
+    fj.npairs = npairs;
+    fj.pw = rj.pw;
+    fj.plane = rj.nstripes;
+    fj.list = p.list;
+    fj.pairbits = p.pairbits;
+    fj.culprit = p.culprit;
+    // The host knows neither the list's length nor (device-side descriptors) a
+    // listed stripe's size: the grids are the uniform pair pass's caps, or a wave
+    // per work item where the whole batch has fewer, and the waves walk
+    // grid-stride.  An empty list costs every wave one scalar load.
+    const uint64_t items = p.nstripes * kPairSplit;
+    uint64_t cap = hooked_grid_cap(uint64_t(g_num_cu) * 32);
+    // one wave per workgroup, c KiB of LDS each
+    e = launch_job(reinterpret_cast<const void*>(pairs_locate_ragged), static_cast<uint32_t>(std::min(items, cap)), 64,
+                   size_t(c) * 64 * sizeof(u32x4), stream, rj);
+    if (e == hipSuccess) {
+        const uint64_t need = (p.nstripes + kBlock - 1) / kBlock;
+        cap = hooked_grid_cap(uint64_t(g_num_cu) * 8);
+        e = launch_job(reinterpret_cast<const void*>(pairs_finish), static_cast<uint32_t>(std::min(need, cap)), kBlock,
+                       0, stream, fj);
+    }
+    if (e == hipSuccess && heal) {
+        rj.recs = dev + off_cor;
+        const uint64_t need = (items + kBlock / 64 - 1) / (kBlock / 64);
+        e = launch_job(reinterpret_cast<const void*>(pairs_correct_ragged), static_cast<uint32_t>(std::min(need, cap)),
+                       kBlock, 0, stream, rj);
+    }
+    up.done(stream);
+    if (e == hipSuccess) t_last_kernel = heal ? "pairs_correct_ragged" : "pairs_locate_ragged";
     return e;
 }
 

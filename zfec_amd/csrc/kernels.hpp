@@ -323,11 +323,41 @@ struct PairsSpec {
     uint64_t sz, nstripes;
     const uint32_t* list;
     uint32_t* pairbits;
+    uint32_t* culprit;   // the two planes, device memory
+    uint64_t plane = 0;  // words from plane 0 to plane 1; 0: nstripes
+};
+// `plane`: words from plane 0 to plane 1, 0 for nstripes.  A run of a ragged
+// call writes into the planes of the whole call, which lie further apart.
+hipError_t launch_locate2_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
+                                 uint32_t* culprit, uint32_t* list, uint32_t* pairbits, hipStream_t stream,
+                                 uint64_t plane = 0);
+hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream);
+
+// The pair pass of a batch whose stripes each have their own size
+// (pairs_locate_ragged, pairs_finish, pairs_correct_ragged;
+// fec_locate2_batch_ragged / fec_correct2_batch_ragged), over the list and
+// the planes launch_locate2_finish wrote after a ragged location.  sizes and
+// off are device memory: what the location staged (RaggedScrubStaged) or the
+// caller's arrays.  Slot j of listed stripe s is at blocks + off[s] + j * B,
+// B = bstride or sizes[s] when that is 0; each kernel reads and writes a
+// stripe only where it fits `bytes` by its own test over all k + c slots.
+// Records, upload, fixed grids and the empty list as launch_pairs; the planes
+// are nstripes words apart.
+struct PairsRaggedSpec {
+    uint32_t k, c;
+    const uint8_t* P;         // host memory, as everything down to crows (PairsSpec)
+    const uint8_t* pivots;
+    const uint32_t* sources;  // null: locate only
+    const uint8_t* crows;
+    uint8_t* blocks;          // the arena, a kernel-visible address
+    uint64_t bytes, bstride;
+    const uint64_t *sizes, *off;  // nstripes each, device memory
+    uint64_t nstripes;
+    const uint32_t* list;
+    uint32_t* pairbits;
     uint32_t* culprit;  // the two planes, device memory
 };
-hipError_t launch_locate2_finish(const uint32_t* bits, uint32_t words, uint32_t k, uint32_t c, uint64_t nstripes,
-                                 uint32_t* culprit, uint32_t* list, uint32_t* pairbits, hipStream_t stream);
-hipError_t launch_pairs(const PairsSpec& p, hipStream_t stream);
+hipError_t launch_pairs_ragged(const PairsRaggedSpec& p, hipStream_t stream);
 
 // A batched encode or decode whose stripes each have their own size
 // (matapply_ragged<K, R>, k <= 4; fec_encode_batch_ragged / fec_decode_batch_ragged).
